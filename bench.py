@@ -15,10 +15,17 @@ samples @ 48 kHz per GPU ("scaling": "weak": every rank holds its own 8192-seque
 global batch; --scaling strong splits ONE 8192-sequence batch over the ranks instead).
 Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-Besides the contract fields the line carries its own audit: `parity` (the bench path's y and fused
-gradient at full size against the CPU oracle, checked after the timed region), `value_batch_major`
-(the same step with x handed over as [B,T], the reference scripts' layout) and `kernel_ms` (min /
-median / max of the per-step HIP-event times of the two recurrence kernels).
+A plain run sets up, warms up, times the K steps and prints the line: the contract fields, the step's
+configuration, `kernel_ms` (min / median / max of the HIP-event times of the recurrence kernel(s) of the
+timed steps) and the HBM roofline priced with them.  --full adds the measurements that take runs of
+their own: `parity` (the bench path's y and fused gradient at full size against the CPU oracle, checked
+after the timed region), `value_batch_major` (the same step with x handed over as [B,T], the reference
+scripts' layout), the other scaling curve (N > 1), value_cold, strong_proxy, value_sustained,
+value_fwd_1024, the copy bandwidth beside the roofline and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files: sse [1], grad [4]
+(dL/d{Is, nVt, R, C}), theta [4] (the parameters after that step's update) and y_sample [256, T] (y of
+256 sequences of rank 0's shard, picked with a fixed seed).
 """
 import argparse
 import json
@@ -352,6 +359,8 @@ class Trainer:
         self.adam = None if args.no_optimizer else binding.Adam(
             4, lr=[1e-3 * float(v) for v in th_host], lo=[1e-15, 1e-3, 180.0, 1e-13], hi=[1e-3, 1.0, 1.0e6, 1.0], device=dev)
         self.first_sse = None
+        self.keep_outputs = False      # run(): copy what the last timed step computed (--dump-outputs)
+        self.outputs = None
         self.ev = [binding.Event() for _ in range(4)]
         self.t_fwd, self.t_bwd = [], []
         self.loop_events = []          # (start, stop[, start, stop]) around the recurrence kernel(s) of every 4th timed step
@@ -395,6 +404,15 @@ class Trainer:
                 self.t_bwd.append(ev[2].elapsed_ms(ev[3]))
         return buf[0], buf[1:]
 
+    def last_outputs(self, n_seq=256, seed=2024):
+        """What the step hands its caller, as the last step left it: sse [1], grad [4], theta [4] (after the update) and y of
+        n_seq sequences (a fixed, seeded pick) as [n_seq, T]; float32 host arrays."""
+        st = self.stepper
+        idx = np.sort(np.random.default_rng(seed).choice(st.B, size=min(n_seq, st.B), replace=False))
+        y = st.y[:, torch.as_tensor(idx, device=st.y.device)].t()
+        return {"sse": st.sse.cpu().numpy(), "grad": st.gtheta.cpu().numpy(), "theta": self.theta.cpu().numpy(),
+                "y_sample": y.cpu().numpy()}
+
     def run(self, warmup, steps, dev):
         """W untimed steps, then exactly K steps between barrier + synchronize; max over ranks."""
         n_ev = 2 if self.fused else 4
@@ -433,7 +451,7 @@ class Trainer:
                 torch.cuda.synchronize()
         # Inside the timed region every 4th step carries events (a pair of event records costs the stream ~9 us of dispatch
         # gap: bracketing EVERY step of a 20-step run made the run 8 % slower than the loop it measures); a short run gets
-        # its full sample of kernel durations from a pass of bracketed steps AFTER the closing synchronize.
+        # its full sample of kernel durations from a pass of bracketed steps AFTER the closing synchronize (--full only).
         every = max(1, min(4, steps)) if steps <= 64 else max(4, -(-steps // 1024))
         evs = [[binding.Event() for _ in range(n_ev)] if (i % every == 0 and graph is None) else None for i in range(steps)]
         self.n_in_region = sum(1 for e in evs if e is not None)     # (the first n_in_region entries of t_fwd are the timed region's own)
@@ -453,10 +471,12 @@ class Trainer:
         # the warm-start controller as the TIMED steps left it (the untimed continuation below puts the parameters back afterwards:
         # a jump the controller answers with more warm-up -- not what the timed region ran with)
         self.warm_after_timed = None if self.stepper.warm is None else self.stepper.warm.info()
+        if self.keep_outputs:
+            self.outputs = self.last_outputs()
         if graph is not None:                                  # kernel durations: the warm-up steps' (their last ones: past the cold call)
             evs = [e for e in warm_evs if e is not None][-8:] + evs
             self.n_in_region = 0
-        elif steps <= 64:                                      # (untimed: the same loop continued, every step bracketed)
+        elif steps <= 64 and self.args.full:                   # (untimed: the same loop continued, every step bracketed)
             post = [[binding.Event() for _ in range(n_ev)] for _ in range(steps)]
             keep = [t.clone() for t in ([self.theta] + ([self.adam.m, self.adam.v, self.adam.step] if self.adam is not None else []))]
             for e in post:
@@ -1266,7 +1286,16 @@ def main():
     ap.add_argument("--x-batch-major", action="store_true",
                     help="make the [B,T] layout (the reference scripts') the HEADLINE measurement instead of the engine's "
                          "resident time-major copy")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, the measurements and checks that take runs of their own: parity against the "
+                         "oracle, the other layout, the other scaling curve, the cold step, strong_proxy, the sustained loop, "
+                         "forward-only at 1024 x 4096, copy bandwidth, the CPU baseline, kernel_ms of a short run continued "
+                         "untimed (the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (sse, grad, theta, y_sample; float32)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.config is not None or args.root != "diode"):
+        raise SystemExit("--dump-outputs writes the headline step's outputs: not with --config or --root")
     # auto: replay where it has been exercised on hardware -- one rank (the five-launch MLP-root step; the one-rank RCCL step of
     # --force-dist).  N > 1 launches eagerly by default: a collective inside a captured graph has only ever run on ONE rank
     # (0.1232 eager against 0.1201 ms replayed there: 3 %), and a capture that went wrong on some ranks of a node would hang the
@@ -1344,7 +1373,12 @@ def main():
     tm = not args.x_batch_major
 
     main_run = Trainer(args, x, target, fs, B, T, n_global, world, dev, tm)
+    main_run.keep_outputs = bool(args.dump_outputs) and rank == 0
     dt, loss, grad = main_run.run(args.warmup, args.steps, dev)
+    if main_run.outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in main_run.outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
     ranks = ranks_report(world, dev, main_run.dt_local, args.steps)
     if ranks["ranks_seen"] != world:
@@ -1354,7 +1388,7 @@ def main():
     # contract's default); SURVEY 8e's strong curve -- ONE batch of --batch sequences split over the ranks -- is timed right
     # behind it with the same K / W (at N = 1 the two are the same run)
     companion = None
-    if world > 1 and not args.no_companion and args.loss == "mse":
+    if args.full and world > 1 and not args.no_companion and args.loss == "mse":
         other_kind = "strong" if args.scaling == "weak" else "weak"
         Bg2 = args.batch if other_kind == "strong" else args.batch * world
         c0, c1 = wdist.shard_range(Bg2, rank, world)
@@ -1379,21 +1413,21 @@ def main():
 
     # the other layout, same step, same clock
     other = None
-    if not args.no_batch_major and args.loss == "mse":
+    if args.full and not args.no_batch_major and args.loss == "mse":
         alt = Trainer(args, x, target, fs, B, T, n_global, world, dev, not tm)
         dt_alt, _, _ = alt.run(args.warmup, args.steps, dev)
         other = Bg * T / (dt_alt / args.steps)
         del alt
 
     parity = None
-    if rank == 0 and world == 1 and not args.no_parity and args.loss == "mse":
+    if args.full and rank == 0 and world == 1 and not args.no_parity and args.loss == "mse":
         g_first = None if main_run.first_sse is None else main_run.first_grad.cpu().numpy().astype(np.float64)
         parity = parity_check(stepper, main_run.theta, main_run.xk, x_host, target, fs, n_global, main_run.fused, g_first)
 
     # the STATELESS step: nothing carried from call to call, every chunk warms up from z = 0 (what a loop that presents
     # other data every step gets); same step otherwise, its own autotuned chunk count
     cold = None
-    if not args.no_cold and not args.cold_forward and not args.sequential and main_run.fused:
+    if args.full and not args.no_cold and not args.cold_forward and not args.sequential and main_run.fused:
         cr = Trainer(args, x, target, fs, B, T, n_global, world, dev, tm, cold=True)
         dt_c, _, _ = cr.run(args.warmup, args.steps, dev)
         cold = {"value": Bg * T / (dt_c / args.steps), "ms_per_step": dt_c / args.steps * 1e3,
@@ -1404,7 +1438,8 @@ def main():
     # (its first 1024 sequences), the same step, the same K / W -- what a rank of the 8-GPU strong run computes between two
     # all-reduces (the collective itself -- 20 bytes -- is not in it)
     strong_proxy = None
-    if rank == 0 and world == 1 and not args.no_strong_proxy and args.loss == "mse" and main_run.fused and B % 8 == 0 and B // 8 >= 128:
+    if args.full and rank == 0 and world == 1 and not args.no_strong_proxy and args.loss == "mse" and main_run.fused and \
+            B % 8 == 0 and B // 8 >= 128:
         Bs = B // 8
         xs, ts = x[:Bs].contiguous(), target[:, :Bs].contiguous()
         sp = Trainer(args, xs, ts, fs, Bs, T, n_global, world, dev, tm)
@@ -1433,13 +1468,13 @@ def main():
 
     # the loop kept running (after the headline's burst of a few milliseconds), and BASELINE configs[1] (forward only)
     sustained = fwd1024 = None
-    if rank == 0 and world == 1 and not args.no_sustained and main_run.fused and not args.graph:
+    if args.full and rank == 0 and world == 1 and not args.no_sustained and main_run.fused and not args.graph:
         sustained = sustained_rate(main_run, Bg, T, dt / args.steps * 1e3)
-    if rank == 0 and world == 1 and not args.no_fwd_1024 and args.loss == "mse":
+    if args.full and rank == 0 and world == 1 and not args.no_fwd_1024 and args.loss == "mse":
         fwd1024 = forward_only(args, dev, fs)
 
     if rank == 0:
-        copy_gbs = copy_bandwidth_gbs(dev)
+        copy_gbs = copy_bandwidth_gbs(dev) if args.full else None
         ms_step = dt / args.steps * 1e3
         value = Bg * T / (dt / args.steps)
         t_fwd, t_bwd = main_run.t_fwd, main_run.t_bwd
@@ -1519,7 +1554,7 @@ def main():
             "kernel_ms_in_region": ({"fused_step": spread(f_in)} if fused else {"fwd": spread(f_in), "bwd": spread(b_in)}),
             "kernel_ms_sampling": {"bracketed_in_timed_region": n_in, "all_samples": len(t_fwd),
                                    "note": "kernel_ms_in_region: HIP events around the kernel of every 4th TIMED step (these price the "
-                                           "roofline); kernel_ms: those plus -- for runs of <= 64 steps -- the same loop continued "
+                                           "roofline); kernel_ms: those plus -- with --full, for runs of <= 64 steps -- the same loop continued "
                                            "untimed with every step bracketed (parameters and optimizer state restored afterwards); "
                                            "HIP-graph replay: the warm-up steps' kernels (a replayed step carries no events)"},
             "library": library_identity(),
@@ -1535,7 +1570,7 @@ def main():
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": traffic_src,
                          "algorithmic_bytes_per_sample": dom_bytes, "kernel_ms_used": dom_ms,
-                         "copy_bandwidth": copy_gbs, "frac_of_copy_bandwidth": achieved / copy_gbs},
+                         "copy_bandwidth": copy_gbs, "frac_of_copy_bandwidth": None if copy_gbs is None else achieved / copy_gbs},
         }
         if fused:
             # SURVEY 8(d)'s contract: frac = ALGORITHMIC bytes of forward + backward (24 B/sample) x the samples one launch
@@ -1567,14 +1602,14 @@ def main():
                         "frac_moved": moved / HBM_PEAK_GBS,
                         "frac_traffic": None if traffic is None else traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                         "traffic_over_moved": None if traffic is None else traffic / (BYTES_STEP_MOVED * B * T),
-                        "frac_moved_of_copy_bandwidth": moved / copy_gbs},
+                        "frac_moved_of_copy_bandwidth": None if copy_gbs is None else moved / copy_gbs},
                 "valu": {"frac": None if ach is None else ach / peak, "achieved": ach, "peak": peak,
                          "unit": "G VALU-active cycles/s (chip: 1024 SIMDs x 2.4 GHz)", "source": valu_src, "kind": valu_kind},
                 "practical_bound": "VALU issue: ~110 instructions per two sample-steps (69 packed) at 2 waves per SIMD; valu.frac uses the "
                                    "2.4 GHz peak clock, the chip sustains ~1.9-2.2 GHz under this kernel (sustained.shader_clock_mhz)"})
         else:
             out["roofline"].update({"fwd_kernel_ms": f_ms, "bwd_kernel_ms": b_ms})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(T, fs)
             out["speedup_vs_cpu"] = {"vs_best": value / out["cpu_baseline"]["value"],
                                      "vs_all_cores": value / out["cpu_baseline"]["all_cores"]["value"],

@@ -33,6 +33,8 @@ Goldens:
                         batch_data run on CSV files written by this repo's synthetic-dataset writer
   g9_mlp_relu.npz       clipper_pot.py ClipperModel on a ReLU network (layers.py:63-67): the pretrained 2x16 JSON
                         with its activations switched to "relu" and its weights halved; same arrays as g3
+  g10_reference_models.npz  the model JSON files under wdf_py/diode_clipper/models (all but old/), byte for
+                        byte: `names` (path below models/), `blob` (the files' bytes, concatenated), `ends` (offsets)
   g6_diode_clipper.npz  tf_wdf.py Parallel(ResVs, C) tree + diode-pair root:
                         (a) forward from reference pieces only (tf_wdf elements + diode_pair_func)
                         (b) f64 forward + autograd grads wrt Is, nVt, R, C with a torch
@@ -600,10 +602,26 @@ def g9_mlp_relu():
     np.savez(os.path.join(HERE, "g9_mlp_relu.npz"), **out)
 
 
+def g10_reference_models():
+    root = os.path.join(REF, "wdf_py", "diode_clipper", "models")
+    names, chunks = [], []
+    for dp, dn, fns in sorted(os.walk(root)):
+        dn.sort()
+        if os.path.basename(dp) == "old":
+            continue
+        for fn in sorted(fns):
+            if fn.endswith(".json"):
+                names.append(os.path.relpath(os.path.join(dp, fn), root))
+                chunks.append(np.frombuffer(open(os.path.join(dp, fn), "rb").read(), dtype=np.uint8))
+    print("g10", len(names), "model files,", sum(c.size for c in chunks), "bytes")
+    np.savez_compressed(os.path.join(HERE, "g10_reference_models.npz"), names=np.array(names),
+                        blob=np.concatenate(chunks), ends=np.cumsum([c.size for c in chunks]))
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
     fns = {"g1": g1_rc_lowpass, "g2": g2_voltage_divider, "g3": g3_mlp_clipper,
            "g4": g4_diode_pair, "g5": g5_omega, "g6": g6_diode_clipper, "g7": g7_recorded_programs,
-           "g8": g8_dataimport, "g9": g9_mlp_relu}
+           "g8": g8_dataimport, "g9": g9_mlp_relu, "g10": g10_reference_models}
     for w in which:
         fns[w]()

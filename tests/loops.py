@@ -1,9 +1,8 @@
 """Per-sample loops written by hand for the loop-recorder tests (compat tier): circuits the two
 simple_circuits scripts do NOT contain, driven sample by sample through the drop-in tf_wdf API the way
 a user script would -- set the source, send the waves up and down the tree, read a voltage, write it
-into a TensorArray.  The reference's own script classes are exercised elsewhere: executed in the
-build container (tests/test_trace_cpu.py, AST-extracted from the checkout) and, on the GPU box,
-through the programs recorded from them (tests/golden/g7_recorded_programs.npz)."""
+into a TensorArray.  The reference's own script classes are exercised through the programs recorded
+from them (tests/golden/g7_recorded_programs.npz)."""
 
 
 def unroll(tf, n_steps, one_step):

@@ -17,7 +17,10 @@ def _run(args, env=None, timeout=300):
 
 
 def _clean_env():
-    return {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    # the ranks meet over gloo as on a box without a GPU (on a one-GPU box the second rank would have no device of its own)
+    env.update({"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})
+    return env
 
 
 def test_bench_starts_its_own_ranks_and_counts_them():

@@ -7,7 +7,6 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
-REF = "/root/reference"
 DiodeConfig = namedtuple("DiodeConfig", ["name", "Is", "nabla", "Vt", "N_up", "N_down"])
 D1 = DiodeConfig("1N4148 (1U-1D)", 4.352e-9, 1.906, 25.85e-3, 1, 1)
 
@@ -68,30 +67,29 @@ def test_json_weight_roundtrip(tmp_path):
             assert np.array_equal(l1.kernel.numpy(), l2.kernel.numpy()) and np.array_equal(l1.bias.numpy(), l2.bias.numpy())
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_all_committed_reference_models_load():
-    """Every current-schema JSON under wdf_py/diode_clipper/models (72 files, SURVEY #13) loads."""
+def test_all_committed_reference_models_load(golden):
+    """Every current-schema JSON under wdf_py/diode_clipper/models (72 files, SURVEY #13) loads: the files themselves, as
+    tests/golden/gen_golden.py g10 stored them (all but the legacy schema under old/, unused by the scripts)."""
     from layers import DenseRootModel
     from wdf_hip import mlp_root
-    root = os.path.join(REF, "wdf_py/diode_clipper/models")
+    g = golden("g10_reference_models.npz")
+    blob, ends = g["blob"].tobytes(), [0] + [int(e) for e in g["ends"]]
+    assert len(g["names"]) == len(ends) - 1 >= 60
     n = 0
-    for dp, dn, fns in os.walk(root):
-        if os.path.basename(dp) == "old":
-            continue                                            # legacy schema, unused by the scripts
-        for fn in fns:
-            if fn.endswith(".json"):
-                js = json.load(open(os.path.join(dp, fn)))
-                if "layers" not in js or "in_shape" not in js:
-                    continue
-                dense_shapes = [l["shape"] for l in js["layers"] if l["type"] == "dense"]
-                if not isinstance(js["in_shape"][-1], int) or \
-                        any(not (isinstance(sh, list) and isinstance(sh[-1], int)) for sh in dense_shapes):
-                    continue      # legacy variants (e.g. 1N4148_clipper_pot.json) the reference loader cannot read either
-                m = DenseRootModel(js)
-                dense, hidden, n_tanh = mlp_root.describe(m)
-                assert (hidden in (4, 8, 16) and n_tanh == 3) or (hidden in (4, 8) and n_tanh in (4, 5))
-                assert mlp_root.flat_weights(dense).numel() == 3 * hidden + (n_tanh - 1) * (hidden * hidden + hidden) + hidden + 1
-                n += 1
+    for i, fn in enumerate(g["names"]):
+        assert fn.endswith(".json")
+        js = json.loads(blob[ends[i]:ends[i + 1]])
+        if "layers" not in js or "in_shape" not in js:
+            continue
+        dense_shapes = [l["shape"] for l in js["layers"] if l["type"] == "dense"]
+        if not isinstance(js["in_shape"][-1], int) or \
+                any(not (isinstance(sh, list) and isinstance(sh[-1], int)) for sh in dense_shapes):
+            continue      # legacy variants (e.g. 1N4148_clipper_pot.json) the reference loader cannot read either
+        m = DenseRootModel(js)
+        dense, hidden, n_tanh = mlp_root.describe(m)
+        assert (hidden in (4, 8, 16) and n_tanh == 3) or (hidden in (4, 8) and n_tanh in (4, 5))
+        assert mlp_root.flat_weights(dense).numel() == 3 * hidden + (n_tanh - 1) * (hidden * hidden + hidden) + hidden + 1
+        n += 1
     assert n >= 60
 
 

@@ -90,7 +90,7 @@ def test_bench_two_rank_path_rehearsal():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--batch", "1024", "--seq-len", "2048", "--rehearse-on-one-gpu"]
+           "--batch", "1024", "--seq-len", "2048", "--rehearse-on-one-gpu", "--full"]
     out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -122,7 +122,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     here (one-GPU box); on a node with N GPUs the same entry point runs one rank per GPU over RCCL."""
     env_clean = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     d = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "1024", "--seq-len", "2048", "--rehearse-on-one-gpu",
-                    "--no-batch-major"], env=env_clean)
+                    "--full", "--no-batch-major"], env=env_clean)
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["ranks"]["world_size"] == 2
     assert "started the ranks itself" in d["ranks"]["launcher"]
     assert d["scaling"] == "weak" and d["config"]["global_batch"] == 2048
@@ -149,12 +149,27 @@ def _run_bench(extra, launcher=None, timeout=900, env=None):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run times the headline step only (no parity, no second layout, no CPU leg) and --dump-outputs writes what
+    its last timed step computed: float32 arrays, the seeded sample of y included, the loss matching the line's."""
+    d = _run_bench(["--steps", "3", "--warmup", "1", "--batch", "1024", "--seq-len", "2048", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "samples/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 1024 * 2048 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["parity"] is None and d["value_batch_major"] is None and d["value_cold"] is None and "cpu_baseline" not in d
+    out = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(out) == {"sse", "grad", "theta", "y_sample"} and all(a.dtype == np.float32 for a in out.values())
+    assert out["sse"].shape == (1,) and out["grad"].shape == (4,) and out["theta"].shape == (4,)
+    assert out["y_sample"].shape == (256, 2048) and np.all(np.isfinite(out["y_sample"])) and np.max(np.abs(out["y_sample"])) > 0
+    assert abs(float(out["sse"][0]) / (1024 * 2048) - d["config"]["optimizer"]["loss_last_step"]) < 1e-6 * d["config"]["optimizer"]["loss_last_step"]
+    assert np.allclose(out["theta"], d["config"]["optimizer"]["theta_final"], rtol=1e-6)
+
+
 def test_bench_force_dist_runs_the_rccl_branch():
     """bench.py --force-dist: a one-rank nccl (= RCCL) process group, the fused [SSE, grads] device buffer
     all-reduced on it every step, Adam as its own launch afterwards -- the N > 1 step on the one GPU of the
     test box.  Same numbers as the folded single-rank step (the all-reduce of one rank is the identity)."""
     common = ["--steps", "6", "--warmup", "2", "--batch", "2048", "--seq-len", "2048", "--plan", "8,192,16",
-              "--no-cpu-baseline", "--no-batch-major"]
+              "--full", "--no-cpu-baseline", "--no-batch-major"]
     d = _run_bench(common + ["--force-dist"])
     ref = _run_bench(common)
     assert "RCCL" in d["config"]["collective"] and ref["config"]["collective"] is None
@@ -179,7 +194,7 @@ def test_bench_strong_scaling_rehearsal():
     launcher = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(port)]
     d = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "2048", "--seq-len", "2048", "--scaling", "strong",
-                    "--rehearse-on-one-gpu", "--no-batch-major"], launcher=launcher)
+                    "--rehearse-on-one-gpu", "--full", "--no-batch-major"], launcher=launcher)
     assert d["scaling"] == "strong" and d["config"]["global_batch"] == 2048 and d["config"]["parallelism"] == "dp2"
     assert "1024 sequences" in d["config"]["workload"] and d["ranks_seen"] == 2
     assert d["scaling_curves"]["weak"]["global_batch"] == 4096 and d["scaling_curves"]["strong"]["value"] == d["value"]

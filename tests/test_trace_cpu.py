@@ -1,8 +1,6 @@
 """CPU: the loop recorder turns a reference-style per-sample loop into the same state-space
 matrices the Circuit probe derives -- checked with the kernel launch replaced by a capture
 (no compute here; the GPU suite runs the real thing)."""
-import ast
-import os
 
 import numpy as np
 import pytest
@@ -10,7 +8,6 @@ import pytest
 torch = pytest.importorskip("torch")
 
 FS = 48000
-REF = "/root/reference"
 
 
 class Captured(Exception):
@@ -85,33 +82,13 @@ def test_recorder_rejects_nonuniform_loops(capture):
     trace._current = None
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-@pytest.mark.parametrize("script,probe", [("wdf_py/simple_circuits/lpf.py", "C1"),
-                                          ("wdf_py/simple_circuits/voltage_divider.py", "R1")])
-def test_reference_model_classes_run_unchanged(capture, script, probe):
-    """The reference's own Model class (AST-extracted from the script, nothing edited) records
-    and lowers through the drop-in tf_wdf."""
-    import tf_wdf as wdf
-    tree = ast.parse(open(os.path.join(REF, script)).read())
-    cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "Model"]
-    ns = {"tf": wdf.tf, "wdf": wdf, "FS": FS}
-    exec(compile(ast.Module(cls, []), script, "exec"), ns)
-    m = ns["Model"]()
-    x = np.random.default_rng(1).standard_normal((1, 64))
-    out = m.forward(x)
-    assert tuple(out.shape) == (64, 1, 1)
-    ref, _ = wdf.Circuit(m.I1, m.Vs, getattr(m, probe)).matrices()
-    assert torch.allclose(capture["coef"].double(), ref, rtol=1e-6, atol=1e-9)
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_reference_clipper_model_runs_unchanged(monkeypatch):
-    """clipper_pot.py's own ClipperModel (AST-extracted, unedited) with a committed reference
-    weight file: the recorder recognises the per-sample-R clipper loop and hands it to the
-    MLP-root kernel (captured here)."""
+def test_clipper_loop_with_a_reference_weight_file_lowers_to_the_mlp_kernel(monkeypatch, golden):
+    """The pot clipper loop (tests/loops.py PotClipper) with one of the reference's committed weight files (2x16, stored by
+    tests/golden/gen_golden.py g10): the recorder recognises the per-sample-R clipper loop and hands it to the MLP-root
+    kernel (captured here)."""
     import json
     import tf_wdf as wdf
-    from layers import DenseRootModel
+    from loops import PotClipper
     from wdf_hip import mlp_root, trace
     got = {}
 
@@ -124,17 +101,15 @@ def test_reference_clipper_model_runs_unchanged(monkeypatch):
 
     monkeypatch.setattr(trace, "_device", lambda: torch.device("cpu"))
     monkeypatch.setattr(mlp_root._ClipperMlpFn, "apply", FakeFn.apply)
-    script = "wdf_py/diode_clipper/clipper_pot.py"
-    tree = ast.parse(open(os.path.join(REF, script)).read())
-    cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "ClipperModel"]
-    ns = {"tf": wdf.tf, "wdf": wdf, "FS": FS, "C_val": 4.7e-9, "DenseRootModel": DenseRootModel}
-    exec(compile(ast.Module(cls, []), script, "exec"), ns)
-    mj = json.load(open(os.path.join(REF, "wdf_py/diode_clipper/models/1N4148 (1U-1D)_2x16_training_2000.json")))
-    model = ns["ClipperModel"](mj)
+    g = golden("g10_reference_models.npz")
+    names, ends = list(g["names"]), [0] + [int(e) for e in g["ends"]]
+    i = names.index("1N4148 (1U-1D)_2x16_training_2000.json")
+    mj = json.loads(g["blob"].tobytes()[ends[i]:ends[i + 1]])
+    model = PotClipper(wdf, FS, 4.7e-9, mlp_json=mj)
     B, T = 3, 20
     rng = np.random.default_rng(2)
     data = np.stack([rng.standard_normal((B, T)), np.full((B, T), 25.2e3)], axis=-1)     # [B,T,2]
-    out = model.forward(data)
+    out = model.run(data)
     assert tuple(out.shape) == (T, B, 1, 1)                              # clipper_pot.py:126
     assert got["hidden"] == 16 and got["n_tanh"] == 3 and got["w"].numel() == 609
     assert torch.allclose(got["x"].double(), torch.as_tensor(data[:, :, 0]), atol=1e-6)
