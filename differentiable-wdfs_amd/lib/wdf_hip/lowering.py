@@ -325,6 +325,7 @@ _LIN_OCC = int(os.environ.get("WDF_LIN_OCC", "2"))       # chunks are cut so tha
 _NL_OCC = int(os.environ.get("WDF_NL_OCC", "1"))
 _NL_WMIN = int(os.environ.get("WDF_NL_WMIN", "16"))      # the shortest warm-up the device's controller may settle on
 _ROWS = 1024                                             # result rows per slab (see _LinResident.entry)
+_DYN_CHAN_ENTRIES = 8                                    # _run_dyn's per-sequence answers kept (each holds its input)
 NL_TOL = 1.0e-6                                          # boundary tolerance of the diode-root one-pass step (plan_ss_time_parallel's)
 
 
@@ -595,6 +596,7 @@ class _DynResident:
                         raise binding.WdfHipError("Circuit.to_device: this network's weights already live in another circuit's vector")
                     with torch.no_grad():
                         v.data = self.w[o:o + n].view(v.shape)
+                    v._wdf_flat = (self, o, n)
                     o += n
 
 
@@ -912,8 +914,10 @@ class Circuit:
         call starts from the states the PREVIOUS carry_state call on this circuit ended in (zero the first time) -- lpf.py:30-49
         never resets C1, so its epoch n starts where epoch n - 1 ended; the state handed over is a constant of the new call
         (the reference's stored tensor belongs to the previous tape).  `circ.last_state` [ns,B] is what the call ended in
-        (set whenever z0 / carry_state is used); `circ.reset_state()` forgets it.  A resident linear tree runs this inside the
-        one-pass step (wdf_ss_lin_step_mse's z0 / zT); every other circuit composes it from __call__(x, z0, return_state)."""
+        (set whenever z0 / carry_state is used; a tensor of its own that later calls leave alone); `circ.reset_state()` forgets
+        it.  A resident linear tree runs this inside the one-pass step (wdf_ss_lin_step_mse's z0 / zT); every other circuit
+        composes it from __call__(x, z0, return_state).  `circ.last_output` [T,B] is the call's y; on a resident tree it is the
+        batch's own output buffer, valid until the next call on the same (x, target) -- clone it to keep it longer."""
         binding.require_gpu()
         stateful = z0 is not None or carry_state
         if carry_state and z0 is None:
@@ -940,7 +944,7 @@ class Circuit:
             loss._wdf_fused = (out, {id(v): i for i, v in live})
             self.last_output = ent["y"]                          # the forward's y [T,B] of this call (TensorArray.stack() layout)
             if stateful:
-                self.last_state = ent["zT"]
+                self.last_state = ent["zT"].clone()              # (ent["zT"] is one of two ping-pong buffers: [ns,B], kept by value)
             return loss
         if stateful:
             y, zT = self(x, z0=z0, return_state=True)
@@ -1133,12 +1137,15 @@ class Circuit:
         # A pot that keeps its value along every sequence (the reference's recordings: dataimport.py:96 repeats the file's
         # resistance down the whole channel, batch_data cuts sequences out of it): calc_impedance gives ONE row per sequence --
         # the tape runs over B values instead of B x T, the kernels read rows [1,n,B] and the sweep sums dL/d(row) over the
-        # steps itself.  Looked at once per input tensor (one comparison pass, cached on the storage).
+        # steps itself.  Looked at once per input tensor (one comparison pass, cached on the storage).  Every answer kept also
+        # keeps the caller's tensor (_dyn_chan_held, same keys): the address cannot be handed to other data -- a pot that
+        # moves -- while its answer is in the cache; at most _DYN_CHAN_ENTRIES of them, the oldest out first.
         per_seq = False
         if chan >= 0 and not x.requires_grad and T > 1 and getattr(self, "per_sequence_rows", True):
             with torch._C.DisableTorchFunctionSubclass():
                 ckey = tensor_key(self._anchor) if isinstance(getattr(self, "_anchor", None), torch.Tensor) else None
             cache = self.__dict__.setdefault("_dyn_chan_const", {})
+            held = self.__dict__.setdefault("_dyn_chan_held", {})
             if ckey is not None and ckey in cache:
                 per_seq = cache[ckey]
             else:
@@ -1146,9 +1153,11 @@ class Circuit:
                     rch = x[:, :, self.ni]
                     per_seq = bool((rch == rch[:, :1]).all())
                 if ckey is not None:
-                    if len(cache) > 16:
-                        cache.clear()
-                    cache[ckey] = per_seq
+                    while len(cache) >= _DYN_CHAN_ENTRIES:
+                        old = next(iter(cache))
+                        del cache[old]
+                        held.pop(old, None)
+                    cache[ckey], held[ckey] = per_seq, self._anchor
         vals = []
         for i, (e, n) in enumerate(params):
             if i == chan:
