@@ -6,11 +6,12 @@ missing or a call fails, this raises -- the product never computes on the CPU.
 """
 import ctypes as C
 import os
-import weakref
 
 import numpy as np
 
 import torch
+
+from .tensor_cache import ObjectMemo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # WDF_HIP_LIB: another build of the same library (A/B timing of kernel variants on one box)
@@ -506,36 +507,26 @@ def clipper_bwd_mse_tp_adam(x, theta, fs, zstash, zT, target, gscale, n_chunks, 
     return gtheta, sse
 
 
-_R_SEQ_CACHE = {}       # (id(r), layout) -> (weakref to r, version, bool)
+_R_SEQ_CACHE = ObjectMemo(64)       # (r, layout) -> bool
 R_PER_SEQUENCE = os.environ.get("WDF_R_PER_SEQUENCE", "1") not in ("", "0")     # (0: always the per-sample evaluation, for A/B runs and tests)
 
 
 def r_is_per_sequence(r, time_major):
     """Is the resistance channel constant along every sequence (the reference's recordings: one pot value per file,
-    dataimport.py:96 -- batch_data cuts the sequences out of it)?  One comparison pass per tensor OBJECT and version, cached
-    (engine.resistance_max's rule): the one-pass step then evaluates calc_impedance once per chunk instead of every step
-    (WDF_R_PER_SEQUENCE).  Not keyed on the address: a fresh tensor the allocator puts where a freed one was (a loop that builds
-    every batch's channel anew) may hold a pot that moves, and a False hit there would freeze it along every chunk.  The entry
-    holds a weak reference only, so no device memory is kept.  A miss during stream capture answers False (the per-sample path
-    is exact for every channel) and caches nothing: the comparison would have to synchronise."""
+    dataimport.py:96 -- batch_data cuts the sequences out of it)?  One comparison pass per tensor OBJECT and version
+    (tensor_cache.ObjectMemo: a fresh channel at a freed one's address may hold a pot that moves): the one-pass step then
+    evaluates calc_impedance once per chunk instead of every step (WDF_R_PER_SEQUENCE).  A miss during stream capture answers
+    False (the per-sample path is exact for every channel) and caches nothing: the comparison would have to synchronise."""
     if r is None or not R_PER_SEQUENCE:
         return False
-    key = (id(r), bool(time_major))
-    hit = _R_SEQ_CACHE.get(key)
-    if hit is not None and hit[0]() is r and hit[1] == r._version:
-        return hit[2]
+    hit = _R_SEQ_CACHE.get(r, bool(time_major))
+    if hit is not None:
+        return hit
     if r.is_cuda and torch.cuda.is_current_stream_capturing():
         return False
-    if len(_R_SEQ_CACHE) > 64:
-        for k in [k for k, v in _R_SEQ_CACHE.items() if v[0]() is None]:
-            del _R_SEQ_CACHE[k]
-        if len(_R_SEQ_CACHE) > 64:
-            _R_SEQ_CACHE.clear()
     with torch.no_grad():
         first = r[0:1, :] if time_major else r[:, 0:1]
-        flag = bool((r == first).all())
-    _R_SEQ_CACHE[key] = (weakref.ref(r), r._version, flag)
-    return flag
+        return _R_SEQ_CACHE.put(r, bool((r == first).all()), bool(time_major))
 
 
 def step_mse_workspace(B, n_chunks, device):

@@ -6,12 +6,12 @@ The forward call replaces the reference's whole per-sample Python loop
 the two and into the loss / optimizer.
 """
 import math
-import weakref
 from collections import namedtuple
 
 import torch
 
 from . import binding
+from .tensor_cache import ObjectMemo
 
 # ---- time-parallel plan -------------------------------------------------------------------
 # k_fwd / warmup / tol: chunks, warm-up steps and verified tolerance of the speculative forward
@@ -54,31 +54,27 @@ def plan_time_parallel(B, T, R, C, fs, tol=1.0e-6, time_major=False, R_min=None)
     return TpPlan(k_fwd, W, float(tol), k_bwd)
 
 
-_R_MAX_CACHE = {}      # id(tensor) -> (weakref to the tensor, version, max)
+_R_MAX_CACHE = ObjectMemo(256)      # tensor -> (max, min)
+
+
+def _r_range(r):
+    lo, hi = torch.aminmax(r)
+    return _R_MAX_CACHE.put(r, (float(hi), float(lo)))
 
 
 def resistance_max(r):
     """max of a per-sample resistance tensor: the planner needs the slowest sequence's memory.
     One device sync, cached per tensor OBJECT and version (a training set is the same tensor every
     epoch; a fresh tensor -- even one the allocator put at a recycled address -- is looked at again)."""
-    hit = _R_MAX_CACHE.get(id(r))
-    if hit is None or hit[0]() is not r or hit[1] != r._version:
-        if len(_R_MAX_CACHE) > 256:
-            for k in [k for k, v in _R_MAX_CACHE.items() if v[0]() is None]:
-                del _R_MAX_CACHE[k]
-        lo, hi = torch.aminmax(r)
-        hit = (weakref.ref(r), r._version, float(hi), float(lo))
-        _R_MAX_CACHE[id(r)] = hit
-    return hit[2]
+    return (_R_MAX_CACHE.get(r) or _r_range(r))[0]
 
 
 def resistance_min(r):
     """min of a per-sample resistance tensor (same cache entry as resistance_max)."""
-    resistance_max(r)
-    return _R_MAX_CACHE[id(r)][3]
+    return (_R_MAX_CACHE.get(r) or _r_range(r))[1]
 
 
-_SPLIT_CACHE = {}      # id(x) -> (weakref to x, version, xv, r)
+_SPLIT_CACHE = ObjectMemo(64)      # (x, layout) -> (xv, r)
 
 
 def split_channels(x, with_r, time_major=False, anchor=None):
@@ -93,19 +89,13 @@ def split_channels(x, with_r, time_major=False, anchor=None):
     # the cache hangs on the object the CALLER holds (`anchor`: the tensor as the script passed it),
     # not on the normalised views made from it, which are new objects every call
     anchor = x if anchor is None else anchor
-    key = (id(anchor), bool(time_major))
-    hit = _SPLIT_CACHE.get(key)
-    ver = getattr(anchor, "_version", None)
-    if hit is None or hit[0]() is not anchor or hit[1] != ver or (with_r and hit[3] is None):
-        if len(_SPLIT_CACHE) > 64:
-            for k in [k for k, v in _SPLIT_CACHE.items() if v[0]() is None]:
-                del _SPLIT_CACHE[k]
+    hit = _SPLIT_CACHE.get(anchor, bool(time_major))
+    if hit is None or (with_r and hit[1] is None):
         def chan(c):
             v = xt[:, :, c]
             return v.t().contiguous() if time_major else v.contiguous()
-        hit = (weakref.ref(anchor), ver, chan(0), chan(1) if with_r else None)
-        _SPLIT_CACHE[key] = hit
-    return hit[2], (hit[3] if with_r else None)
+        hit = _SPLIT_CACHE.put(anchor, (chan(0), chan(1) if with_r else None), bool(time_major))
+    return hit[0], (hit[1] if with_r else None)
 
 
 LAST_TP_STATUS = {"status": None}     # device status word of the most recent time-parallel forward

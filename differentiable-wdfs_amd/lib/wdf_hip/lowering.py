@@ -15,7 +15,6 @@ import collections
 import ctypes
 import math
 import os
-import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -24,6 +23,7 @@ import torch
 from . import binding
 from . import compat_tf as tf
 from . import warmstart
+from .tensor_cache import EntryCache, ObjectMemo, tensor_key  # noqa: F401  (tensor_key: re-exported)
 
 
 # ------------------------------------------------------------------------------ autograd glue
@@ -279,43 +279,6 @@ class _SsDynFn(torch.autograd.Function):
                 None, None, None, None, None)
 
 
-# ------------------------------------------------------------------------------ resident entries: which batch is this?
-def tensor_key(t):
-    """What names a batch for the resident paths' caches: the STORAGE a tensor looks at (address, shape, strides, dtype,
-    device) and its version counter -- not the Python object.  A training loop that cuts the same mini-batches out of its
-    dataset every epoch (`X[i:j]`: a fresh tensor object each time, the same memory) then finds its stepper, its resident
-    time-major copy and its warm-start state again; an in-place change of the data bumps the version (shared by all views
-    of a storage) and misses.  The entry keeps the first tensor it was made for alive, so the address cannot be handed to
-    other data while the entry exists."""
-    return (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, t._version, t.device.type, t.device.index)
-
-
-class EntryCache:
-    """Insertion-ordered cache of resident entries: at most `max_entries`, and -- beyond the first four -- at most
-    `max_bytes` of device buffers in total (a full-batch loop keeps a training and a validation set; a mini-batch loop
-    keeps every mini-batch of an epoch while they are small)."""
-
-    def __init__(self, max_entries=256, max_bytes=16 << 30):
-        self.d, self.nbytes, self.max_entries, self.max_bytes = {}, {}, int(max_entries), int(max_bytes)
-
-    def get(self, key):
-        return self.d.get(key)
-
-    def put(self, key, ent, nbytes=0):
-        self.d[key] = ent
-        self.nbytes[key] = int(nbytes)
-        while len(self.d) > self.max_entries or (len(self.d) > 4 and sum(self.nbytes.values()) > self.max_bytes):
-            old = next(iter(self.d))
-            del self.d[old], self.nbytes[old]
-        return ent
-
-    def values(self):
-        return self.d.values()
-
-    def __len__(self):
-        return len(self.d)
-
-
 def _nbytes(*ts):
     return sum(t.numel() * t.element_size() for t in ts if isinstance(t, torch.Tensor))
 
@@ -325,7 +288,6 @@ _LIN_OCC = int(os.environ.get("WDF_LIN_OCC", "2"))       # chunks are cut so tha
 _NL_OCC = int(os.environ.get("WDF_NL_OCC", "1"))
 _NL_WMIN = int(os.environ.get("WDF_NL_WMIN", "16"))      # the shortest warm-up the device's controller may settle on
 _ROWS = 1024                                             # result rows per slab (see _LinResident.entry)
-_DYN_CHAN_ENTRIES = 8                                    # _run_dyn's per-sequence answers kept (each holds its input)
 NL_TOL = 1.0e-6                                          # boundary tolerance of the diode-root one-pass step (plan_ss_time_parallel's)
 
 
@@ -422,8 +384,7 @@ class _LinResident:
         return self._hc_val
 
     def entry(self, x, target):
-        key = (tensor_key(x), tensor_key(target))
-        ent = self.cache.get(key)
+        ent = self.cache.get((x, target))
         if ent is None:
             circ, dev = self.circ, self.pb.block.device
             xd = x.as_subclass(torch.Tensor).to(dev).float()
@@ -451,10 +412,10 @@ class _LinResident:
             # slab of _ROWS; a full slab is replaced by a fresh one and lives on for as long as anything still refers to
             # it): the loss history a script keeps (lpf.py:99 `losses.append(loss)`) and gradients read after the loop stay
             # what they were -- no copy per call, one allocation per _ROWS calls
-            ent = self.cache.put(key, {"x": x_tm, "t": tgt, "y": y, "ws": ws,
+            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": y, "ws": ws,
                                        "ring": torch.zeros((_ROWS, 2 + self.pb.n), dtype=torch.float32, device=dev), "turn": 0,
-                                       "B": B, "T": T, "k": k, "hold": (x, target), "calls": 0, "watch": None, "replans": 0},
-                                 _nbytes(x_tm, tgt, y, ws))
+                                       "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0},
+                                 nbytes=_nbytes(x_tm, tgt, y, ws))
         return ent
 
     def _plan_nl(self, B, T, k, dev, cold_floor=0):
@@ -830,9 +791,7 @@ class Circuit:
             if now[i] is not v or getattr(v, "_wdf_block", (None,))[0] is not pb:
                 raise binding.WdfHipError("Circuit.to_device: a component Variable was replaced (set_resistance?) or moved to another "
                                           "block after to_device(); build a new Circuit")
-        with torch._C.DisableTorchFunctionSubclass():
-            key = (tensor_key(x), tensor_key(target), kind, int(skip))
-        ent = self._res_cache.get(key)
+        ent = self._res_cache.get((x, target), (kind, int(skip)))
         if ent is None:
             dp, cap = self.root, self.top.P2
             xd = x.as_subclass(torch.Tensor).to(pb.block.device).float()
@@ -848,17 +807,15 @@ class Circuit:
             st = engine.MseStep(B, T, float(cap.FS), tp, pb.block.device, n_up=dp.N_up, n_down=dp.N_down, time_major=True,
                                 warm=True, loss=kind, skip=int(skip))
             live = [(i, v) for i, v in sorted(pb.members.items()) if v.requires_grad]
-            ent = self._res_cache.put(key, (st, xv, r, tgt, 1.0 / float(B * T) if kind == "mse" else 1.0,
-                                            [i for i, _ in live], [v for _, v in live],
-                                            x, target,                    # (x, target held: their storage stays theirs)
-                                            {id(v): i for i, v in live}),
-                                      3 * _nbytes(xv, r, tgt))
+            ent = self._res_cache.put((x, target), (st, xv, r, tgt, 1.0 / float(B * T) if kind == "mse" else 1.0,
+                                                    [i for i, _ in live], [v for _, v in live], {id(v): i for i, v in live}),
+                                      (kind, int(skip)), 3 * _nbytes(xv, r, tgt))
         st, xv, r, tgt, inv_n, idx, live = ent[:7]
         engine.LAST_TP_STATUS["status"] = st.status
         loss, out = engine._ResidentMseFn.apply(st, pb.block, xv, r, tgt, inv_n, idx, *live)
         loss = loss.as_subclass(tf.Tensor)
         # d loss / d Variable is already known: tape.gradient(loss, ...) on THIS tensor reads it (compat_tf.GradientTape)
-        loss._wdf_fused = (out, ent[9])
+        loss._wdf_fused = (out, ent[7])
         return loss
 
     def mse_esr(self, x, target, skip=0, z0=None, carry_state=False):
@@ -1094,16 +1051,10 @@ class Circuit:
         warm = None
         if tp is not None and tp.k_fwd >= 2 and kind == binding.ROOT_DIODE_PAIR and self._anchor is not None and self.warm_start:
             # the caller's tensor object and version name the batch: the same one again -> its chunks start warm
-            ws = self.__dict__.setdefault("_ss_warm", {})
-            wkey = (id(self._anchor), self._anchor._version, tuple(x.shape))
-            hit = ws.get(wkey)
-            if hit is None or hit[0]() is not self._anchor:
-                for k_ in [k_ for k_, v_ in ws.items() if v_[0]() is None]:
-                    del ws[k_]
-                if len(ws) >= 4:
-                    ws.pop(next(iter(ws)))                         # oldest out
-                hit = ws[wkey] = (weakref.ref(self._anchor), SsWarmStart(x.shape[1], x.shape[0], self.ns, tp))
-            warm = hit[1]
+            ws = self.__dict__.setdefault("_ss_warm", ObjectMemo(4))
+            warm = ws.get(self._anchor, tuple(x.shape))
+            if warm is None:
+                warm = ws.put(self._anchor, SsWarmStart(x.shape[1], x.shape[0], self.ns, tp), tuple(x.shape))
             warm.plan = tp                  # (the cold plan follows the components as they train; the warm state stays)
         y, zT = _StateSpaceFn.apply(coef, rootp, x.contiguous(), z0t, self.ns, self.ni, kind, n_up, n_down,
                                     bool(return_state), tp, warm)
@@ -1137,27 +1088,18 @@ class Circuit:
         # A pot that keeps its value along every sequence (the reference's recordings: dataimport.py:96 repeats the file's
         # resistance down the whole channel, batch_data cuts sequences out of it): calc_impedance gives ONE row per sequence --
         # the tape runs over B values instead of B x T, the kernels read rows [1,n,B] and the sweep sums dL/d(row) over the
-        # steps itself.  Looked at once per input tensor (one comparison pass, cached on the storage).  Every answer kept also
-        # keeps the caller's tensor (_dyn_chan_held, same keys): the address cannot be handed to other data -- a pot that
-        # moves -- while its answer is in the cache; at most _DYN_CHAN_ENTRIES of them, the oldest out first.
+        # steps itself.  Looked at once per input tensor (one comparison pass, cached on the storage: EntryCache holds the
+        # caller's tensor, so no other data -- a pot that moves -- can land at its address while the answer is kept).
         per_seq = False
         if chan >= 0 and not x.requires_grad and T > 1 and getattr(self, "per_sequence_rows", True):
-            with torch._C.DisableTorchFunctionSubclass():
-                ckey = tensor_key(self._anchor) if isinstance(getattr(self, "_anchor", None), torch.Tensor) else None
-            cache = self.__dict__.setdefault("_dyn_chan_const", {})
-            held = self.__dict__.setdefault("_dyn_chan_held", {})
-            if ckey is not None and ckey in cache:
-                per_seq = cache[ckey]
-            else:
+            cache = self.__dict__.setdefault("_dyn_chan_const", EntryCache(max_entries=8))
+            per_seq = None if self._anchor is None else cache.get(self._anchor)
+            if per_seq is None:
                 with torch.no_grad():
                     rch = x[:, :, self.ni]
                     per_seq = bool((rch == rch[:, :1]).all())
-                if ckey is not None:
-                    while len(cache) >= _DYN_CHAN_ENTRIES:
-                        old = next(iter(cache))
-                        del cache[old]
-                        held.pop(old, None)
-                    cache[ckey], held[ckey] = per_seq, self._anchor
+                if self._anchor is not None:
+                    cache.put(self._anchor, per_seq)
         vals = []
         for i, (e, n) in enumerate(params):
             if i == chan:
@@ -1209,12 +1151,9 @@ class Circuit:
         if tp is not None and self.warm_start and self.ns >= 1 and z0t is None and isinstance(getattr(self, "_anchor", None), torch.Tensor):
             # the same batch again (a training loop: lpf.py:86-99 re-runs data_in every epoch) -> its chunks start warm
             wsd = self.__dict__.setdefault("_dyn_warm", EntryCache(max_entries=4))
-            with torch._C.DisableTorchFunctionSubclass():
-                wkey = (tensor_key(self._anchor), kind)
-            hit = wsd.get(wkey)
-            if hit is None:
-                hit = wsd.put(wkey, (self._anchor, DynWarmStart(T, B, self.ns, tp.k_bwd, tp.warmup if tp.warmup > 0 else 64, tp.tol)))
-            warm = hit[1]
+            warm = wsd.get(self._anchor, kind)
+            if warm is None:
+                warm = wsd.put(self._anchor, DynWarmStart(T, B, self.ns, tp.k_bwd, tp.warmup if tp.warmup > 0 else 64, tp.tol), kind)
         y, zT = _SsDynFn.apply(rows, rootvec, xs, z0t, self.ns, self.ni, kind, hidden, n_tanh, n_up, n_down, bool(return_state), tp, warm)
         y = y.as_subclass(tf.Tensor)
         return (y, zT[:self.ns]) if return_state else y

@@ -6,7 +6,6 @@ The per-lane reverse-sweep kernel returns g_b[n] = dL/d b[n] and the network inp
 over B*T independent samples, done by wdf_clipper_mlp_wgrad (fully parallel HIP kernel)."""
 import os
 import math
-import weakref
 from collections import namedtuple
 
 import torch
@@ -15,6 +14,7 @@ from . import binding
 from . import engine
 from . import warmstart
 from . import compat_tf as tf
+from .tensor_cache import EntryCache, ObjectMemo
 
 
 def describe(model, with_activation=False):
@@ -74,7 +74,7 @@ LAST_TP_STATUS = {"status": None}
 WARM_START = os.environ.get("WDF_MLP_WARM_START", "1") != "0"        # 0: every call warms its chunks up from z = 0
 _TRACE_WARMUP = [] if os.environ.get("WDF_MLP_TRACE_WARMUP") else None    # (probing) per call: (warm-up steps, warm-started?)
 _TRACE_VERDICTS = []   # (probing, with _TRACE_WARMUP) per verdict read back: (warm-up, n_bad, max miss, gated waves, sequential waves)
-_WARM_START = {}       # (batch object, version, shape, chunks, planned warm-up, r) -> warmstart.WarmUpController + the previous call's states
+_WARM_START = ObjectMemo(8)       # (x, r; shape, chunks, planned warm-up) -> warmstart.WarmUpController + the previous call's states
 KAPPA_FROM_FORWARD = os.environ.get("WDF_MLP_KAPPA_FROM_FORWARD", "1") != "0"   # 0: the reverse sweep recomputes kappa
 _WARMUP_ADAPT = {}     # (x shape, forward chunks, planned warm-up) -> {"warmup": steps in use, "calls": n}
 
@@ -96,28 +96,20 @@ class _ClipperMlpFn(torch.autograd.Function):
             # a training call also takes kappa from the forward (the reverse sweep then skips its first pass)
             use_kappa = need and tp.k_bwd > 1 and KAPPA_FROM_FORWARD
             # ... and, the second time it sees a batch, starts every chunk from the state the previous call had there
-            # (the weights moved by one optimizer step): a fraction of the warm-up closes that gap.  Keyed by the
-            # batch's address and shape; other data at the same address is caught by the verification like any miss.
+            # (the weights moved by one optimizer step): a fraction of the warm-up closes that gap.  Kept per batch OBJECT
+            # (x and r) and version: a tensor that lands at the same address later is another batch, an in-place change
+            # of x restarts cold.
             warm = None
             if use_kappa and WARM_START and tp.warmup_per_wave is None and z0 is None:
-                # keyed on the batch OBJECT and its version (a weak reference: the entry dies with the tensor, another
-                # tensor that lands at the same address later is another key, in-place changes of x restart cold)
-                wkey = (id(x), x._version, tuple(x.shape), tp.k_fwd, tp.warmup, None if r is None else (id(r), r._version))
-                warm = _WARM_START.get(wkey)
-                if warm is not None and (warm["xref"]() is not x or (r is not None and warm["rref"]() is not r)):
-                    warm = None                                  # (an id reused by another tensor)
+                wkey = (tuple(x.shape), tp.k_fwd, tp.warmup)
+                warm = _WARM_START.get((x, r), wkey)
                 if warm is None:
-                    for k in [k for k, v in _WARM_START.items() if v["xref"]() is None or (v["rref"] is not None and v["rref"]() is None)]:
-                        del _WARM_START[k]                       # entries whose batch has been freed
-                    if len(_WARM_START) >= 8:
-                        _WARM_START.pop(next(iter(_WARM_START)))     # oldest out
                     # (a wave or two re-run now and then is the fp32 floor of this path crossing the tolerance --
                     #  plan_mlp_time_parallel's note -- which no warm-up cures: only 8 or more per verdict count as a
                     #  warm-up too short; the weights swing with periods of ~16 calls, so 32 clean calls before less is tried)
                     ctl = warmstart.WarmUpController(ad["warmup"], int(os.environ.get("WDF_MLP_WARM_W", ad["warmup"] // 3)),
                                                      unit=16, floor=32, miss_waves=8, wait_calls=32)
-                    warm = _WARM_START[wkey] = {"ctl": ctl, "rows": {}, "idx": None, "idx_key": None,
-                                                "xref": weakref.ref(x), "rref": None if r is None else weakref.ref(r)}
+                    warm = _WARM_START.put((x, r), {"ctl": ctl, "rows": {}, "idx": None, "idx_key": None}, wkey)
             zinit, w_used = None, ad["warmup"]
             if warm is not None:
                 # the previous call's verified states at this call's chunk starts (the weights moved by one optimizer step).
@@ -262,7 +254,7 @@ def clipper_mlp_segmented(theta2, w, x, r, fs, hidden, n_tanh, plan, tol=1.0e-6,
     return y, zT, miss
 
 
-_WROW_CACHE = {}       # id(r) -> (weakref, version, (C, fs, tol), int32 tensor, max)
+_WROW_CACHE = ObjectMemo(64)       # (r; C, fs, tol) -> (int32 tensor, max)
 
 
 def _warmup_steps(rho, tol):
@@ -277,12 +269,9 @@ def warmup_per_wave(r, C, fs, tol=1.0e-6):
     int32[ceil(B/4)] warm-up steps for the time-parallel forward, one per 4 consecutive sequences, from the
     slowest memory |1 - 2p| among them (p = Rc/(R+Rc) at the smallest and the largest pot value of the four
     sequences); cached per resistance tensor (a training set is the same tensor every epoch).  Also the max."""
-    hit = _WROW_CACHE.get(id(r))
     key = (float(C), float(fs), float(tol))
-    if hit is None or hit[0]() is not r or hit[1] != r._version or hit[2] != key:
-        if len(_WROW_CACHE) > 64:
-            for k in [k for k, v in _WROW_CACHE.items() if v[0]() is None]:
-                del _WROW_CACHE[k]
+    hit = _WROW_CACHE.get(r, key)
+    if hit is None:
         B = r.shape[0]
         Rc = 1.0 / (2.0 * float(C) * float(fs))
         lo, hi = r.amin(dim=1), r.amax(dim=1)
@@ -293,9 +282,8 @@ def warmup_per_wave(r, C, fs, tol=1.0e-6):
         rho = torch.maximum((1.0 - 2.0 * Rc / (lo + Rc)).abs(), (1.0 - 2.0 * Rc / (hi + Rc)).abs()).clamp(1e-6, 1.0 - 1e-9)
         W = torch.ceil(math.log(0.01 * tol) / torch.log(rho))
         W = (torch.ceil(W / 16.0) * 16.0).clamp(min=16.0).to(torch.int32).contiguous()
-        hit = (weakref.ref(r), r._version, key, W, int(W.max()))
-        _WROW_CACHE[id(r)] = hit
-    return hit[3], hit[4]
+        hit = _WROW_CACHE.put(r, (W, int(W.max())), key)
+    return hit
 
 
 def plan_mlp_time_parallel(B, T, r, R_static, C, fs, tol=4.0e-6, hidden=None, n_tanh=None):
@@ -407,23 +395,18 @@ def _run_clipper_relu(circ, x, z0, return_state, dense, hidden, n_layers):
     # one forward-only stepper per input (clipper_pot.py:251-262 validates on the same val_X every epoch): its buffers, its
     # plan and its warm-start snapshots are kept; only the weights are refreshed
     anchor = getattr(circ, "_anchor", None)
-    key = None if anchor is None else (id(anchor), anchor._version, tuple(x.shape))
-    cache = circ.__dict__.setdefault("_relu_fwd", {})
-    ent = cache.get(key) if key is not None else None
+    cache = circ.__dict__.setdefault("_relu_fwd", ObjectMemo(2))
+    st = None if anchor is None else cache.get(anchor, tuple(x.shape))
     with torch.no_grad():
         w = flat_weights(dense).float().to(dev).contiguous()
-        if ent is None or ent[0]() is not anchor:
+        if st is None:
             xv, r = engine.split_channels(x, circ.per_sample_R is not None, anchor=anchor)
             Rv = None if circ.per_sample_R is not None else float(vs.R)
             st = MlpTrainStep(xv, r, torch.zeros((int(x.shape[1]), int(x.shape[0])), dtype=torch.float32, device=dev), w.clone(), hidden,
                               n_layers, float(cap.FS), float(cap.C), R_static=Rv, skip=0, adam=None, activation="relu")
-            if key is not None:
-                if len(cache) >= 2:
-                    cache.pop(next(iter(cache)))
-                import weakref
-                cache[key] = (weakref.ref(anchor), st)
+            if anchor is not None:
+                cache.put(anchor, st, tuple(x.shape))
         else:
-            st = ent[1]
             st.w.copy_(w)
         st.forward_only()
     return st.y.clone().as_subclass(tf.Tensor)
@@ -779,14 +762,10 @@ class MlpResident:
                 self.vars.append(v)
                 o += n
         self.spec = {id(v): v._wdf_flat[1:] + (tuple(v.shape),) for v in self.vars}
-        from . import lowering
-        self.cache = lowering.EntryCache()
+        self.cache = EntryCache()
 
     def entry(self, x, target, skip):
-        from . import lowering
-        with torch._C.DisableTorchFunctionSubclass():
-            key = (lowering.tensor_key(x), lowering.tensor_key(target), int(skip))
-        ent = self.cache.get(key)
+        ent = self.cache.get((x, target), int(skip))
         if ent is None:
             circ, dev = self.circ, self.w.device
             xd = x.as_subclass(torch.Tensor).to(dev).float()
@@ -795,7 +774,7 @@ class MlpResident:
             tgt = target.as_subclass(torch.Tensor).to(dev).float().reshape(T, B).contiguous()
             st = MlpTrainStep(xv, r, tgt, self.w, self.hidden, self.n_layers, self.fs, self.C, R_static=self.R_static,
                               skip=int(skip), adam=None, activation=self.act)
-            ent = self.cache.put(key, {"st": st, "hold": (x, target), "calls": 0}, 8 * tgt.numel() * 4)
+            ent = self.cache.put((x, target), {"st": st, "calls": 0}, int(skip), 8 * tgt.numel() * 4)
         return ent
 
 

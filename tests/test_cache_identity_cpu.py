@@ -130,3 +130,19 @@ def test_resistance_max_min_answer_for_the_second_tensor_at_the_same_address(eng
     assert engine.resistance_max(r2) == 5.0e3 and engine.resistance_min(r2) == 300.0
     r2.add_(1.0)                                               # in place: looked at again
     assert engine.resistance_max(r2) == 5.001e3 and engine.resistance_min(r2) == 301.0
+
+
+def test_warmup_per_wave_answers_for_the_second_tensor_at_the_same_address():
+    from wdf_hip import mlp_root
+    C, fs = 33.0e-9, 48000.0
+    a = np.full((8, 64), 1.0e3, np.float32)
+    r1 = torch.from_numpy(a)
+    W1, m1 = mlp_root.warmup_per_wave(r1, C, fs)
+    a[4:, 10] = 1.0e5                                          # the second group of four sequences now has a slow memory
+    r2 = torch.from_numpy(a)
+    assert same_key(r1, r2)
+    W2, m2 = mlp_root.warmup_per_wave(r2, C, fs)
+    Wf, mf = mlp_root.warmup_per_wave(r2.clone(), C, fs)       # (a tensor no cache has seen)
+    assert torch.equal(W2, Wf) and m2 == mf
+    assert torch.equal(W2[:1], W1[:1]) and int(W2[1]) > int(W1[1]) and m2 > m1
+    assert mlp_root.warmup_per_wave(r2, C, fs)[0] is W2        # the same object again hits

@@ -76,7 +76,7 @@ for root, resident in (("diode", False), ("diode", True), ("mlp2x16", False), ("
     g = tape.gradient(loss, params)
     torch.cuda.synchronize()
     if "--trace" in sys.argv:                                  # the warm start's controller: warm-ups run, the verdicts read back
-        for _, ws in circ.__dict__["_dyn_warm"].values():
+        for ws in circ.__dict__["_dyn_warm"].values():
             print("# warm-ups of the last calls:", list(ws.trace)[-24:], file=sys.stderr)
             print("# verdicts (warm-up, n_bad, max miss, gated groups, -):", list(ws.ctl.verdicts)[-12:], file=sys.stderr)
     print(json.dumps({"tree": "HPF clipper, pot on the source resistance (one value per sequence, dataimport.py:96)", "root": root,
