@@ -1,5 +1,6 @@
 // wdf_asym.h -- diode clipper with two DIFFERENT antiparallel diodes (BASELINE config 5):
-// fp64 Newton on the exact Shockley pair versus the fp32 Wright-omega closed form.
+// Newton on the exact Shockley pair, in fp32 or in fp64, and -- kept for comparison -- the fp32 Wright-omega closed form,
+// which is a MODEL APPROXIMATION (it drops the reverse diode's saturation current), not a precision point.
 //
 // Tree as in wdf_clipper.h (P1 = Parallel(ResistiveVoltageSource(R), Capacitor(C, fs))).
 // Root: up-diode (Is1, V1 = n1 Vt) conducts for v > 0, down-diode (Is2, V2) for v < 0:
@@ -9,22 +10,33 @@
 // to pin parity against: the oracle is an fp64 safeguarded Newton and
 // mpmath in the tests.
 //
-//  NEWTON (fp64): solve v + Rp i(v) - a = 0 per lane, started from the omega closed form,
+//  NEWTON_F64 (mode 1): solve v + Rp i(v) - a = 0 per lane, started from the omega closed form,
 //      iterated until EVERY lane of the wave meets |dv| <= tol (|v| + V) -- the wavefront
 //      ballot is the loop condition, so a wave stops as soon as its slowest sequence has
-//      converged -- or max_iter is reached.
-//  OMEGA (fp32): the two-diode generalisation of Werner eqn 39 (Toms917DiodePair.h:51-59):
+//      converged -- or max_iter is reached.  State in fp64.
+//  NEWTON_F32 (mode 2): the same equation, the same start value, damping and ballot, every operation in fp32
+//      (v_exp_f32, v_rcp_f32), state in fp32.  Two things differ from the fp64 loop and both matter:
+//      the reflected wave is formed as b = 2 v - a (v - Rp i(v) amplifies the last ulp of v through the exponential:
+//      7e-6 V at |a| = 6 V against 3e-7 V), and the stop rule's tolerance is max(tol, 4 FLT_EPSILON) -- below that the
+//      step only flips the last bit of v and no wave would ever stop before max_iter.
+//  OMEGA (mode 0, fp32): the two-diode generalisation of Werner eqn 39 (Toms917DiodePair.h:51-59):
 //      b = a - 2 lam (Vf w(log(Rp Isf/Vf) + lam a/Vf) - Vr w(log(Rp Isr/Vr) - lam a/Vr)),
 //      f = the diode that conducts for this sign of a, r = the other.  Like eqn 39 it neglects
-//      the reverse diode's saturation current in the forward branch (error ~ Rp Is_r).
+//      the reverse diode's saturation current in the forward branch (error ~ Rp Is_r: 8 mV at the root, 0.1 V on y for
+//      a germanium-like reverse diode).  It is a different model, not a cheaper solve of this one; it stays as the
+//      Newton modes' start value and for comparison.
 #pragma once
 
+#include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "wdf_omega.h"
 
 namespace wdf {
+
+// the values of WDF_ASYM_* (include/wdf_hip.h)
+constexpr int kAsymOmega = 0, kAsymNewton64 = 1, kAsymNewton32 = 2;
 
 struct AsymConsts {
     float p, Rp;
@@ -120,11 +132,38 @@ __device__ __forceinline__ double asym_newton_root(const AsymConsts& c, double a
     return v - Rp * i;
 }
 
-// One step of the tree around the root; S is the state type (double for NEWTON, float otherwise).
-template <bool NEWTON>
+// The exact pair solved in fp32: returns b; iters += Newton iterations this wave ran.  Start value: the closed form's
+// v = (a + b)/2.  The residual is written (v - a) + Rp i: v - a is exact near the root (Sterbenz) where v + Rp i - a would
+// round the sum first.  Stop rule: every lane of the wave at |dv| <= max(tol, 4 FLT_EPSILON) (|v| + V) -- at 4.8e-7 the
+// iteration stalls cleanly (3e-7 observed); any smaller tolerance is met only by chance, dv then being the last bit of v.
+// The exponentials are evaluated afresh every iteration: a carried exponential times a polynomial in dv (the fp64 loop's
+// saving) costs as many issue cycles as the two v_exp_f32 it replaces and adds an fp32 rounding per iteration to e.
+__device__ __forceinline__ float asym_newton32_root(const AsymConsts& c, float a, double tol, int max_iter, int& iters)
+{
+    const float iV1 = fast_rcp(c.V1), iV2 = fast_rcp(c.V2), vscale = fminf(c.V1, c.V2), lim = 4.0f * vscale;
+    const float k1 = c.Rp * c.Is1, k2 = c.Rp * c.Is2, d1 = k1 * iV1, d2 = k2 * iV2;
+    const float tl = fmaxf((float)tol, 4.0f * FLT_EPSILON);
+    float v = 0.5f * (a + asym_omega_root(c, a));
+    for (int it = 0; it < max_iter; ++it) {
+        const float e1 = fast_exp(v * iV1), e2 = fast_exp(-v * iV2);
+        const float f = (v - a) + fmaf(k1, e1 - 1.0f, -k2 * (e2 - 1.0f));
+        const float fp = fmaf(d1, e1, fmaf(d2, e2, 1.0f));
+        const float q = f * fast_rcp(fp);
+        // (not a number -- v_exp_f32 overflowed on a wild start value -- moves nothing: see asym_newton_f32)
+        const float dv = (q == q) ? fminf(fmaxf(q, -lim), lim) : 0.0f;
+        v -= dv;
+        ++iters;
+        const bool active = fabsf(dv) > tl * (fabsf(v) + vscale);
+        if (__builtin_amdgcn_ballot_w64(active) == 0) break;     // the whole wave has converged
+    }
+    return fmaf(2.0f, v, -a);
+}
+
+// One step of the tree around the root; S is the state type (double for NEWTON_F64, float otherwise).
+template <int MODE>
 struct AsymStep;
 template <>
-struct AsymStep<true> {
+struct AsymStep<kAsymNewton64> {
     using S = double;
     static __device__ __forceinline__ float run(const AsymConsts& c, float xin, double& z, double tol, int max_iter,
                                                 int& iters)
@@ -141,7 +180,7 @@ struct AsymStep<true> {
     }
 };
 template <>
-struct AsymStep<false> {
+struct AsymStep<kAsymOmega> {
     using S = float;
     static __device__ __forceinline__ float run(const AsymConsts& c, float xin, float& z, double, int, int&)
     {
@@ -154,9 +193,23 @@ struct AsymStep<false> {
         return y;
     }
 };
+template <>
+struct AsymStep<kAsymNewton32> {
+    using S = float;
+    static __device__ __forceinline__ float run(const AsymConsts& c, float xin, float& z, double tol, int max_iter, int& iters)
+    {
+        const float b_diff = z - xin;
+        const float b_temp = -c.p * b_diff;
+        const float a = z + b_temp;
+        const float zn = asym_newton32_root(c, a, tol, max_iter, iters) + b_temp;
+        const float y = 0.5f * (zn + z);
+        z = zn;
+        return y;
+    }
+};
 
 // x [B][T] -> y [T][B]; theta6 = {Is1, V1, Is2, V2, R, C}; iters_out: optional int64[gridDim.x]
-template <bool NEWTON, bool VEC4>
+template <int MODE, bool VEC4>
 __global__ __launch_bounds__(64) void clipper_asym_fwd_kernel(const float* __restrict__ x,
                                                               const float* __restrict__ theta6, float fs,
                                                               float* __restrict__ y, float* __restrict__ zstash,
@@ -165,7 +218,7 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_kernel(const float* __res
                                                               long long* __restrict__ iters_out, int64_t B, int64_t T,
                                                               const unsigned* __restrict__ gate = nullptr)
 {
-    using S = typename AsymStep<NEWTON>::S;
+    using S = typename AsymStep<MODE>::S;
     if (gate != nullptr && gate[blockIdx.x] == 0u) return;    // sequential re-run behind a time-parallel pass: flagged waves only
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t b = b_raw < B ? b_raw : B - 1;
@@ -197,13 +250,13 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < kB; ++k) {
             if (zp) { *zp = (float)z; zp += B; }
-            *yp = AsymStep<NEWTON>::run(c, xc[k], z, tol, max_iter, iters);
+            *yp = AsymStep<MODE>::run(c, xc[k], z, tol, max_iter, iters);
             yp += B;
         }
     }
     for (int64_t t = nfull * kB; t < T; ++t) {
         if (zp) { *zp = (float)z; zp += B; }
-        *yp = AsymStep<NEWTON>::run(c, x[b * T + t], z, tol, max_iter, iters);
+        *yp = AsymStep<MODE>::run(c, x[b * T + t], z, tol, max_iter, iters);
         yp += B;
     }
     if (zT) zT[b] = (float)z;
@@ -218,7 +271,7 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_kernel(const float* __res
 // launched GATED and re-runs exactly those waves.  L and W are multiples of 8.
 struct AsymTpStatus { int n_bad; float max_miss; int gated_waves; int pad; };
 
-template <bool NEWTON>
+template <int MODE>
 __global__ __launch_bounds__(64) void clipper_asym_fwd_tp_kernel(const float* __restrict__ x, const float* __restrict__ theta6,
                                                                  float fs, float* __restrict__ y, float* __restrict__ zstash,
                                                                  const float* __restrict__ z0, float* __restrict__ zT,
@@ -226,7 +279,7 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_tp_kernel(const float* __
                                                                  int max_iter, AsymTpStatus* __restrict__ status, int64_t B,
                                                                  int64_t T, int64_t L, int64_t W)
 {
-    using S = typename AsymStep<NEWTON>::S;
+    using S = typename AsymStep<MODE>::S;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *status = AsymTpStatus{0, 0.0f, 0, 0};   // the verify kernel adds
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t b = b_raw < B ? b_raw : B - 1;
@@ -254,7 +307,7 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_tp_kernel(const float* __
         for (int i = 0; i < kB; ++i) {
             if (tb + i < t1) {                                   // wave-uniform (the last chunk's ragged end)
                 const S zb = z;
-                const float yv = AsymStep<NEWTON>::run(c, xc[i], z, tol, max_iter, iters);
+                const float yv = AsymStep<MODE>::run(c, xc[i], z, tol, max_iter, iters);
                 if (owned) {
                     if (zstash) zstash[(tb + i) * B + b] = (float)zb;
                     y[(tb + i) * B + b] = yv;
@@ -380,7 +433,7 @@ static __global__ __launch_bounds__(256) void clipper_asym_grad_reduce_kernel(co
     }
 }
 
-// ---- time-parallel reverse sweep (both modes) ---------------------------------------------------------------------------
+// ---- time-parallel reverse sweep (all modes) ----------------------------------------------------------------------------
 // The sweep above is one dependent chain per sequence (128 waves on 1024 SIMDs at B = 8192) and re-solves the root by Newton
 // at every step.  Neither is needed:
 //  * Given the stash, every step's local quantities are independent of the adjoint: the root needs no re-solve -- the
@@ -392,7 +445,9 @@ static __global__ __launch_bounds__(256) void clipper_asym_grad_reduce_kernel(co
 //    a chunk run with the unknown entering adjoint Lam carries (m, g0): gz = m Lam + g0, and leaves
 //        {P, q}: gz at its first step's exit = P Lam + q ;  {alpha_i, beta_i}: its sums = alpha_i Lam + beta_i.
 //    clipper_asym_bwd_combine_kernel walks a sequence's K records last to first -- exact, no truncation.
-// NEWTON mode differentiates the exact Shockley pair implicitly (formulas above).  OMEGA mode differentiates the fp32
+// NEWTON = both Newton modes (the fp32 one has no other reverse sweep): the exact Shockley pair differentiated implicitly
+// (formulas above) at the root the forward stored -- nothing is re-solved, so the forward's precision is not this kernel's
+// concern.  OMEGA mode differentiates the fp32
 // closed form the OMEGA forward evaluates (asym_omega_root): with xf = lf + |a|/Vf, xr = lr - |a|/Vr, w' = w/(1 + w):
 //     db/da   = 1 - 2 (wf' + wr')
 //     db/dVf  = -2 lam (wf - wf' (1 + |a|/Vf)) ;  db/dVr  = 2 lam (wr - wr' (1 - |a|/Vr))
@@ -531,7 +586,7 @@ static __global__ __launch_bounds__(64) void clipper_asym_bwd_combine_kernel(con
 }
 
 // element-wise root, for accuracy sweeps: b[i] = root(a[i])
-template <bool NEWTON>
+template <int MODE>
 __global__ void asym_root_kernel(const float* __restrict__ a, const float* __restrict__ theta6, float fs,
                                  double* __restrict__ b, double tol, int max_iter, int64_t n)
 {
@@ -539,10 +594,13 @@ __global__ void asym_root_kernel(const float* __restrict__ a, const float* __res
     const int64_t j = i < n ? i : n - 1;
     const AsymConsts c = asym_load(theta6, fs);
     double r;
-    if constexpr (NEWTON) {
+    if constexpr (MODE == kAsymNewton64) {
         int it = 0;
         const float bw = asym_omega_root(c, a[j]);
         r = asym_newton_root(c, (double)a[j], 0.5 * ((double)a[j] + (double)bw), tol, max_iter, it);
+    } else if constexpr (MODE == kAsymNewton32) {
+        int it = 0;
+        r = (double)asym_newton32_root(c, a[j], tol, max_iter, it);
     } else {
         r = (double)asym_omega_root(c, a[j]);
     }

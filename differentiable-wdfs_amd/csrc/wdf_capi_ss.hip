@@ -287,20 +287,26 @@ int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns,
     return check_launch("wdf_ss_grad_reduce");
 }
 
+static bool asym_mode_known(int mode)
+{
+    return mode == WDF_ASYM_OMEGA_F32 || mode == WDF_ASYM_NEWTON_F64 || mode == WDF_ASYM_NEWTON_F32;
+}
+
 int wdf_clipper_asym_fwd(const float* x, const float* theta6, float fs, int mode, double tol, int max_iter, float* y,
                          float* zstash, const float* z0, float* zT, long long* iters, int64_t B, int64_t T, void* stream)
 {
     if (!x || !theta6 || !y) return fail(WDF_EINVAL, "null x/theta6/y");
     if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
-    if (mode != WDF_ASYM_OMEGA_F32 && mode != WDF_ASYM_NEWTON_F64) return fail(WDF_EINVAL, "unknown mode %d", mode);
-    if (mode == WDF_ASYM_NEWTON_F64 && (!(tol > 0.0) || max_iter < 1)) return fail(WDF_EINVAL, "tol > 0, max_iter >= 1");
+    if (!asym_mode_known(mode)) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (mode != WDF_ASYM_OMEGA_F32 && (!(tol > 0.0) || max_iter < 1)) return fail(WDF_EINVAL, "tol > 0, max_iter >= 1");
     const unsigned grid = (unsigned)((B + 63) / 64);
     const bool v4 = (T % 4 == 0) && aligned16(x);
-#define WDF_ASYM(NEWTON_, V4_)                                                                                \
-    hipLaunchKernelGGL((wdf::clipper_asym_fwd_kernel<NEWTON_, V4_>), dim3(grid), dim3(64), 0, (hipStream_t)stream, x, \
+#define WDF_ASYM(MODE_, V4_)                                                                                  \
+    hipLaunchKernelGGL((wdf::clipper_asym_fwd_kernel<MODE_, V4_>), dim3(grid), dim3(64), 0, (hipStream_t)stream, x, \
                        theta6, fs, y, zstash, z0, zT, tol, max_iter, iters, B, T)
-    if (mode == WDF_ASYM_NEWTON_F64) { if (v4) WDF_ASYM(true, true); else WDF_ASYM(true, false); }
-    else { if (v4) WDF_ASYM(false, true); else WDF_ASYM(false, false); }
+    if (mode == WDF_ASYM_NEWTON_F64) { if (v4) WDF_ASYM(wdf::kAsymNewton64, true); else WDF_ASYM(wdf::kAsymNewton64, false); }
+    else if (mode == WDF_ASYM_NEWTON_F32) { if (v4) WDF_ASYM(wdf::kAsymNewton32, true); else WDF_ASYM(wdf::kAsymNewton32, false); }
+    else { if (v4) WDF_ASYM(wdf::kAsymOmega, true); else WDF_ASYM(wdf::kAsymOmega, false); }
 #undef WDF_ASYM
     return check_launch("wdf_clipper_asym_fwd");
 }
@@ -317,8 +323,8 @@ int wdf_clipper_asym_fwd_tp(const float* x, const float* theta6, float fs, int m
 {
     if (!x || !theta6 || !y || !ws || !status) return fail(WDF_EINVAL, "null x/theta6/y/ws/status");
     if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
-    if (mode != WDF_ASYM_OMEGA_F32 && mode != WDF_ASYM_NEWTON_F64) return fail(WDF_EINVAL, "unknown mode %d", mode);
-    if (mode == WDF_ASYM_NEWTON_F64 && (!(tol > 0.0) || max_iter < 1)) return fail(WDF_EINVAL, "tol > 0, max_iter >= 1");
+    if (!asym_mode_known(mode)) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (mode != WDF_ASYM_OMEGA_F32 && (!(tol > 0.0) || max_iter < 1)) return fail(WDF_EINVAL, "tol > 0, max_iter >= 1");
     if (n_chunks < 1 || warmup < 0 || !(verify_tol >= 0.0f)) return fail(WDF_EINVAL, "n_chunks >= 1, warmup >= 0, verify_tol >= 0");
     int64_t L = (T + n_chunks - 1) / n_chunks;
     L = (L + 7) / 8 * 8;
@@ -331,20 +337,22 @@ int wdf_clipper_asym_fwd_tp(const float* x, const float* theta6, float fs, int m
     const dim3 grid((unsigned)((B + 63) / 64), (unsigned)K);
     hipStream_t s = (hipStream_t)stream;
     const bool v4 = (T % 4 == 0) && aligned16(x);
-    if (mode == WDF_ASYM_NEWTON_F64)
-        hipLaunchKernelGGL((wdf::clipper_asym_fwd_tp_kernel<true>), grid, dim3(64), 0, s, x, theta6, fs, y, zstash, z0, zT, zwarm, zend,
-                           tol, max_iter, (wdf::AsymTpStatus*)status, B, T, L, W);
-    else
-        hipLaunchKernelGGL((wdf::clipper_asym_fwd_tp_kernel<false>), grid, dim3(64), 0, s, x, theta6, fs, y, zstash, z0, zT, zwarm, zend,
-                           tol, max_iter, (wdf::AsymTpStatus*)status, B, T, L, W);
+#define WDF_ASYM_TP(MODE_)                                                                                                       \
+    hipLaunchKernelGGL((wdf::clipper_asym_fwd_tp_kernel<MODE_>), grid, dim3(64), 0, s, x, theta6, fs, y, zstash, z0, zT, zwarm, zend, \
+                       tol, max_iter, (wdf::AsymTpStatus*)status, B, T, L, W)
+    if (mode == WDF_ASYM_NEWTON_F64) WDF_ASYM_TP(wdf::kAsymNewton64);
+    else if (mode == WDF_ASYM_NEWTON_F32) WDF_ASYM_TP(wdf::kAsymNewton32);
+    else WDF_ASYM_TP(wdf::kAsymOmega);
+#undef WDF_ASYM_TP
     if (K > 1) {
         hipLaunchKernelGGL(wdf::asym_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, zwarm, zend, B, (int64_t)K, verify_tol, gate,
                            (wdf::AsymTpStatus*)status);
-#define WDF_ASYM_GATED(NEWTON_, V4_)                                                                                       \
-        hipLaunchKernelGGL((wdf::clipper_asym_fwd_kernel<NEWTON_, V4_>), dim3(grid.x), dim3(64), 0, s, x, theta6, fs, y, zstash, z0, \
+#define WDF_ASYM_GATED(MODE_, V4_)                                                                                         \
+        hipLaunchKernelGGL((wdf::clipper_asym_fwd_kernel<MODE_, V4_>), dim3(grid.x), dim3(64), 0, s, x, theta6, fs, y, zstash, z0, \
                            zT, tol, max_iter, (long long*)nullptr, B, T, (const unsigned*)gate)
-        if (mode == WDF_ASYM_NEWTON_F64) { if (v4) WDF_ASYM_GATED(true, true); else WDF_ASYM_GATED(true, false); }
-        else { if (v4) WDF_ASYM_GATED(false, true); else WDF_ASYM_GATED(false, false); }
+        if (mode == WDF_ASYM_NEWTON_F64) { if (v4) WDF_ASYM_GATED(wdf::kAsymNewton64, true); else WDF_ASYM_GATED(wdf::kAsymNewton64, false); }
+        else if (mode == WDF_ASYM_NEWTON_F32) { if (v4) WDF_ASYM_GATED(wdf::kAsymNewton32, true); else WDF_ASYM_GATED(wdf::kAsymNewton32, false); }
+        else { if (v4) WDF_ASYM_GATED(wdf::kAsymOmega, true); else WDF_ASYM_GATED(wdf::kAsymOmega, false); }
 #undef WDF_ASYM_GATED
     }
     return check_launch("wdf_clipper_asym_fwd_tp");
@@ -378,7 +386,7 @@ int wdf_clipper_asym_bwd_tp(const float* x, const float* theta6, float fs, int m
 {
     if (!x || !theta6 || !zstash || !zT || !gy || !ws || !gtheta6) return fail(WDF_EINVAL, "null x/theta6/zstash/zT/gy/ws/gtheta6");
     if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
-    if (mode != WDF_ASYM_OMEGA_F32 && mode != WDF_ASYM_NEWTON_F64) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (!asym_mode_known(mode)) return fail(WDF_EINVAL, "unknown mode %d", mode);
     if (n_chunks < 1) return fail(WDF_EINVAL, "n_chunks >= 1");
     int64_t L = (T + n_chunks - 1) / n_chunks;
     L = (L + 7) / 8 * 8;
@@ -391,7 +399,8 @@ int wdf_clipper_asym_bwd_tp(const float* x, const float* theta6, float fs, int m
     const bool v4 = (T % 4 == 0) && aligned16(x);
 #define WDF_ASYM_BWD(NEWTON_, V4_) \
     hipLaunchKernelGGL((wdf::clipper_asym_bwd_tp_kernel<NEWTON_, V4_>), grid, dim3(64), 0, s, x, theta6, fs, zstash, zT, gy, rec, B, T, L)
-    if (mode == WDF_ASYM_NEWTON_F64) { if (v4) WDF_ASYM_BWD(true, true); else WDF_ASYM_BWD(true, false); }
+    // both Newton modes: the exact pair, differentiated at the root the forward stored (nothing is re-solved)
+    if (mode != WDF_ASYM_OMEGA_F32) { if (v4) WDF_ASYM_BWD(true, true); else WDF_ASYM_BWD(true, false); }
     else { if (v4) WDF_ASYM_BWD(false, true); else WDF_ASYM_BWD(false, false); }
 #undef WDF_ASYM_BWD
     hipLaunchKernelGGL(wdf::clipper_asym_bwd_combine_kernel, dim3(grid.x), dim3(64), 0, s, (const double*)rec, gzT, part, gz0, B, (int64_t)K);
@@ -403,14 +412,16 @@ int wdf_asym_root(const float* a, const float* theta6, float fs, int mode, doubl
                   void* stream)
 {
     if (!a || !theta6 || !b || n <= 0) return fail(WDF_EINVAL, "wdf_asym_root: bad arguments");
-    if (mode != WDF_ASYM_OMEGA_F32 && mode != WDF_ASYM_NEWTON_F64) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (!asym_mode_known(mode)) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (mode == WDF_ASYM_NEWTON_F32 && (!(tol > 0.0) || max_iter < 1)) return fail(WDF_EINVAL, "tol > 0, max_iter >= 1");
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (mode == WDF_ASYM_NEWTON_F64)
-        hipLaunchKernelGGL((wdf::asym_root_kernel<true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, theta6, fs, b,
-                           tol, max_iter, n);
-    else
-        hipLaunchKernelGGL((wdf::asym_root_kernel<false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, theta6, fs, b,
-                           tol, max_iter, n);
+#define WDF_ASYM_ROOT(MODE_)                                                                                              \
+    hipLaunchKernelGGL((wdf::asym_root_kernel<MODE_>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, theta6, fs, b, \
+                       tol, max_iter, n)
+    if (mode == WDF_ASYM_NEWTON_F64) WDF_ASYM_ROOT(wdf::kAsymNewton64);
+    else if (mode == WDF_ASYM_NEWTON_F32) WDF_ASYM_ROOT(wdf::kAsymNewton32);
+    else WDF_ASYM_ROOT(wdf::kAsymOmega);
+#undef WDF_ASYM_ROOT
     return check_launch("wdf_asym_root");
 }
 

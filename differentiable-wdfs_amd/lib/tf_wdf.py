@@ -11,6 +11,9 @@ New surface (not in the reference):
   DiodePair(next, Is, Vt=25.85e-3, nDiodes=1, N_up=1, N_down=1, trainable=False)
       analytic Wright-omega diode-pair root (formula diode_pretraining.py:39-60, element
       protocol Toms917DiodePair.h:21-59) with trainable Is and nVt;
+  AsymDiodePair(next, Is_up, Is_down, Vt=25.85e-3, nDiodes_up=1, nDiodes_down=1, trainable=False, solver="newton_f32")
+      two DIFFERENT antiparallel diodes, the exact Shockley pair solved by Newton (csrc/wdf_asym.h); a root for
+      Circuit on the diode-clipper tree, trainable Is and nVt per diode;
   Circuit(top, root, probe) / run(...) / Circuit.mse(x, target)
       the fast tier: lowers the WHOLE per-sample loop the scripts own (lpf.py:39-46,
       clipper_pot.py:113-124) to one HIP kernel launch, and its tape.gradient to one reverse
@@ -244,6 +247,48 @@ class DiodePair(_Element):
 
     def reflected(self):
         return self._emit(_lowering.diode_pair_reflected(self))
+
+
+class AsymDiodePair(_Element):
+    '''ROOT of two DIFFERENT antiparallel diodes (new API; the reference's pairs are copies of one diode).
+
+        i(v) = Is_up (exp(v / nVt_up) - 1) - Is_down (exp(-v / nVt_down) - 1),   a = v + R i(v),   b = 2 v - a
+
+    The up diode conducts for v > 0 (csrc/wdf_asym.h).  Trainable variables: Is_up, nVt_up (= nDiodes_up * Vt), Is_down,
+    nVt_down, constrained like DiodePair's.  solver: "newton_f32" (default: the exact pair solved in fp32, y within fp32
+    rounding of the fp64 solve), "newton_f64" (the same in fp64, slower) or "omega_f32" (the Wright-omega closed form
+    stretched to unequal diodes: a MODEL APPROXIMATION that drops the reverse diode's saturation current, kept for
+    comparison).
+
+    The root runs inside tf_wdf.Circuit on the diode-clipper tree (Parallel(ResistiveVoltageSource, Capacitor), probe = the
+    capacitor): the fused loop takes the source's R and the capacitor's C, not a port resistance, so there is no
+    element-wise reflected().'''
+
+    SOLVERS = {"omega_f32": 0, "newton_f64": 1, "newton_f32": 2}          # wdf_hip.binding.ASYM_*
+
+    def __init__(self, next, Is_up, Is_down, Vt=25.85e-3, nDiodes_up=1.0, nDiodes_down=1.0, trainable=False,  # noqa: A002
+                 solver="newton_f32"):
+        super().__init__()
+        if solver not in self.SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(self.SOLVERS)}, got {solver!r}")
+        self.next = next
+        self.solver = solver
+        self.mode = self.SOLVERS[solver]
+
+        def var(value, name, lo, hi):
+            return tf.Variable(initial_value=value, name=name, dtype=tf.float32, trainable=trainable, constraint=_clipped(lo, hi))
+        self.Is_up = var(Is_up, "saturation_current_up", 1.0e-15, 1.0e-3)
+        self.nVt_up = var(float(nDiodes_up) * float(Vt), "n_thermal_voltage_up", 1.0e-3, 1.0)
+        self.Is_down = var(Is_down, "saturation_current_down", 1.0e-15, 1.0e-3)
+        self.nVt_down = var(float(nDiodes_down) * float(Vt), "n_thermal_voltage_down", 1.0e-3, 1.0)
+
+    def calc_impedance(self):
+        self.R = self.next.R
+
+    def reflected(self):
+        raise _lowering.binding.WdfHipError(
+            "AsymDiodePair has no element-wise reflected(): run it as the root of tf_wdf.Circuit on the diode-clipper tree "
+            "(Parallel(ResistiveVoltageSource, Capacitor), probe = the capacitor)")
 
 
 # ---- fast tier ------------------------------------------------------------------------------

@@ -988,7 +988,9 @@ def clipper_mlp_wgrad(ain, lrin, gb, theta2, w, hidden, n_tanh, fs):
     return gw
 
 
-ASYM_OMEGA_F32, ASYM_NEWTON_F64 = 0, 1
+# WDF_ASYM_*: the closed form is a model approximation (it drops the reverse diode's saturation current), kept for comparison;
+# the two Newton modes solve the exact pair -- in fp64, or entirely in fp32 (tolerance floor 4 FLT_EPSILON, fp32 state)
+ASYM_OMEGA_F32, ASYM_NEWTON_F64, ASYM_NEWTON_F32 = 0, 1, 2
 
 
 def clipper_asym_fwd(x, theta6, fs, mode, tol=1e-12, max_iter=50, z0=None, want_zT=False, want_iters=False, want_stash=False):
@@ -1049,7 +1051,7 @@ def clipper_asym_bwd(x, theta6, fs, zstash, gy, tol=1e-12, max_iter=50):
 
 
 def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None, want_gz0=False, ws=None):
-    """Time-parallel reverse sweep of the two-different-diode clipper, either mode (wdf_clipper_asym_bwd_tp): no root
+    """Time-parallel reverse sweep of the two-different-diode clipper, any mode (wdf_clipper_asym_bwd_tp): no root
     re-solve (consecutive stash entries give b), chunks composed exactly.  zT [B]: the forward's final state.
     -> gtheta6 (and dL/dz0 [B] when want_gz0)."""
     require_gpu()

@@ -54,6 +54,18 @@ def plan_time_parallel(B, T, R, C, fs, tol=1.0e-6, time_major=False, R_min=None)
     return TpPlan(k_fwd, W, float(tol), k_bwd)
 
 
+def plan_asym_time_parallel(B, T, R, C, fs, tol=1.0e-6):
+    """TpPlan for the two-different-diode clipper (csrc/wdf_asym.h); k_fwd = 1 (sequential forward) when T is too short for
+    two warmed-up chunks.  Its
+    kernels are one wave per 64 sequences and chunk like the symmetric pair's: the forward at ~2 waves per SIMD (a chunk
+    re-runs `warmup` steps from z = 0, so more chunks cost more), the exact reverse sweep at ~4 (no redundancy); the
+    warm-up outlasts the diode-off forgetting rate 1 - 2p, the slowest the state ever forgets (a conducting diode only
+    forgets faster).  At 8192 x 4096 and 45 kOhm / 4.7 nF that is 16 forward chunks warmed up over 192 steps and 32
+    reverse chunks: the fastest plan measured for every mode (profiles/r07_c5_asym_sweep.jsonl).  The forward verifies
+    every chunk boundary on the device and re-runs what misses: a poor plan costs time, never correctness."""
+    return plan_time_parallel(B, T, R, C, fs, tol=tol)
+
+
 _R_MAX_CACHE = ObjectMemo(256)      # tensor -> (max, min)
 
 
@@ -180,21 +192,23 @@ def clipper_stateful(theta, x, fs, r=None, n_up=1, n_down=1, z0=None):
 
 
 class _ClipperAsymFn(torch.autograd.Function):
-    """y [T,B] = clipper with two different antiparallel diodes, differentiable w.r.t.
-    theta6 = {Is_up, nVt_up, Is_down, nVt_down, R, C} (csrc/wdf_asym.h).  mode: fp64 Newton on the exact Shockley pair
-    (default) or the fp32 Wright-omega closed form -- each differentiates its own forward.  The reverse sweep is the
-    time-parallel one (no root re-solve, chunks composed exactly: wdf_clipper_asym_bwd_tp) unless tp says k_bwd = 0, which
-    keeps the sequential Newton-re-solving sweep (wdf_clipper_asym_bwd; Newton mode only)."""
+    """(y [T,B], zT [B]) = clipper with two different antiparallel diodes, differentiable w.r.t.
+    theta6 = {Is_up, nVt_up, Is_down, nVt_down, R, C} (csrc/wdf_asym.h).  mode: Newton on the exact Shockley pair in fp64
+    (default) or in fp32, or the fp32 Wright-omega closed form (a model approximation) -- each differentiates its own forward.
+    The reverse sweep is the time-parallel one (no root re-solve, chunks composed exactly: wdf_clipper_asym_bwd_tp) unless tp
+    says k_bwd = 0, which keeps the sequential Newton-re-solving sweep (wdf_clipper_asym_bwd; fp64 Newton mode only: the
+    other modes then run the time-parallel sweep with one chunk).  z0 is a constant of the call, zT comes back detached."""
 
     @staticmethod
-    def forward(ctx, theta6, x, fs, tol, max_iter, tp, mode):
+    def forward(ctx, theta6, x, fs, tol, max_iter, tp, mode, z0):
         th = theta6.detach().contiguous()
         if tp is not None and tp.k_fwd > 1:      # time chunks, verified on the device (wdf_clipper_asym_fwd_tp)
-            y, zT, zs, st = binding.clipper_asym_fwd_tp(x, th, fs, mode, tp.k_fwd, tp.warmup, tol=tol,
-                                                        max_iter=max_iter, verify_tol=tp.tol, want_stash=True, want_zT=True)
+            y, zT, zs, st = binding.clipper_asym_fwd_tp(x, th, fs, mode, tp.k_fwd, tp.warmup, tol=tol, max_iter=max_iter,
+                                                        verify_tol=tp.tol, z0=z0, want_stash=True, want_zT=True)
             LAST_TP_STATUS["status"] = st
         else:
-            y, zT, _, zs = binding.clipper_asym_fwd(x, th, fs, mode, tol=tol, max_iter=max_iter, want_stash=True, want_zT=True)
+            y, zT, _, zs = binding.clipper_asym_fwd(x, th, fs, mode, tol=tol, max_iter=max_iter, z0=z0, want_stash=True,
+                                                    want_zT=True)
         B, T = x.shape
         if tp is not None:
             k_bwd = int(tp.k_bwd)
@@ -202,26 +216,36 @@ class _ClipperAsymFn(torch.autograd.Function):
             k_bwd = max(1, min(T // 64, (2 * N_SIMD) // max(1, -(-B // 64))))
         ctx.cfg = (fs, tol, max_iter, mode, k_bwd)
         ctx.save_for_backward(th, x, zs, zT)
-        return y
+        ctx.mark_non_differentiable(zT)
+        return y, zT
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, _gzT):
         fs, tol, max_iter, mode, k_bwd = ctx.cfg
         th, x, zs, zT = ctx.saved_tensors
         if k_bwd < 1 and mode == binding.ASYM_NEWTON_F64:
             g = binding.clipper_asym_bwd(x, th, fs, zs, gy.contiguous(), tol=tol, max_iter=max_iter)
         else:
             g = binding.clipper_asym_bwd_tp(x, th, fs, mode, zs, zT, gy.contiguous(), max(1, k_bwd))
-        return g, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None
 
 
-def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None):
+def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None, z0=None, return_state=False):
     """Two-different-diode clipper loop (BASELINE config 5) with gradients to all six parameters.
-    mode: binding.ASYM_NEWTON_F64 (default: the exact model) or binding.ASYM_OMEGA_F32 (the fp32 closed form).
-    tp: a TpPlan (plan_time_parallel with the circuit's R, C) -> the forward runs in k_fwd verified time chunks and the
-    reverse sweep in k_bwd exact ones (k_bwd = 0: the sequential sweep)."""
+    mode: binding.ASYM_NEWTON_F64 (default: the exact model in fp64), binding.ASYM_NEWTON_F32 (the exact model in fp32: the
+    fast one; tol is floored at 4 FLT_EPSILON) or binding.ASYM_OMEGA_F32 (the fp32 closed form: a model approximation, kept
+    for comparison).
+    tp: a TpPlan (plan_asym_time_parallel with the circuit's R, C) -> the forward runs in k_fwd verified time chunks and the
+    reverse sweep in k_bwd exact ones (k_bwd = 0: the sequential sweep, fp64 Newton mode; one exact chunk otherwise).
+    z0 [B]: the capacitor state the loop starts from (default zero), a constant of the call: no gradient flows into it.
+    return_state: -> (y, zT), zT [B] the state the loop ended in, detached."""
     mode = binding.ASYM_NEWTON_F64 if mode is None else int(mode)
-    return _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode)
+    if z0 is not None:
+        z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        if z0.numel() != x.shape[0]:
+            raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    y, zT = _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode, z0)
+    return (y, zT) if return_state else y
 
 
 class MseStep:

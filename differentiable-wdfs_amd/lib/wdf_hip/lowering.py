@@ -687,7 +687,7 @@ class Circuit:
         self.caps = [e for e in self.elements if _kind(e) == "Capacitor"]
         self.sources = [e for e in self.elements if _kind(e) == "ResistiveVoltageSource"]
         self.root_kind = _kind(root)
-        if self.root_kind not in ("IdealVoltageSource", "DiodePair", "DenseRootModel"):
+        if self.root_kind not in ("IdealVoltageSource", "DiodePair", "AsymDiodePair", "DenseRootModel"):
             raise ValueError(f"unsupported root {self.root_kind}")
         self.ns = len(self.caps)
         self.ni = len(self.sources) + (1 if self.root_kind == "IdealVoltageSource" else 0)
@@ -697,6 +697,9 @@ class Circuit:
                              "tf_wdf.py:51-52,80-81)")
         if self.ni < 1:
             raise ValueError("the circuit has no voltage source")
+        if self.root_kind == "AsymDiodePair" and not (self._is_clipper() and per_sample_R is None and not self.force_generic):
+            raise binding.WdfHipError("an AsymDiodePair root runs on the diode-clipper tree only: top = Parallel(ResistiveVoltageSource, "
+                                      "Capacitor), probe = the capacitor, no per_sample_R, not force_generic (csrc/wdf_asym.h)")
         # Outside the clipper topology a per-sample impedance or a DenseRootModel root runs on the streamed-coefficient kernels
         # (csrc/wdf_ss_dyn.h) -- and so does, since round 6, ANY tree of five to eight capacitors (the static-coefficient kernels
         # of csrc/wdf_statespace.h are compiled for at most four: a larger tree hands the streamed kernels one static row)
@@ -714,6 +717,9 @@ class Circuit:
         lpf.py:86-99 / clipper_pot.py:245-269 run without a host round trip per step (print / .numpy() / float() on a
         Variable still work: they copy back on demand).  Diode-clipper topology only: the generic lowering differentiates
         its float64 probe on the host and needs the Variables there.  Returns self."""
+        if self.root_kind == "AsymDiodePair":
+            raise binding.WdfHipError("Circuit.to_device: there is no resident training step for an AsymDiodePair root; the circuit "
+                                      "trains on the host path (its forward and reverse sweep are single launches either way)")
         binding.require_gpu()
         if any(getattr(self, a, None) is not None for a in ("_lin", "_pblock", "_tree", "_mlp", "_dynres")):
             return self
@@ -1009,6 +1015,8 @@ class Circuit:
             return self._run_dyn(x, z0, return_state)
         if self._is_clipper() and self.root_kind == "DiodePair" and not self.force_generic:
             return self._run_clipper(x, z0, return_state)
+        if self.root_kind == "AsymDiodePair":
+            return self._run_clipper_asym(x, z0, return_state)
         if self.root_kind == "DenseRootModel":
             from . import mlp_root
             return mlp_root.run_clipper_mlp(self, x, z0, return_state)
@@ -1209,6 +1217,26 @@ class Circuit:
         plan = SsTpPlan(k_fwd, W, float(tol), k_max)
         cache[key] = (plan, 0)
         return plan
+
+    def _run_clipper_asym(self, x, z0, return_state):
+        """The clipper tree under an AsymDiodePair root: one launch of the two-different-diode loop (engine.clipper_asym) in the
+        root's solver mode, gradients to the four diode Variables, R and C."""
+        from . import engine
+        dp, vs, cap = self.root, self.top.P1, self.top.P2
+        dev = x.device
+        Rv = vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R))
+        parts = [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, Rv, cap.C]
+        theta6 = self._theta(parts, dev)
+        xv, _ = engine.split_channels(x, False, anchor=getattr(self, "_anchor", None))
+        tp = self.time_parallel
+        if tp == "auto":
+            tp = engine.plan_asym_time_parallel(xv.shape[0], xv.shape[1], float(parts[4]), float(parts[5]), float(cap.FS))
+        elif not isinstance(tp, engine.TpPlan):
+            tp = None
+        z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor)
+        y, zT = engine.clipper_asym(theta6, xv, float(cap.FS), tp=tp, mode=dp.mode, z0=z0t, return_state=True)
+        y = y.as_subclass(tf.Tensor)
+        return (y, zT.reshape(1, -1)) if return_state else y
 
     def _run_clipper(self, x, z0, return_state):
         from . import engine

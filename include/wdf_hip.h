@@ -548,10 +548,19 @@ int wdf_ss_dyn_rows_bwd(const int32_t* tape_ops, int n_ops, const double* consts
  * Clipper with two DIFFERENT antiparallel diodes (BASELINE config 5; csrc/wdf_asym.h).  New
  * API, no reference counterpart (its pairs are copies of one diode, diode_pretraining.py:46-47).
  * theta6  device float[6] = {Is_up, nVt_up, Is_down, nVt_down, R, C}
- * mode    WDF_ASYM_OMEGA_F32: fp32 Wright-omega closed form (two-diode form of eqn 39);
+ * mode    WDF_ASYM_OMEGA_F32: fp32 Wright-omega closed form (two-diode form of eqn 39).  A MODEL
+ *         APPROXIMATION, not a precision point: it drops the reverse diode's saturation current
+ *         (~Rp Is_down at the root, 0.1 V on y for a germanium-like pair); kept for comparison;
  *         WDF_ASYM_NEWTON_F64: fp64 Newton on the exact Shockley pair, iterated per wave until
  *         every lane meets |dv| <= tol (|v| + nVt) (wavefront ballot) or max_iter; two iterations
- *         in fp32 from the closed form's value come first (counted in iters).
+ *         in fp32 from the closed form's value come first (counted in iters);
+ *         WDF_ASYM_NEWTON_F32: the same equation, v + Rp i(v) - a = 0 with
+ *         i(v) = Is_up (exp(v/nVt_up) - 1) - Is_down (exp(-v/nVt_down) - 1), solved by damped Newton
+ *         entirely in fp32 from the closed form's value, same ballot and max_iter, b = 2 v - a.
+ *         fp32 cannot resolve a step below the last bit of v, so the tolerance in effect is
+ *         max(tol, 4 FLT_EPSILON) = 4.8e-7 (tol must still be > 0, max_iter >= 1).  Its state and its
+ *         stash are fp32; y agrees with the fp64 mode to fp32 rounding.  Its reverse sweep is
+ *         wdf_clipper_asym_bwd_tp (wdf_clipper_asym_bwd re-solves in fp64 and has no mode).
  * iters   optional device int64[(B+63)/64]: Newton iterations each wave ran (sum / (B T / 64
  *         * ...) gives the mean per sample).
  * zstash  optional [T][B]: state before each step, for wdf_clipper_asym_bwd.
@@ -561,6 +570,7 @@ int wdf_ss_dyn_rows_bwd(const int32_t* tape_ops, int n_ops, const double* consts
  * wdf_asym_root: b[i] = root(a[i]) (double out) for accuracy sweeps.
  * ---------------------------------------------------------------------------------- */
 enum { WDF_ASYM_OMEGA_F32 = 0, WDF_ASYM_NEWTON_F64 = 1 };
+#define WDF_ASYM_NEWTON_F32 2
 int wdf_clipper_asym_fwd(const float* x, const float* theta6, float fs, int mode, double tol, int max_iter,
                          float* y, float* zstash, const float* z0, float* zT, long long* iters,
                          int64_t B, int64_t T, void* stream);
@@ -577,11 +587,11 @@ size_t wdf_clipper_asym_bwd_ws_bytes(int64_t B);
 int wdf_clipper_asym_bwd(const float* x, const float* theta6, float fs, double tol, int max_iter,
                          const float* zstash, const float* gy, void* ws, float* gtheta6,
                          int64_t B, int64_t T, void* stream);
-/* Time-parallel reverse sweep, BOTH modes (round 5).  The root is not re-solved: b = z[t+1] + p (z[t] - x[t]) from two
+/* Time-parallel reverse sweep, ALL modes (round 5).  The root is not re-solved: b = z[t+1] + p (z[t] - x[t]) from two
  * consecutive stash entries (zT = z[T], as wdf_clipper_asym_fwd(_tp) returns it); the adjoint recurrence is linear in the
  * adjoint entering a chunk, so the n_chunks chunks (a count that tiles T in 8-step units) run independently and one walk per
- * sequence composes them -- exact.  mode NEWTON differentiates the exact Shockley pair implicitly (wdf_clipper_asym_bwd's
- * formulas), mode OMEGA the fp32 closed form the OMEGA forward evaluates.  gzT (optional [B]): dL/dz[T]; gz0 (optional [B]):
+ * sequence composes them -- exact.  Both NEWTON modes differentiate the exact Shockley pair implicitly (wdf_clipper_asym_bwd's
+ * formulas) at the root their forward stored, mode OMEGA the fp32 closed form the OMEGA forward evaluates.  gzT (optional [B]): dL/dz[T]; gz0 (optional [B]):
  * receives dL/dz[0].  ws: wdf_clipper_asym_bwd_tp_ws_bytes(B, n_chunks). */
 size_t wdf_clipper_asym_bwd_tp_ws_bytes(int64_t B, int n_chunks);
 int wdf_clipper_asym_bwd_tp(const float* x, const float* theta6, float fs, int mode, const float* zstash, const float* zT,
