@@ -91,9 +91,10 @@ __device__ __forceinline__ float asym_newton_f32(const AsymConsts& c, float a, f
     return v;
 }
 
-// returns b; *iters += Newton iterations this wave ran
-__device__ __forceinline__ double asym_newton_root(const AsymConsts& c, double a, double v0, double tol, int max_iter,
-                                                   int& iters)
+// returns b; *iters += Newton iterations this wave ran.  v_out, e1_out, e2_out: the root and exp(v/V1), exp(-v/V2) there --
+// the loop carries them anyway, so a caller that differentiates the root (wdf_asym_step.h) exponentiates nothing again.
+__device__ __forceinline__ double asym_newton_solve(const AsymConsts& c, double a, double v0, double tol, int max_iter,
+                                                    int& iters, double& v_out, double& e1_out, double& e2_out)
 {
     const double Rp = c.Rp, Is1 = c.Is1, Is2 = c.Is2, iV1 = 1.0 / (double)c.V1, iV2 = 1.0 / (double)c.V2;
     const double vscale = fmin((double)c.V1, (double)c.V2);
@@ -129,7 +130,15 @@ __device__ __forceinline__ double asym_newton_root(const AsymConsts& c, double a
         if (__builtin_amdgcn_ballot_w64(active) == 0) break;     // the whole wave has converged
     }
     const double i = Is1 * (e1 - 1.0) - Is2 * (e2 - 1.0);
+    v_out = v; e1_out = e1; e2_out = e2;
     return v - Rp * i;
+}
+
+__device__ __forceinline__ double asym_newton_root(const AsymConsts& c, double a, double v0, double tol, int max_iter,
+                                                   int& iters)
+{
+    double v, e1, e2;
+    return asym_newton_solve(c, a, v0, tol, max_iter, iters, v, e1, e2);
 }
 
 // The exact pair solved in fp32: returns b; iters += Newton iterations this wave ran.  Start value: the closed form's
@@ -138,45 +147,79 @@ __device__ __forceinline__ double asym_newton_root(const AsymConsts& c, double a
 // iteration stalls cleanly (3e-7 observed); any smaller tolerance is met only by chance, dv then being the last bit of v.
 // The exponentials are evaluated afresh every iteration: a carried exponential times a polynomial in dv (the fp64 loop's
 // saving) costs as many issue cycles as the two v_exp_f32 it replaces and adds an fp32 rounding per iteration to e.
-__device__ __forceinline__ float asym_newton32_root(const AsymConsts& c, float a, double tol, int max_iter, int& iters)
+// v_out, e1_out, e2_out: the root and exp(v/V1), exp(-v/V2) there, for a caller that differentiates it (wdf_asym_step.h).  The
+// loop's last exponentials belong to the iterate before the last step dv: times exp(-+dv/V) to second order they are the
+// root's (|dv|/V < 1e-3, which every converged wave meets by orders of magnitude: 2e-10 relative); a wave with a lane
+// outside that bound -- max_iter ran out -- exponentiates again.  A caller that does not use them pays nothing.
+__device__ __forceinline__ float asym_newton32_solve(const AsymConsts& c, float a, double tol, int max_iter, int& iters,
+                                                     float& v_out, float& e1_out, float& e2_out)
 {
     const float iV1 = fast_rcp(c.V1), iV2 = fast_rcp(c.V2), vscale = fminf(c.V1, c.V2), lim = 4.0f * vscale;
     const float k1 = c.Rp * c.Is1, k2 = c.Rp * c.Is2, d1 = k1 * iV1, d2 = k2 * iV2;
     const float tl = fmaxf((float)tol, 4.0f * FLT_EPSILON);
     float v = 0.5f * (a + asym_omega_root(c, a));
+    float e1 = 1.0f, e2 = 1.0f, dv = 0.0f;
     for (int it = 0; it < max_iter; ++it) {
-        const float e1 = fast_exp(v * iV1), e2 = fast_exp(-v * iV2);
+        e1 = fast_exp(v * iV1);
+        e2 = fast_exp(-v * iV2);
         const float f = (v - a) + fmaf(k1, e1 - 1.0f, -k2 * (e2 - 1.0f));
         const float fp = fmaf(d1, e1, fmaf(d2, e2, 1.0f));
         const float q = f * fast_rcp(fp);
         // (not a number -- v_exp_f32 overflowed on a wild start value -- moves nothing: see asym_newton_f32)
-        const float dv = (q == q) ? fminf(fmaxf(q, -lim), lim) : 0.0f;
+        dv = (q == q) ? fminf(fmaxf(q, -lim), lim) : 0.0f;
         v -= dv;
         ++iters;
         const bool active = fabsf(dv) > tl * (fabsf(v) + vscale);
         if (__builtin_amdgcn_ballot_w64(active) == 0) break;     // the whole wave has converged
     }
+    const float s1 = -dv * iV1, s2 = dv * iV2;
+    if (__builtin_amdgcn_ballot_w64(!(fmaxf(fabsf(s1), fabsf(s2)) < 1.0e-3f)) != 0) {
+        e1 = fast_exp(v * iV1);
+        e2 = fast_exp(-v * iV2);
+    } else {
+        e1 *= fmaf(s1, fmaf(s1, 0.5f, 1.0f), 1.0f);
+        e2 *= fmaf(s2, fmaf(s2, 0.5f, 1.0f), 1.0f);
+    }
+    v_out = v; e1_out = e1; e2_out = e2;
     return fmaf(2.0f, v, -a);
 }
 
+__device__ __forceinline__ float asym_newton32_root(const AsymConsts& c, float a, double tol, int max_iter, int& iters)
+{
+    float v, e1, e2;
+    return asym_newton32_solve(c, a, tol, max_iter, iters, v, e1, e2);
+}
+
 // One step of the tree around the root; S is the state type (double for NEWTON_F64, float otherwise).
+// the root a Newton-mode step solved and the two exponentials there (fp32: what the local partials are formed from)
+struct AsymRootAt { float v, e1, e2; };
+
 template <int MODE>
 struct AsymStep;
 template <>
 struct AsymStep<kAsymNewton64> {
     using S = double;
-    static __device__ __forceinline__ float run(const AsymConsts& c, float xin, double& z, double tol, int max_iter,
-                                                int& iters)
+    static __device__ __forceinline__ float run_at(const AsymConsts& c, float xin, double& z, double tol, int max_iter,
+                                                   int& iters, AsymRootAt& at)
     {
         const double b_diff = z - (double)xin;
         const double b_temp = -(double)c.p * b_diff;
         const double a = z + b_temp;
         const float bw = asym_omega_root(c, (float)a);                   // start value: v0 = (a + b)/2 of the closed form
-        const double br = asym_newton_root(c, a, (double)asym_newton_f32(c, (float)a, 0.5f * ((float)a + bw), iters), tol, max_iter, iters);
+        double v, e1, e2;
+        const double br = asym_newton_solve(c, a, (double)asym_newton_f32(c, (float)a, 0.5f * ((float)a + bw), iters), tol, max_iter, iters,
+                                            v, e1, e2);
+        at = AsymRootAt{(float)v, (float)e1, (float)e2};
         const double zn = br + b_temp;
         const float y = (float)(0.5 * (zn + z));
         z = zn;
         return y;
+    }
+    static __device__ __forceinline__ float run(const AsymConsts& c, float xin, double& z, double tol, int max_iter,
+                                                int& iters)
+    {
+        AsymRootAt at;
+        return run_at(c, xin, z, tol, max_iter, iters, at);
     }
 };
 template <>
@@ -196,15 +239,21 @@ struct AsymStep<kAsymOmega> {
 template <>
 struct AsymStep<kAsymNewton32> {
     using S = float;
-    static __device__ __forceinline__ float run(const AsymConsts& c, float xin, float& z, double tol, int max_iter, int& iters)
+    static __device__ __forceinline__ float run_at(const AsymConsts& c, float xin, float& z, double tol, int max_iter, int& iters,
+                                                   AsymRootAt& at)
     {
         const float b_diff = z - xin;
         const float b_temp = -c.p * b_diff;
         const float a = z + b_temp;
-        const float zn = asym_newton32_root(c, a, tol, max_iter, iters) + b_temp;
+        const float zn = asym_newton32_solve(c, a, tol, max_iter, iters, at.v, at.e1, at.e2) + b_temp;
         const float y = 0.5f * (zn + z);
         z = zn;
         return y;
+    }
+    static __device__ __forceinline__ float run(const AsymConsts& c, float xin, float& z, double tol, int max_iter, int& iters)
+    {
+        AsymRootAt at;
+        return run_at(c, xin, z, tol, max_iter, iters, at);
     }
 };
 
@@ -456,6 +505,21 @@ static __global__ __launch_bounds__(256) void clipper_asym_grad_reduce_kernel(co
 // rec: double [K][14][B] = {P, q, alpha[6], beta[6]}.   L is a multiple of 8.
 constexpr int kAsymRec = 14;
 
+// The Newton modes' local partials at a root v (e1 = exp(v/V1), e2 = exp(-v/V2)), the formulas above in fp32:
+// Da = d b / d a and cf = d b / d{Is1, V1, Is2, V2, Rp}.  Shared by the reverse sweep and the one-pass step (wdf_asym_step.h).
+__device__ __forceinline__ void asym_newton_partials(const AsymConsts& c, float v, float e1, float e2, float& Daf, float (&cf)[5])
+{
+    const float iV1 = fast_rcp(c.V1), iV2 = fast_rcp(c.V2);
+    const float iF = fast_rcp(fmaf(c.Rp, fmaf(c.Is1 * iV1, e1, c.Is2 * iV2 * e2), 1.0f));
+    Daf = fmaf(2.0f, iF, -1.0f);
+    const float k2 = -2.0f * iF, k2R = k2 * c.Rp;
+    cf[0] = k2R * (e1 - 1.0f);
+    cf[1] = -k2R * c.Is1 * e1 * v * iV1 * iV1;
+    cf[2] = -k2R * (e2 - 1.0f);
+    cf[3] = -k2R * c.Is2 * e2 * v * iV2 * iV2;
+    cf[4] = k2 * fmaf(c.Is1, e1 - 1.0f, -c.Is2 * (e2 - 1.0f));
+}
+
 template <bool NEWTON, bool VEC4>
 __global__ __launch_bounds__(64) void clipper_asym_bwd_tp_kernel(const float* __restrict__ x, const float* __restrict__ theta6,
                                                                  float fs, const float* __restrict__ zstash,
@@ -506,15 +570,7 @@ __global__ __launch_bounds__(64) void clipper_asym_bwd_tp_kernel(const float* __
                     const float br = fmaf(c.p, bd, znext);        // b = z[t+1] + p (z[t] - x[t]): no re-solve
                     const float v = 0.5f * (a + br);
                     const float iV1 = fast_rcp(c.V1), iV2 = fast_rcp(c.V2);
-                    const float e1 = fast_exp(v * iV1), e2 = fast_exp(-v * iV2);
-                    const float iF = fast_rcp(fmaf(c.Rp, fmaf(c.Is1 * iV1, e1, c.Is2 * iV2 * e2), 1.0f));
-                    Daf = fmaf(2.0f, iF, -1.0f);
-                    const float k2 = -2.0f * iF, k2R = k2 * c.Rp;
-                    cf[0] = k2R * (e1 - 1.0f);
-                    cf[1] = -k2R * c.Is1 * e1 * v * iV1 * iV1;
-                    cf[2] = -k2R * (e2 - 1.0f);
-                    cf[3] = -k2R * c.Is2 * e2 * v * iV2 * iV2;
-                    cf[4] = k2 * fmaf(c.Is1, e1 - 1.0f, -c.Is2 * (e2 - 1.0f));
+                    asym_newton_partials(c, v, fast_exp(v * iV1), fast_exp(-v * iV2), Daf, cf);
                 } else {
                     const float lam = vsign(a), aa = fabsf(a);
                     const bool pos = a >= 0.0f;

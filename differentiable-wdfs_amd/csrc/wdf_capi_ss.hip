@@ -5,6 +5,7 @@
 #include "wdf_statespace.h"
 #include "wdf_ss_step.h"
 #include "wdf_asym.h"
+#include "wdf_asym_step.h"
 using namespace wdfcapi;
 
 namespace {
@@ -423,6 +424,72 @@ int wdf_asym_root(const float* a, const float* theta6, float fs, int mode, doubl
     else WDF_ASYM_ROOT(wdf::kAsymOmega);
 #undef WDF_ASYM_ROOT
     return check_launch("wdf_asym_root");
+}
+
+// ---- the one-pass MSE step of the two-different-diode clipper (wdf_asym_step.h) ------------------------------------------
+// ws: [records double K x 15 x B][per-wave partials double waves x 8][zwarm, zend float K x B each][gate unsigned waves][ticket]
+size_t wdf_clipper_asym_step_mse_ws_bytes(int64_t B, int n_chunks)
+{
+    if (B <= 0 || n_chunks <= 0) return 0;
+    const size_t waves = (size_t)((B + 63) / 64);
+    return ((size_t)n_chunks * (size_t)wdf::kAsymStepRec * (size_t)B + waves * 8) * sizeof(double) +
+           (size_t)2 * (size_t)n_chunks * (size_t)B * sizeof(float) + (waves + 2) * sizeof(unsigned);
+}
+
+int wdf_clipper_asym_step_mse(const float* x, float* theta6, float fs, int mode, double tol, int max_iter, const float* target,
+                              float gscale, float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                              float verify_tol, void* ws, void* status, float* out7, float* m, float* v, int32_t* step,
+                              const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream)
+{
+    if (!x || !theta6 || !target || !y || !ws || !status || !out7) return fail(WDF_EINVAL, "null x/theta6/target/y/ws/status/out7");
+    if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
+    if (!asym_mode_known(mode)) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (mode == WDF_ASYM_OMEGA_F32)
+        return fail(WDF_EINVAL, "mode 0 (the closed form) has no one-pass step: use wdf_clipper_asym_fwd_tp + wdf_clipper_asym_bwd_tp");
+    if (!(tol > 0.0) || max_iter < 1) return fail(WDF_EINVAL, "tol > 0, max_iter >= 1");
+    if (n_chunks < 1 || n_chunks > 65535 || warmup < 0 || !(verify_tol >= 0.0f))
+        return fail(WDF_EINVAL, "n_chunks in 1..65535, warmup >= 0, verify_tol >= 0");
+    if (!aligned8(ws)) return fail(WDF_EINVAL, "ws must be 8-byte aligned");
+    if (z0 && z0 == zT) return fail(WDF_EINVAL, "zT must not alias z0 (every chunk that starts at t = 0 reads z0)");
+    if (m && (!v || !step || !lr)) return fail(WDF_EINVAL, "Adam: m, v, step and lr go together");
+    int64_t L = (T + n_chunks - 1) / n_chunks;
+    L = (L + 7) / 8 * 8;
+    const int K = (int)((T + L - 1) / L);
+    if (K != n_chunks) return fail(WDF_EINVAL, "n_chunks = %d does not tile T = %lld in 8-step units (%d does)", n_chunks, (long long)T, K);
+    const int64_t W = ((int64_t)warmup + 7) / 8 * 8;
+    const int64_t Lall = (T + 7) / 8 * 8;                       // one chunk: the repair launch
+    const size_t waves = (size_t)((B + 63) / 64);
+    double* rec = (double*)ws;
+    double* part = rec + (size_t)K * (size_t)wdf::kAsymStepRec * (size_t)B;
+    float* zwarm = (float*)(part + waves * 8);
+    float* zend = zwarm + (size_t)K * (size_t)B;
+    unsigned* gate = (unsigned*)(zend + (size_t)K * (size_t)B);
+    unsigned* ticket = gate + waves;
+    const dim3 grid((unsigned)waves, (unsigned)K);
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = (T % 4 == 0) && aligned16(x);
+    const wdf::AsymStepAdam adam{m, v, step, lr, lo, hi, beta1, beta2, eps};
+#define WDF_ASYM_STEP(MODE_, V4_, GRID_, GATE_, L_)                                                                              \
+    hipLaunchKernelGGL((wdf::clipper_asym_step_kernel<MODE_, V4_>), GRID_, dim3(64), 0, s, x, (const float*)theta6, fs, target, y, z0, \
+                       zT, zwarm, zend, rec, tol, max_iter, (wdf::AsymTpStatus*)status, ticket, (const unsigned*)(GATE_), B, T, L_, W)
+#define WDF_ASYM_STEP_MODES(GRID_, GATE_, L_)                                                                                    \
+    if (mode == WDF_ASYM_NEWTON_F64) { if (v4) WDF_ASYM_STEP(wdf::kAsymNewton64, true, GRID_, GATE_, L_); else WDF_ASYM_STEP(wdf::kAsymNewton64, false, GRID_, GATE_, L_); } \
+    else { if (v4) WDF_ASYM_STEP(wdf::kAsymNewton32, true, GRID_, GATE_, L_); else WDF_ASYM_STEP(wdf::kAsymNewton32, false, GRID_, GATE_, L_); }
+    {
+        EventBracket bracket(s);
+        WDF_ASYM_STEP_MODES(grid, nullptr, L)
+    }
+    if (K > 1) {
+        // every boundary checked on the device; the waves where one missed run again, exactly, as one chunk
+        hipLaunchKernelGGL(wdf::asym_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, zwarm, zend, B, (int64_t)K, verify_tol, gate,
+                           (wdf::AsymTpStatus*)status);
+        WDF_ASYM_STEP_MODES(dim3(grid.x), gate, Lall)
+    }
+#undef WDF_ASYM_STEP_MODES
+#undef WDF_ASYM_STEP
+    hipLaunchKernelGGL(wdf::clipper_asym_step_finish_kernel, dim3(grid.x), dim3(64), 0, s, (const double*)rec,
+                       (const unsigned*)(K > 1 ? gate : nullptr), part, ticket, theta6, fs, gscale, out7, adam, B, (int64_t)K);
+    return check_launch("wdf_clipper_asym_step_mse");
 }
 
 // ---- the one-pass MSE step of linear trees (wdf_ss_step.h) -------------------------------------------------------------

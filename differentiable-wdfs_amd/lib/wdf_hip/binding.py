@@ -161,6 +161,11 @@ def lib():
     L.wdf_ss_dyn_rows_bwd.argtypes = [ip, ci, dp, ci, ip, ci, vp, ci, ci, fp, fp, vp, vp, i64, i64, vp]
     L.wdf_clipper_mlp_wgrad_matrix_core_chunks.restype = ci
     L.wdf_clipper_mlp_wgrad_matrix_core_chunks.argtypes = [i64, i64]
+    L.wdf_clipper_asym_step_mse_ws_bytes.restype = C.c_size_t
+    L.wdf_clipper_asym_step_mse_ws_bytes.argtypes = [i64, ci]
+    L.wdf_clipper_asym_step_mse.restype = ci
+    L.wdf_clipper_asym_step_mse.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, cf, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, fp,
+                                            fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
     L.wdf_asym_root.restype = ci
     L.wdf_asym_root.argtypes = [fp, fp, cf, ci, C.c_double, ci, vp, i64, vp]
     L.wdf_mlp_weight_count.restype = ci
@@ -294,6 +299,7 @@ EXPORTED_SYMBOLS = (
     "wdf_clipper_step_mse_tp", "wdf_clipper_step_esr_tp", "wdf_esr_finish", "wdf_loss_sums_ws_bytes", "wdf_loss_sums", "wdf_esr_coef", "wdf_loss_esr_grad", "wdf_clipper_bwd_esr_tp",
     "wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp_ws_bytes", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_ws_bytes", "wdf_clipper_asym_bwd",
     "wdf_clipper_asym_bwd_tp_ws_bytes", "wdf_clipper_asym_bwd_tp", "wdf_asym_root",
+    "wdf_clipper_asym_step_mse_ws_bytes", "wdf_clipper_asym_step_mse",
     "wdf_ss_dyn_row_len", "wdf_ss_dyn_fwd", "wdf_ss_dyn_bwd_ws_bytes", "wdf_ss_dyn_bwd", "wdf_clipper_mlp_wgrad_matrix_core_chunks",
     "wdf_ss_dyn_fwd_tp_ws_bytes", "wdf_ss_dyn_fwd_tp", "wdf_ss_dyn_bwd_tp_ws_bytes", "wdf_ss_dyn_bwd_tp",
     "wdf_ss_dyn_rows", "wdf_ss_dyn_rows_bwd_ws_bytes", "wdf_ss_dyn_rows_bwd",
@@ -1071,6 +1077,58 @@ def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None,
                                        _ptr(ws), _ptr(g), _ptr(gz0), B, T, K, _stream())
     _check(rc, "wdf_clipper_asym_bwd_tp")
     return (g, gz0) if want_gz0 else g
+
+
+def asym_chunks(T, n_chunks):
+    """The chunk count the asym kernels accept for T: n_chunks rounded to one that tiles T in 8-step units."""
+    Lc = -(-(-(-int(T) // max(1, int(n_chunks)))) // 8) * 8
+    return -(-int(T) // Lc)
+
+
+def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, y=None,
+                          z0=None, want_zT=False, ws=None, status=None, out7=None, opt=None):
+    """The MSE training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_mse): forward,
+    loss and d(gscale/2 sum (y - target)^2)/d{Is_up, nVt_up, Is_down, nVt_down, R, C}, x [B,T] and target [T,B] read once, y
+    written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is rounded like asym_chunks(); y, ws, status,
+    out7 can be preallocated; opt: a binding.Adam(6, ...) to update theta6 in the step's last launch.
+    -> y [T,B], zT [B] | None, out7 = {sse, gtheta6}, status (int32[4]; read with mlp_tp_status())."""
+    require_gpu()
+    x, theta6, target, z0 = _f32_dev(x, "x"), _f32_dev(theta6, "theta6"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
+    if theta6.numel() != 6:
+        raise WdfHipError("theta6 must hold {Is_up, nVt_up, Is_down, nVt_down, R, C}")
+    B, T = x.shape
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if z0 is not None and z0.numel() != B:
+        raise WdfHipError(f"z0 must hold one state per sequence ({B})")
+    if opt is not None and opt.n != 6:
+        raise WdfHipError("clipper_asym_step_mse: the optimizer holds {Is_up, nVt_up, Is_down, nVt_down, R, C}")
+    K = asym_chunks(T, n_chunks)
+    if y is None:
+        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
+    elif tuple(_f32_dev(y, "y").shape) != (T, B):
+        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
+    need = lib().wdf_clipper_asym_step_mse_ws_bytes(B, K)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
+    if status is None:
+        status = torch.empty((4,), dtype=torch.int32, device=x.device)
+    if out7 is None:
+        out7 = torch.empty((7,), dtype=torch.float32, device=x.device)
+    elif _f32_dev(out7, "out7").numel() != 7:
+        raise WdfHipError("out7 must hold {sse, gtheta6}")
+    o = opt
+    rc = lib().wdf_clipper_asym_step_mse(
+        _ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(gscale), _ptr(y), _ptr(z0),
+        _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(out7),
+        *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
+        0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
+        None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
+    _check(rc, "wdf_clipper_asym_step_mse")
+    return y, zT, out7, status
 
 
 def asym_root(a, theta6, fs, mode, tol=1e-12, max_iter=50):

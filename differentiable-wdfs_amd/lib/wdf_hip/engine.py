@@ -62,7 +62,8 @@ def plan_asym_time_parallel(B, T, R, C, fs, tol=1.0e-6):
     warm-up outlasts the diode-off forgetting rate 1 - 2p, the slowest the state ever forgets (a conducting diode only
     forgets faster).  At 8192 x 4096 and 45 kOhm / 4.7 nF that is 16 forward chunks warmed up over 192 steps and 32
     reverse chunks: the fastest plan measured for every mode (profiles/r07_c5_asym_sweep.jsonl).  The forward verifies
-    every chunk boundary on the device and re-runs what misses: a poor plan costs time, never correctness."""
+    every chunk boundary on the device and re-runs what misses: a poor plan costs time, never correctness.  The one-pass
+    step (AsymMseStep) takes k_fwd, warmup and tol from the same plan and ignores k_bwd: it has no reverse chunks."""
     return plan_time_parallel(B, T, R, C, fs, tol=tol)
 
 
@@ -246,6 +247,88 @@ def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None, z0
             raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
     y, zT = _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode, z0)
     return (y, zT) if return_state else y
+
+
+class AsymMseStep:
+    """The MSE training step of the two-different-diode clipper in one pass over the data (csrc/wdf_asym_step.h,
+    binding.clipper_asym_step_mse): forward, loss and gradient in one sweep, x [B,T] and target [T,B] read once, y written
+    once, no stash, no dL/dy array, no reverse sweep.  Buffers are allocated once; step_fused() returns device tensors
+    (sse[1], gtheta6[6]) -- views of self.out = {sse, dIs_up, dnVt_up, dIs_down, dnVt_down, dR, dC}, the sum of squared errors
+    of THIS batch and d(mean over n_global)/dtheta6 -- and nothing synchronises.  tp: a TpPlan (plan_asym_time_parallel;
+    k_bwd is ignored: the step has no reverse chunks) or None for one chunk.  mode: binding.ASYM_NEWTON_F32 (default) or
+    binding.ASYM_NEWTON_F64; the closed form (a model approximation) has no one-pass step."""
+
+    def __init__(self, B, T, fs, tp, device, mode=None, n_global=None, tol=1.0e-12, max_iter=50):
+        self.mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
+        if self.mode not in (binding.ASYM_NEWTON_F32, binding.ASYM_NEWTON_F64):
+            raise binding.WdfHipError(f"AsymMseStep: mode {self.mode} has no one-pass step (the Newton modes have)")
+        self.B, self.T, self.fs, self.tp = int(B), int(T), float(fs), tp
+        self.tol, self.max_iter = float(tol), int(max_iter)
+        self.n_global = float(n_global if n_global is not None else self.B * self.T)
+        self.gscale = 2.0 / self.n_global
+        k, self.warmup, self.verify_tol = (tp.k_fwd, tp.warmup, tp.tol) if tp is not None else (1, 0, 1.0e-6)
+        self.k = binding.asym_chunks(self.T, k)
+        self.ws = torch.empty((binding.lib().wdf_clipper_asym_step_mse_ws_bytes(self.B, self.k),), dtype=torch.uint8, device=device)
+        self.status = torch.zeros((4,), dtype=torch.int32, device=device)
+        self.out = torch.zeros((7,), dtype=torch.float32, device=device)      # {sse, gtheta6}
+        self.sse, self.gtheta = self.out[0:1], self.out[1:7]
+        self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=device)
+        self.zT = None
+
+    def step_fused(self, theta6, x, target, adam=None, z0=None, want_zT=False):
+        """adam: a binding.Adam(6, ...) to update theta6 in the step's own last launch; otherwise the caller applies its
+        optimizer to self.gtheta.  z0 [B]: the state the call starts from, a constant of it; want_zT: self.zT <- the state
+        it ends in.  Fills self.y, self.out, self.status."""
+        _, self.zT, _, _ = binding.clipper_asym_step_mse(
+            x, theta6, self.fs, self.mode, target, self.gscale, self.k, self.warmup, tol=self.tol, max_iter=self.max_iter,
+            verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws, status=self.status, out7=self.out, opt=adam)
+        return self.sse, self.gtheta
+
+
+class _ClipperAsymMseFn(torch.autograd.Function):
+    """mean((clipper_asym(theta6, x) - target)^2) as the one-pass step (AsymMseStep.step_fused; one stepper per shape, buffers
+    reused); backward only scales the stored gradient.  keep: -> (loss, y [T,B], zT [B]), the call's own output and final
+    state, detached; otherwise the loss alone (y stays in the stepper's buffer: no copy)."""
+    _steppers = {}
+
+    @staticmethod
+    def forward(ctx, theta6, x, target, fs, tp, mode, z0, keep):
+        B, T = x.shape
+        key = (B, T, float(fs), tp, mode, x.device)
+        st = _ClipperAsymMseFn._steppers.get(key)
+        if st is None:
+            if len(_ClipperAsymMseFn._steppers) > 8:
+                _ClipperAsymMseFn._steppers.clear()
+            st = _ClipperAsymMseFn._steppers[key] = AsymMseStep(B, T, fs, tp, x.device, mode=mode)
+        LAST_TP_STATUS["status"] = st.status
+        st.step_fused(theta6.detach().contiguous(), x, target, z0=z0, want_zT=keep)
+        out = st.out.clone()
+        ctx.save_for_backward(out)
+        if not keep:
+            return out[0] / float(B * T)
+        y, zT = st.y.clone(), st.zT        # (the stepper's y is overwritten by the next call of this shape)
+        ctx.mark_non_differentiable(y, zT)
+        return out[0] / float(B * T), y, zT
+
+    @staticmethod
+    def backward(ctx, gl, *_):
+        (out,) = ctx.saved_tensors
+        return gl * out[1:7], None, None, None, None, None, None, None
+
+
+def clipper_asym_mse(theta6, x, target, fs, tp=None, mode=None, z0=None, return_state=False):
+    """Scalar mean-squared error of the two-different-diode clipper's output against target [T,B], differentiable w.r.t.
+    theta6 = {Is_up, nVt_up, Is_down, nVt_down, R, C} (float32[6] on the device), as ONE pass over the data
+    (wdf_clipper_asym_step_mse): no stash, no torch loss temporaries, no reverse sweep.  mode: binding.ASYM_NEWTON_F32
+    (default) or binding.ASYM_NEWTON_F64.  tp: a TpPlan (plan_asym_time_parallel) or None for one chunk.
+    z0 [B]: the state the loop starts from, a constant of the call.
+    -> loss, or (loss, y [T,B], zT [B]) with return_state: the call's output and final state, detached."""
+    mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
+    if z0 is not None:
+        z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        if z0.numel() != x.shape[0]:
+            raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state))
 
 
 class MseStep:

@@ -870,8 +870,9 @@ class Circuit:
     def mse(self, x, target, z0=None, carry_state=False):
         """tf.reduce_mean(tf.square(self(x) - target)) as ONE fused evaluation where the kernels allow
         it (diode-pair clipper: forward kernel + MSE-fused reverse sweep, the gradient of every
-        trainable component ready when tape.gradient asks); any other circuit takes the plain path.
-        target: [T,B] like the output.
+        trainable component ready when tape.gradient asks; the clipper under an AsymDiodePair root with a Newton solver: the
+        one-pass step of csrc/wdf_asym_step.h, forward, loss and six gradients in one sweep); any other circuit takes the
+        plain path.  target: [T,B] like the output.
 
         z0 [ns,B]: the capacitor states the call starts from (default: zero, clipper_pot.py:110-111).  carry_state=True: the
         call starts from the states the PREVIOUS carry_state call on this circuit ended in (zero the first time) -- lpf.py:30-49
@@ -909,6 +910,8 @@ class Circuit:
             if stateful:
                 self.last_state = ent["zT"].clone()              # (ent["zT"] is one of two ping-pong buffers: [ns,B], kept by value)
             return loss
+        if self.root_kind == "AsymDiodePair" and self.root.mode != binding.ASYM_OMEGA_F32:
+            return self._mse_clipper_asym(x, target, z0, stateful)      # the Newton solvers: the one-pass step
         if stateful:
             y, zT = self(x, z0=z0, return_state=True)
             self.last_state, self.last_output = zT.detach(), y.detach()
@@ -1237,6 +1240,37 @@ class Circuit:
         y, zT = engine.clipper_asym(theta6, xv, float(cap.FS), tp=tp, mode=dp.mode, z0=z0t, return_state=True)
         y = y.as_subclass(tf.Tensor)
         return (y, zT.reshape(1, -1)) if return_state else y
+
+    def _mse_clipper_asym(self, x, target, z0, stateful):
+        """mse() on the clipper tree under an AsymDiodePair root with a Newton solver: forward, loss and the six gradients in
+        one pass over the data (engine.clipper_asym_mse) -- no stash, no torch loss, no reverse sweep.  State in and out as
+        the composed path handles it: z0 is a constant of the call, last_state / last_output are set on stateful calls."""
+        from . import engine
+        anchor = x if isinstance(x, torch.Tensor) else None
+        x = torch.as_tensor(x).as_subclass(torch.Tensor)
+        x = (x if x.is_cuda else x.cuda()).float()
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        if x.dim() != 3 or x.shape[2] != 1:
+            raise binding.WdfHipError(f"x must be [B,T,1] (or [B,T] for one channel), got {tuple(x.shape)}")
+        dp, vs, cap = self.root, self.top.P1, self.top.P2
+        Rv = vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R))
+        parts = [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, Rv, cap.C]
+        theta6 = self._theta(parts, x.device)
+        xv, _ = engine.split_channels(x, False, anchor=anchor)
+        B, T = xv.shape
+        tgt = torch.as_tensor(target).as_subclass(torch.Tensor).to(x.device).float().reshape(T, B).contiguous()
+        tp = self.time_parallel
+        if tp == "auto":
+            tp = engine.plan_asym_time_parallel(B, T, float(parts[4]), float(parts[5]), float(cap.FS))
+        elif not isinstance(tp, engine.TpPlan):
+            tp = None
+        z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor)
+        if not stateful:
+            return engine.clipper_asym_mse(theta6, xv, tgt, float(cap.FS), tp=tp, mode=dp.mode).as_subclass(tf.Tensor)
+        loss, y, zT = engine.clipper_asym_mse(theta6, xv, tgt, float(cap.FS), tp=tp, mode=dp.mode, z0=z0t, return_state=True)
+        self.last_state, self.last_output = zT.reshape(1, -1), y.as_subclass(tf.Tensor)
+        return loss.as_subclass(tf.Tensor)
 
     def _run_clipper(self, x, z0, return_state):
         from . import engine

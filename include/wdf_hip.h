@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -599,6 +599,24 @@ int wdf_clipper_asym_bwd_tp(const float* x, const float* theta6, float fs, int m
                             int n_chunks, void* stream);
 int wdf_asym_root(const float* a, const float* theta6, float fs, int mode, double tol, int max_iter,
                   double* b, int64_t n, void* stream);
+
+/* The MSE training step of this clipper in ONE pass over the data (csrc/wdf_asym_step.h), both NEWTON modes: forward, loss and
+ * gradient with x [B][T] and target [T][B] read once and y [T][B] written once -- no state stash, no dL/dy array, one root solve
+ * per sample.  The gradient is carried forward in time as the state's tangent to the six parameters; the n_chunks time chunks
+ * (a count that tiles T in 8-step units) start `warmup` steps early from z = 0 and are verified like wdf_clipper_asym_fwd_tp's
+ * (same verify_tol, same status words); each records how its sums depend on the tangent entering it, so one walk per sequence
+ * composes them exactly, and the waves where a boundary missed are re-run as one chunk before that walk.
+ * out7 (device float[7]) = {sum (y - target)^2 of this call, d(gscale/2 x that sum)/d{Is_up, nVt_up, Is_down, nVt_down, R, C}}
+ * (gscale = 2/N for the mean over N samples).  m != NULL: Adam with clip bounds on theta6 in the same last launch
+ * (wdf_adam_step's rule, n = 6; v, step, lr then required, lo / hi optional).  z0 (optional [B]) is a constant of the call,
+ * zT (optional [B]) receives the final state and must not alias z0.  WDF_ASYM_OMEGA_F32 is rejected (WDF_EINVAL): the
+ * closed form keeps wdf_clipper_asym_fwd_tp + wdf_clipper_asym_bwd_tp.  ws: wdf_clipper_asym_step_mse_ws_bytes bytes, 8-byte
+ * aligned, no initialisation needed. */
+size_t wdf_clipper_asym_step_mse_ws_bytes(int64_t B, int n_chunks);
+int wdf_clipper_asym_step_mse(const float* x, float* theta6, float fs, int mode, double tol, int max_iter, const float* target,
+                              float gscale, float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                              float verify_tol, void* ws, void* status, float* out7, float* m, float* v, int32_t* step,
+                              const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream);
 
 /* Element-wise diode-pair root and Wright omega on device arrays (n elements): the
  * building blocks above, exposed for parity tests against diode_pretraining.py:39-60 /
