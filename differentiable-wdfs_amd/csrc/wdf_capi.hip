@@ -1,8 +1,8 @@
-// wdf_capi.hip -- the C ABI of libwdf_hip.so (include/wdf_hip.h), part 1 of 4: library state,
-// element-wise building blocks, loss sums, optimizer, events.  gfx950 only.
+// wdf_capi.hip -- the C ABI of libwdf_hip.so (include/wdf_hip.h): library state, element-wise building blocks, loss sums,
+// optimizer, events.  gfx950 only.
 //
 // Argument checking, template dispatch and launches; no algorithm lives here.
-// (clipper kernels: wdf_capi_clipper.hip; state-space and asym root: wdf_capi_ss.hip; MLP root: wdf_capi_mlp.hip)
+// (the kernel families: wdf_capi_clipper.hip, _asym, _ss, _ss_step, _ss_dyn, _mlp, _mlp_step; what they share: wdf_capi_common.h)
 #include "wdf_capi_common.h"
 #include "wdf_elementwise.h"
 #include "wdf_optim.h"

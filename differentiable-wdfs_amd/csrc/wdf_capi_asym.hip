@@ -1,0 +1,235 @@
+// wdf_capi_asym.hip -- C ABI of the two-different-diode (asymmetric) clipper (csrc/wdf_asym.h, csrc/wdf_asym_step.h): sequential and
+// time-parallel forward / reverse sweep, the stand-alone root, the one-pass MSE step.  Argument checking, workspace layouts,
+// template dispatch and launches.
+#include "wdf_capi_common.h"
+#include "wdf_asym.h"
+#include "wdf_asym_step.h"
+using namespace wdfcapi;
+
+namespace {
+
+static_assert(WDF_ASYM_OMEGA_F32 == wdf::kAsymOmega && WDF_ASYM_NEWTON_F64 == wdf::kAsymNewton64 && WDF_ASYM_NEWTON_F32 == wdf::kAsymNewton32,
+              "the header's mode numbers are the kernels'");
+using AsymModes = Values<int, wdf::kAsymOmega, wdf::kAsymNewton64, wdf::kAsymNewton32>;
+constexpr int kUnit = 8;                     // chunk lengths and warm-ups are multiples of 8 steps
+
+int asym_check(int64_t B, int64_t T, float fs, int mode)
+{
+    if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
+    if (mode < WDF_ASYM_OMEGA_F32 || mode > WDF_ASYM_NEWTON_F32) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    return WDF_OK;
+}
+
+int newton_check(double tol, int max_iter) { return (!(tol > 0.0) || max_iter < 1) ? fail(WDF_EINVAL, "tol > 0, max_iter >= 1") : WDF_OK; }
+
+// the sequential forward; with a gate: only the waves the verification flagged, the others leave at once
+bool launch_asym_fwd(int mode, bool v4, const float* x, const float* theta6, float fs, float* y, float* zstash, const float* z0, float* zT,
+                     double tol, int max_iter, long long* iters, int64_t B, int64_t T, const unsigned* gate, hipStream_t s)
+{
+    return dispatch([&](auto m, auto v) {
+        hipLaunchKernelGGL((wdf::clipper_asym_fwd_kernel<m(), v()>), dim3(waves64(B)), dim3(64), 0, s, x, theta6, fs, y, zstash, z0, zT, tol,
+                           max_iter, iters, B, T, gate);
+    }, AsymModes{mode}, Bools{v4});
+}
+
+struct AsymFwdWs { float* zwarm; float* zend; unsigned* gate; size_t bytes; };
+AsymFwdWs asym_fwd_ws(void* ws, int64_t B, int K)
+{
+    Carver c(ws);
+    AsymFwdWs w;
+    w.zwarm = c.take<float>((size_t)K * (size_t)B);
+    w.zend = c.take<float>((size_t)K * (size_t)B);
+    w.gate = c.take<unsigned>(waves64(B));
+    w.bytes = c.off;
+    return w;
+}
+
+struct AsymBwdWs { double* rec; double* part; size_t bytes; };
+AsymBwdWs asym_bwd_ws(void* ws, int64_t B, int K)
+{
+    Carver c(ws);
+    AsymBwdWs w;
+    w.rec = c.take<double>((size_t)K * (size_t)wdf::kAsymRec * (size_t)B);
+    w.part = c.take<double>(waves64(B) * 8);
+    w.bytes = c.off;
+    return w;
+}
+
+// [records double K x 15 x B][per-wave partials double waves x 8][zwarm, zend float K x B each][gate unsigned waves][ticket]
+struct AsymStepWs { double* rec; double* part; float* zwarm; float* zend; unsigned* gate; unsigned* ticket; size_t bytes; };
+AsymStepWs asym_step_ws(void* ws, int64_t B, int K)
+{
+    Carver c(ws);
+    AsymStepWs w;
+    w.rec = c.take<double>((size_t)K * (size_t)wdf::kAsymStepRec * (size_t)B);
+    w.part = c.take<double>(waves64(B) * 8);
+    w.zwarm = c.take<float>((size_t)K * (size_t)B);
+    w.zend = c.take<float>((size_t)K * (size_t)B);
+    w.gate = c.take<unsigned>(waves64(B));
+    w.ticket = c.take<unsigned>(2);
+    w.bytes = c.off;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wdf_clipper_asym_fwd(const float* x, const float* theta6, float fs, int mode, double tol, int max_iter, float* y,
+                         float* zstash, const float* z0, float* zT, long long* iters, int64_t B, int64_t T, void* stream)
+{
+    if (!x || !theta6 || !y) return fail(WDF_EINVAL, "null x/theta6/y");
+    int rc = asym_check(B, T, fs, mode);
+    if (rc) return rc;
+    if (mode != WDF_ASYM_OMEGA_F32 && (rc = newton_check(tol, max_iter))) return rc;
+    const bool v4 = (T % 4 == 0) && aligned16(x);
+    if (!launch_asym_fwd(mode, v4, x, theta6, fs, y, zstash, z0, zT, tol, max_iter, iters, B, T, nullptr, (hipStream_t)stream))
+        return no_kernel("wdf_clipper_asym_fwd");
+    return check_launch("wdf_clipper_asym_fwd");
+}
+
+size_t wdf_clipper_asym_fwd_tp_ws_bytes(int64_t B, int n_chunks)
+{
+    return (B > 0 && n_chunks > 0) ? asym_fwd_ws(nullptr, B, n_chunks).bytes : 0;
+}
+
+int wdf_clipper_asym_fwd_tp(const float* x, const float* theta6, float fs, int mode, double tol, int max_iter, float* y,
+                            float* zstash, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                            float verify_tol, void* ws, void* status, void* stream)
+{
+    if (!x || !theta6 || !y || !ws || !status) return fail(WDF_EINVAL, "null x/theta6/y/ws/status");
+    int rc = asym_check(B, T, fs, mode);
+    if (rc) return rc;
+    if (mode != WDF_ASYM_OMEGA_F32 && (rc = newton_check(tol, max_iter))) return rc;
+    if (n_chunks < 1 || warmup < 0 || !(verify_tol >= 0.0f)) return fail(WDF_EINVAL, "n_chunks >= 1, warmup >= 0, verify_tol >= 0");
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
+    const int64_t W = round_up((int64_t)warmup, kUnit);
+    const AsymFwdWs w = asym_fwd_ws(ws, B, g.K);
+    const dim3 grid(waves64(B), (unsigned)g.K);
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = (T % 4 == 0) && aligned16(x);
+    bool ok = dispatch([&](auto m) {
+        hipLaunchKernelGGL((wdf::clipper_asym_fwd_tp_kernel<m()>), grid, dim3(64), 0, s, x, theta6, fs, y, zstash, z0, zT, w.zwarm, w.zend,
+                           tol, max_iter, (wdf::AsymTpStatus*)status, B, T, g.L, W);
+    }, AsymModes{mode});
+    if (ok && g.K > 1) {
+        hipLaunchKernelGGL(wdf::asym_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, w.zwarm, w.zend, B, (int64_t)g.K, verify_tol, w.gate,
+                           (wdf::AsymTpStatus*)status);
+        ok = launch_asym_fwd(mode, v4, x, theta6, fs, y, zstash, z0, zT, tol, max_iter, nullptr, B, T, w.gate, s);
+    }
+    return ok ? check_launch("wdf_clipper_asym_fwd_tp") : no_kernel("wdf_clipper_asym_fwd_tp");
+}
+
+size_t wdf_clipper_asym_bwd_ws_bytes(int64_t B) { return B > 0 ? waves64(B) * 8 * sizeof(double) : 0; }
+
+int wdf_clipper_asym_bwd(const float* x, const float* theta6, float fs, double tol, int max_iter, const float* zstash,
+                         const float* gy, void* ws, float* gtheta6, int64_t B, int64_t T, void* stream)
+{
+    if (!x || !theta6 || !zstash || !gy || !ws || !gtheta6) return fail(WDF_EINVAL, "null x/theta6/zstash/gy/ws/gtheta6");
+    if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
+    if (int rc = newton_check(tol, max_iter)) return rc;
+    const unsigned grid = (unsigned)waves64(B);
+    hipLaunchKernelGGL(wdf::clipper_asym_bwd_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, x, theta6, fs, zstash, gy, tol,
+                       max_iter, (double*)ws, B, T);
+    hipLaunchKernelGGL(wdf::clipper_asym_grad_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+                       (int)grid, theta6, fs, gtheta6);
+    return check_launch("wdf_clipper_asym_bwd");
+}
+
+size_t wdf_clipper_asym_bwd_tp_ws_bytes(int64_t B, int n_chunks)
+{
+    return (B > 0 && n_chunks > 0) ? asym_bwd_ws(nullptr, B, n_chunks).bytes : 0;
+}
+
+int wdf_clipper_asym_bwd_tp(const float* x, const float* theta6, float fs, int mode, const float* zstash, const float* zT,
+                            const float* gy, const float* gzT, void* ws, float* gtheta6, float* gz0, int64_t B, int64_t T,
+                            int n_chunks, void* stream)
+{
+    if (!x || !theta6 || !zstash || !zT || !gy || !ws || !gtheta6) return fail(WDF_EINVAL, "null x/theta6/zstash/zT/gy/ws/gtheta6");
+    int rc = asym_check(B, T, fs, mode);
+    if (rc) return rc;
+    if (n_chunks < 1) return fail(WDF_EINVAL, "n_chunks >= 1");
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
+    const AsymBwdWs w = asym_bwd_ws(ws, B, g.K);
+    const dim3 grid(waves64(B), (unsigned)g.K);
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = (T % 4 == 0) && aligned16(x);
+    // both Newton modes: the exact pair, differentiated at the root the forward stored (nothing is re-solved)
+    dispatch([&](auto newton, auto v) {
+        hipLaunchKernelGGL((wdf::clipper_asym_bwd_tp_kernel<newton(), v()>), grid, dim3(64), 0, s, x, theta6, fs, zstash, zT, gy, w.rec, B, T, g.L);
+    }, Bools{mode != WDF_ASYM_OMEGA_F32}, Bools{v4});
+    hipLaunchKernelGGL(wdf::clipper_asym_bwd_combine_kernel, dim3(grid.x), dim3(64), 0, s, (const double*)w.rec, gzT, w.part, gz0, B, (int64_t)g.K);
+    hipLaunchKernelGGL(wdf::clipper_asym_grad_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)w.part, (int)grid.x, theta6, fs, gtheta6);
+    return check_launch("wdf_clipper_asym_bwd_tp");
+}
+
+int wdf_asym_root(const float* a, const float* theta6, float fs, int mode, double tol, int max_iter, double* b, int64_t n,
+                  void* stream)
+{
+    if (!a || !theta6 || !b || n <= 0) return fail(WDF_EINVAL, "wdf_asym_root: bad arguments");
+    if (mode < WDF_ASYM_OMEGA_F32 || mode > WDF_ASYM_NEWTON_F32) return fail(WDF_EINVAL, "unknown mode %d", mode);
+    if (mode == WDF_ASYM_NEWTON_F32) if (int rc = newton_check(tol, max_iter)) return rc;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    const bool ok = dispatch([&](auto m) {
+        hipLaunchKernelGGL((wdf::asym_root_kernel<m()>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, theta6, fs, b, tol, max_iter, n);
+    }, AsymModes{mode});
+    return ok ? check_launch("wdf_asym_root") : no_kernel("wdf_asym_root");
+}
+
+// ---- the one-pass MSE step (wdf_asym_step.h) ------------------------------------------------------------------------------
+size_t wdf_clipper_asym_step_mse_ws_bytes(int64_t B, int n_chunks)
+{
+    return (B > 0 && n_chunks > 0) ? asym_step_ws(nullptr, B, n_chunks).bytes : 0;
+}
+
+int wdf_clipper_asym_step_mse(const float* x, float* theta6, float fs, int mode, double tol, int max_iter, const float* target,
+                              float gscale, float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                              float verify_tol, void* ws, void* status, float* out7, float* m, float* v, int32_t* step,
+                              const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream)
+{
+    if (!x || !theta6 || !target || !y || !ws || !status || !out7) return fail(WDF_EINVAL, "null x/theta6/target/y/ws/status/out7");
+    int rc = asym_check(B, T, fs, mode);
+    if (rc) return rc;
+    if (mode == WDF_ASYM_OMEGA_F32)
+        return fail(WDF_EINVAL, "mode 0 (the closed form) has no one-pass step: use wdf_clipper_asym_fwd_tp + wdf_clipper_asym_bwd_tp");
+    if ((rc = newton_check(tol, max_iter))) return rc;
+    if (n_chunks < 1 || n_chunks > 65535 || warmup < 0 || !(verify_tol >= 0.0f))
+        return fail(WDF_EINVAL, "n_chunks in 1..65535, warmup >= 0, verify_tol >= 0");
+    if (!aligned8(ws)) return fail(WDF_EINVAL, "ws must be 8-byte aligned");
+    if (z0 && z0 == zT) return fail(WDF_EINVAL, "zT must not alias z0 (every chunk that starts at t = 0 reads z0)");
+    if ((rc = adam_check(m, v, step, lr))) return rc;
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
+    const int64_t W = round_up((int64_t)warmup, kUnit);
+    const int64_t Lall = round_up(T, kUnit);                    // one chunk: the repair launch
+    const AsymStepWs w = asym_step_ws(ws, B, g.K);
+    const dim3 grid(waves64(B), (unsigned)g.K);
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = (T % 4 == 0) && aligned16(x);
+    const wdf::AsymStepAdam adam{m, v, step, lr, lo, hi, beta1, beta2, eps};
+    const auto launch = [&](dim3 gr, const unsigned* gate, int64_t L) {
+        return dispatch([&](auto md, auto vv) {
+            hipLaunchKernelGGL((wdf::clipper_asym_step_kernel<md(), vv()>), gr, dim3(64), 0, s, x, (const float*)theta6, fs, target, y, z0, zT,
+                               w.zwarm, w.zend, w.rec, tol, max_iter, (wdf::AsymTpStatus*)status, w.ticket, gate, B, T, L, W);
+        }, Values<int, wdf::kAsymNewton64, wdf::kAsymNewton32>{mode}, Bools{v4});
+    };
+    bool ok;
+    {
+        EventBracket bracket(s);
+        ok = launch(grid, nullptr, g.L);
+    }
+    if (ok && g.K > 1) {
+        // every boundary checked on the device; the waves where one missed run again, exactly, as one chunk
+        hipLaunchKernelGGL(wdf::asym_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, w.zwarm, w.zend, B, (int64_t)g.K, verify_tol, w.gate,
+                           (wdf::AsymTpStatus*)status);
+        ok = launch(dim3(grid.x), w.gate, Lall);
+    }
+    if (!ok) return no_kernel("wdf_clipper_asym_step_mse");
+    hipLaunchKernelGGL(wdf::clipper_asym_step_finish_kernel, dim3(grid.x), dim3(64), 0, s, (const double*)w.rec,
+                       (const unsigned*)(g.K > 1 ? w.gate : nullptr), w.part, w.ticket, theta6, fs, gscale, out7, adam, B, (int64_t)g.K);
+    return check_launch("wdf_clipper_asym_step_mse");
+}
+
+}  // extern "C"

@@ -1,6 +1,5 @@
-// wdf_capi_mlp.hip -- C ABI part 4 of 4: the tanh-MLP root (layers.py DenseRootModel) kernels.
-// Argument checking, template dispatch and launches.
-// 
+// wdf_capi_mlp.hip -- C ABI of the tanh-MLP root (layers.py DenseRootModel) kernels (csrc/wdf_mlp*.h): sequential and time-parallel
+// forward, the weight-gradient passes, evaluation and pre-training.  Argument checking, template dispatch and launches.
 #include "wdf_capi_common.h"
 #include "wdf_mlp.h"
 #include "wdf_mlp_row.h"
@@ -8,32 +7,36 @@
 #include "wdf_mlp_mfma.h"
 using namespace wdfcapi;
 
-extern "C" {
+namespace {
 
 // the architectures the MLP kernels are instantiated for (every one among the reference's model files)
-static bool mlp_arch_ok(int hidden, int n_tanh_layers)
+constexpr bool mlp_arch_ok(int hidden, int n_tanh_layers)
 {
     return ((hidden == 4 || hidden == 8 || hidden == 16) && n_tanh_layers == 3) ||
            ((hidden == 4 || hidden == 8) && (n_tanh_layers == 4 || n_tanh_layers == 5));
 }
+
+using MlpDepths = Values<int, 3, 4, 5>;
+constexpr int kMlpUnit = 16;                 // chunk lengths and warm-ups: multiples of 16 steps
+
+// f(H, NL, more...) for one of those architectures: no kernel is built for a width and depth mlp_arch_ok() leaves out
+template <class F, class... More> bool dispatch_arch(F&& f, int hidden, int n_tanh_layers, More... more)
+{
+    return dispatch([&](auto H, auto NL, auto... m) {
+        if constexpr (!mlp_arch_ok(H(), NL())) return false;
+        else return dispatch([&] { return f(H, NL, m...); });
+    }, Values<int, 4, 8, 16>{hidden}, MlpDepths{n_tanh_layers}, more...);
+}
+
+}  // namespace
+
+extern "C" {
 
 int wdf_mlp_weight_count(int hidden, int n_tanh_layers)
 {
     if (hidden < 1 || n_tanh_layers < 1) return 0;
     return 2 * hidden + hidden + (n_tanh_layers - 1) * (hidden * hidden + hidden) + hidden + 1;
 }
-
-#define WDF_MLP_CASE(H_, NL_, DYN_, KERNEL, ...)                                                              \
-    if (hidden == H_ && n_tanh_layers == NL_ && dyn == DYN_)                                                  \
-        hipLaunchKernelGGL((wdf::KERNEL<H_, NL_, DYN_>), dim3(grid), dim3(64), 0, (hipStream_t)stream, __VA_ARGS__);
-#define WDF_MLP_DISPATCH(KERNEL, ...)                                                                         \
-    WDF_MLP_CASE(4, 3, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(4, 3, true, KERNEL, __VA_ARGS__)              \
-    WDF_MLP_CASE(8, 3, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(8, 3, true, KERNEL, __VA_ARGS__)              \
-    WDF_MLP_CASE(16, 3, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(16, 3, true, KERNEL, __VA_ARGS__)            \
-    WDF_MLP_CASE(4, 5, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(4, 5, true, KERNEL, __VA_ARGS__)              \
-    WDF_MLP_CASE(8, 5, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(8, 5, true, KERNEL, __VA_ARGS__)              \
-    WDF_MLP_CASE(4, 4, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(4, 4, true, KERNEL, __VA_ARGS__)              \
-    WDF_MLP_CASE(8, 4, false, KERNEL, __VA_ARGS__) WDF_MLP_CASE(8, 4, true, KERNEL, __VA_ARGS__)
 
 static int mlp_check(const float* x, const float* theta2, const float* w, int hidden, int n_tanh_layers, float fs,
                      int64_t B, int64_t T, int flags)
@@ -90,38 +93,30 @@ int wdf_clipper_mlp_fwd(const float* x, const float* r, const float* theta2, con
     int rc = mlp_check(x, theta2, w, hidden, n_tanh_layers, fs, B, T, flags);
     if (rc) return rc;
     if (!y) return fail(WDF_EINVAL, "null y");
-    const unsigned grid = (unsigned)((B + 63) / 64);
+    const unsigned grid = (unsigned)waves64(B);
     const bool dyn = r != nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    bool ok;
     if (flags & WDF_MLP_LANE_PER_SEQUENCE) {
-        WDF_MLP_DISPATCH(clipper_mlp_fwd_kernel, x, r, theta2, w, fs, y, zstash, z0, zT, B, T)
+        ok = dispatch_arch([&](auto H, auto NL, auto DYN) {
+            hipLaunchKernelGGL((wdf::clipper_mlp_fwd_kernel<H(), NL(), DYN()>), dim3(grid), dim3(64), 0, s, x, r, theta2, w, fs, y, zstash, z0, zT,
+                               B, T);
+        }, hidden, n_tanh_layers, Bools{dyn});
     } else if (mlp_fwd_on_matrix_cores(B)) {      // 16 sequences per wave, one chunk (wdf_mlp_mfma.h)
         const dim3 gm((unsigned)((B + 15) / 16), 1u);
-        const int64_t Lp = (T + 15) / 16 * 16;
-#define WDF_MFMA_FWD(NL_)                                                                                      \
-    if (n_tanh_layers == NL_) {                                                                                \
-        if (dyn) hipLaunchKernelGGL((wdf::clipper_mlp_mfma_fwd_tp_kernel<NL_, true, false>), gm, dim3(64), 0,     \
-                                    (hipStream_t)stream, x, r, theta2, w, hidden, fs, y, zstash, z0, zT, (float*)nullptr, \
-                                    (float*)nullptr, (const int*)nullptr, (wdf::MlpTpStatus*)nullptr, B, T, Lp,     \
-                                    (int64_t)0, Lp, (float*)nullptr, (const float*)nullptr, (const unsigned*)nullptr);                   \
-        else hipLaunchKernelGGL((wdf::clipper_mlp_mfma_fwd_tp_kernel<NL_, false, false>), gm, dim3(64), 0,        \
-                                (hipStream_t)stream, x, r, theta2, w, hidden, fs, y, zstash, z0, zT, (float*)nullptr, \
-                                (float*)nullptr, (const int*)nullptr, (wdf::MlpTpStatus*)nullptr, B, T, Lp,         \
-                                (int64_t)0, Lp, (float*)nullptr, (const float*)nullptr, (const unsigned*)nullptr);                       \
-    }
-        WDF_MFMA_FWD(3) WDF_MFMA_FWD(4) WDF_MFMA_FWD(5)
-#undef WDF_MFMA_FWD
+        const int64_t Lp = round_up(T, kMlpUnit);
+        ok = dispatch([&](auto NL, auto DYN) {
+            hipLaunchKernelGGL((wdf::clipper_mlp_mfma_fwd_tp_kernel<NL(), DYN(), false>), gm, dim3(64), 0, s, x, r, theta2, w, hidden, fs, y,
+                               zstash, z0, zT, (float*)nullptr, (float*)nullptr, (const int*)nullptr, (wdf::MlpTpStatus*)nullptr, B, T, Lp,
+                               (int64_t)0, Lp, (float*)nullptr, (const float*)nullptr, (const unsigned*)nullptr);
+        }, MlpDepths{n_tanh_layers}, Bools{dyn});
     } else {                                      // one 16-lane row per sequence (wdf_mlp_row.h)
-        const unsigned grow = (unsigned)((B + 3) / 4);
-#define WDF_ROW_FWD(NL_)                                                                                       \
-    if (n_tanh_layers == NL_) {                                                                                \
-        if (dyn) hipLaunchKernelGGL((wdf::clipper_mlp_row_fwd_kernel<NL_, true>), dim3(grow), dim3(64), 0,        \
-                                    (hipStream_t)stream, x, r, theta2, w, hidden, fs, y, zstash, z0, zT, B, T, (const unsigned*)nullptr);   \
-        else hipLaunchKernelGGL((wdf::clipper_mlp_row_fwd_kernel<NL_, false>), dim3(grow), dim3(64), 0,           \
-                                (hipStream_t)stream, x, r, theta2, w, hidden, fs, y, zstash, z0, zT, B, T, (const unsigned*)nullptr);       \
+        ok = dispatch([&](auto NL, auto DYN) {
+            hipLaunchKernelGGL((wdf::clipper_mlp_row_fwd_kernel<NL(), DYN()>), dim3((unsigned)((B + 3) / 4)), dim3(64), 0, s, x, r, theta2, w,
+                               hidden, fs, y, zstash, z0, zT, B, T, (const unsigned*)nullptr);
+        }, MlpDepths{n_tanh_layers}, Bools{dyn});
     }
-        WDF_ROW_FWD(3) WDF_ROW_FWD(4) WDF_ROW_FWD(5)
-#undef WDF_ROW_FWD
-    }
+    if (!ok) return no_kernel("wdf_clipper_mlp_fwd");
     return check_launch("wdf_clipper_mlp_fwd");
 }
 
@@ -144,15 +139,11 @@ int wdf_clipper_mlp_bwd_w(const float* x, const float* r, const float* theta2, c
     const bool dyn = r != nullptr;
     double* wsd = (double*)ws;
     float* wsw = (float*)((char*)ws + (size_t)grid * 4 * sizeof(double));
-#define WDF_ROW_BWD_W(NL_)                                                                                     \
-    if (n_tanh_layers == NL_) {                                                                                \
-        if (dyn) hipLaunchKernelGGL((wdf::clipper_mlp_row_bwd_w_kernel<NL_, true>), dim3(grid), dim3(64), 0,      \
-                                    (hipStream_t)stream, x, r, theta2, w, hidden, fs, zstash, gy, wsw, wsd, B, T);  \
-        else hipLaunchKernelGGL((wdf::clipper_mlp_row_bwd_w_kernel<NL_, false>), dim3(grid), dim3(64), 0,         \
-                                (hipStream_t)stream, x, r, theta2, w, hidden, fs, zstash, gy, wsw, wsd, B, T);    \
-    }
-    WDF_ROW_BWD_W(3) WDF_ROW_BWD_W(4) WDF_ROW_BWD_W(5)
-#undef WDF_ROW_BWD_W
+    if (!dispatch([&](auto NL, auto DYN) {
+            hipLaunchKernelGGL((wdf::clipper_mlp_row_bwd_w_kernel<NL(), DYN()>), dim3(grid), dim3(64), 0, (hipStream_t)stream, x, r, theta2, w,
+                               hidden, fs, zstash, gy, wsw, wsd, B, T);
+        }, MlpDepths{n_tanh_layers}, Bools{dyn}))
+        return no_kernel("wdf_clipper_mlp_bwd_w");
     rc = check_launch("wdf_clipper_mlp_bwd_w");
     if (rc) return rc;
     hipLaunchKernelGGL(wdf::clipper_mlp_grad_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
@@ -164,21 +155,14 @@ int wdf_clipper_mlp_bwd_w(const float* x, const float* r, const float* theta2, c
 }
 
 // ---- time-parallel MLP-root kernels (wdf_mlp_tp.h) ------------------------------------------------
-struct MlpTpGeom { int64_t L; int K; };
-static MlpTpGeom mlp_tp_geom(int64_t T, int n_chunks)
-{
-    if (n_chunks < 1) n_chunks = 1;
-    int64_t L = (T + n_chunks - 1) / n_chunks;
-    L = (L + 15) / 16 * 16;
-    return {L, (int)((T + L - 1) / L)};
-}
+static ChunkGeom mlp_tp_geom(int64_t T, int n_chunks) { return chunk_geom(T, n_chunks, kMlpUnit); }
 
 // Chunk 0 needs no warm-up: left equal, its waves finish after L steps while every other wave runs L + W.  Balance
 // them by COST: a warm-up step costs rho owned steps (rho = 1 for the plain forward; 0.7 when the owned steps also
 // evaluate the input Jacobian for kappa -- tools/mlp_chunk_probe.py: 0.76 / 1.02 us on the matrix cores, 0.49 / 0.72 us
 // on the row kernel), so L0 = L + rho W with L0 + (K-1) L = T: every wave then takes about as long as chunk 0's
 // (one warm-up value for the batch only; with per-wave warm-ups the chunks stay equal).  -> L0; g.L = the others' length.
-static int64_t mlp_tp_balance(int64_t T, int64_t W, bool one_warmup, bool with_kappa, MlpTpGeom& g)
+static int64_t mlp_tp_balance(int64_t T, int64_t W, bool one_warmup, bool with_kappa, ChunkGeom& g)
 {
     int64_t L0 = g.L;
     if (g.K >= 3 && one_warmup && W > 0) {
@@ -199,8 +183,8 @@ static int64_t mlp_tp_balance(int64_t T, int64_t W, bool one_warmup, bool with_k
 int wdf_clipper_mlp_tp_starts(int64_t T, int n_chunks, int warmup, int64_t* starts)
 {   // (the geometry of wdf_clipper_mlp_fwd_tp_kappa: the only entry point that takes zinit)
     if (T <= 0 || n_chunks < 1 || warmup < 0 || !starts) return fail(WDF_EINVAL, "T > 0, n_chunks >= 1, warmup >= 0, starts");
-    MlpTpGeom g = mlp_tp_geom(T, n_chunks);
-    const int64_t W = ((int64_t)warmup + 15) / 16 * 16;
+    ChunkGeom g = mlp_tp_geom(T, n_chunks);
+    const int64_t W = round_up((int64_t)warmup, kMlpUnit);
     const int64_t L0 = mlp_tp_balance(T, W, true, true, g);
     for (int k = 0; k < g.K; ++k) {
         const int64_t t0 = k == 0 ? 0 : L0 + (int64_t)(k - 1) * g.L;
@@ -230,9 +214,9 @@ static int mlp_fwd_tp_common(const float* x, const float* r, const float* theta2
     if (!y || !ws || !status) return fail(WDF_EINVAL, "null y/ws/status");
     if (want_kappa && (!kappa || !zstash)) return fail(WDF_EINVAL, "null kappa/zstash");
     if (n_chunks < 1 || warmup < 0 || !(tol >= 0.0f)) return fail(WDF_EINVAL, "n_chunks >= 1, warmup >= 0, tol >= 0");
-    MlpTpGeom g = mlp_tp_geom(T, n_chunks);
-    const MlpTpGeom gu = g;                                    // equal chunks: the gated kappa pass's grid
-    const int64_t W = ((int64_t)warmup + 15) / 16 * 16;
+    ChunkGeom g = mlp_tp_geom(T, n_chunks);
+    const ChunkGeom gu = g;                                    // equal chunks: the gated kappa pass's grid
+    const int64_t W = round_up((int64_t)warmup, kMlpUnit);
     const int64_t L0 = mlp_tp_balance(T, W, warmup_per_wave == nullptr, want_kappa, g);
     float* zwarm = (float*)ws;
     float* zend = zwarm + (size_t)g.K * (size_t)B;
@@ -275,7 +259,7 @@ static int mlp_fwd_tp_common(const float* x, const float* r, const float* theta2
             }                                                                                                    \
         }                                                                                                        \
         if (g.K > 1) {                                                                                           \
-            hipLaunchKernelGGL(wdf::mlp_tp_verify_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, zwarm, zend, B, \
+            hipLaunchKernelGGL(wdf::mlp_tp_verify_kernel, dim3((unsigned)waves64(B)), dim3(64), 0, s, zwarm, zend, B, \
                                (int64_t)g.K, tol, gate, (wdf::MlpTpStatus*)status, (const unsigned*)nullptr);     \
             if (want_kappa) {                                                                                    \
                 if (dyn) { WDF_ROW_FWD_TP_REPAIR(NL_, true, true); }                                             \
@@ -284,7 +268,7 @@ static int mlp_fwd_tp_common(const float* x, const float* r, const float* theta2
                 if (dyn) { WDF_ROW_FWD_TP_REPAIR(NL_, true, false); }                                            \
                 else { WDF_ROW_FWD_TP_REPAIR(NL_, false, false); }                                               \
             }                                                                                                    \
-            hipLaunchKernelGGL(wdf::mlp_tp_verify_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s,            \
+            hipLaunchKernelGGL(wdf::mlp_tp_verify_kernel, dim3((unsigned)waves64(B)), dim3(64), 0, s,            \
                                (const float*)zwarm2, (const float*)zend2, B, (int64_t)g.K, tol, gate2,           \
                                (wdf::MlpTpStatus*)status, (const unsigned*)gate);                                \
             if (dyn) hipLaunchKernelGGL((wdf::clipper_mlp_row_fwd_kernel<NL_, true>), dim3(grid_row), dim3(64), 0, s, x, r, \
@@ -350,7 +334,7 @@ static int mlp_bwd_w_tp_common(const float* x, const float* r, const float* thet
     if (!zstash || !gy || !ws || !gtheta2 || !gw) return fail(WDF_EINVAL, "null zstash/gy/ws/gtheta2/gw");
     if (have_kappa && !kappa_in) return fail(WDF_EINVAL, "null kappa");
     if (n_chunks < 1) return fail(WDF_EINVAL, "n_chunks >= 1");
-    const MlpTpGeom g = mlp_tp_geom(T, n_chunks);
+    const ChunkGeom g = mlp_tp_geom(T, n_chunks);
     const dim3 grid((unsigned)((B + 3) / 4), (unsigned)g.K);
     const int nparts = (int)(grid.x * grid.y);
     double* wsd = (double*)ws;                                             // [nparts][4] doubles (8-byte aligned)
@@ -359,12 +343,12 @@ static int mlp_bwd_w_tp_common(const float* x, const float* r, const float* thet
     const int count_w = wdf_mlp_weight_count(hidden, n_tanh_layers);
     const unsigned scan_chunks = (unsigned)((T + wdf::kScanChunk - 1) / wdf::kScanChunk);
     float2* smap = (float2*)(((uintptr_t)(wsw + (size_t)nparts * (size_t)count_w) + 7) & ~(uintptr_t)7);   // [scan_chunks][B]
-    const dim3 sgrid((unsigned)((B + 63) / 64), scan_chunks);
+    const dim3 sgrid((unsigned)waves64(B), scan_chunks);
     // (C) on the matrix cores (wdf_mlp_mfma.h, 16 sequences per wave) when that fills at least half the chip, two waves
     // per SIMD -- bench.py --root mlp2x16 / 2x8 / 4x8: step 0.655 -> 0.578, 0.663 -> 0.596, 1.170 -> 0.978 ms.
     // WDF_MLP_WGRAD_MFMA = a chunk count forces it, 0 switches it off.
     int wm_chunks = wdf_clipper_mlp_wgrad_matrix_core_chunks(B, T);
-    const MlpTpGeom gm = mlp_tp_geom(T, wm_chunks > 0 ? wm_chunks : 1);
+    const ChunkGeom gm = mlp_tp_geom(T, wm_chunks > 0 ? wm_chunks : 1);
     const dim3 wmgrid((unsigned)((B + 15) / 16), (unsigned)gm.K);
     if (wm_chunks > 0 && (int64_t)wmgrid.x * wmgrid.y > (int64_t)nparts) wm_chunks = 0;     // (the partial buffers are sized for the row grid)
     const int rparts = wm_chunks > 0 ? (int)(wmgrid.x * wmgrid.y) : nparts;
@@ -384,7 +368,7 @@ static int mlp_bwd_w_tp_common(const float* x, const float* r, const float* thet
             hipLaunchKernelGGL(wdf::mlp_adjoint_scan_chunked_kernel, sgrid, dim3(64), 0, s,                      \
                                have_kappa ? kappa_in : (const float*)kap, gy, (const float2*)smap, kap, B, T);   \
         } else {                                                                                                 \
-            hipLaunchKernelGGL(wdf::mlp_adjoint_scan_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s,         \
+            hipLaunchKernelGGL(wdf::mlp_adjoint_scan_kernel, dim3((unsigned)waves64(B)), dim3(64), 0, s,         \
                                have_kappa ? kappa_in : (const float*)kap, gy, kap, B, T);                        \
         }                                                                                                        \
         {                                                                                                        \
@@ -440,24 +424,22 @@ int wdf_clipper_mlp_bwd(const float* x, const float* r, const float* theta2, con
     if (rc) return rc;
     if (!zstash || !gy || !gb || !ain || !ws || !gtheta2) return fail(WDF_EINVAL, "null zstash/gy/gb/ain/ws/gtheta2");
     if (r && !lrin) return fail(WDF_EINVAL, "per-sample resistance needs lrin");
-    unsigned grid = (unsigned)((B + 63) / 64);
+    unsigned grid = (unsigned)waves64(B);
     const bool dyn = r != nullptr;
+    bool ok;
     if (flags & WDF_MLP_LANE_PER_SEQUENCE) {
-        WDF_MLP_DISPATCH(clipper_mlp_bwd_kernel, x, r, theta2, w, fs, zstash, gy, gb, ain, lrin, (double*)ws, B, T)
+        ok = dispatch_arch([&](auto H, auto NL, auto DYN) {
+            hipLaunchKernelGGL((wdf::clipper_mlp_bwd_kernel<H(), NL(), DYN()>), dim3(grid), dim3(64), 0, (hipStream_t)stream, x, r, theta2, w, fs,
+                               zstash, gy, gb, ain, lrin, (double*)ws, B, T);
+        }, hidden, n_tanh_layers, Bools{dyn});
     } else {                                      // one 16-lane row per sequence (wdf_mlp_row.h)
         grid = (unsigned)((B + 3) / 4);
-#define WDF_ROW_BWD(NL_)                                                                                       \
-    if (n_tanh_layers == NL_) {                                                                                \
-        if (dyn) hipLaunchKernelGGL((wdf::clipper_mlp_row_bwd_kernel<NL_, true>), dim3(grid), dim3(64), 0,        \
-                                    (hipStream_t)stream, x, r, theta2, w, hidden, fs, zstash, gy, gb, ain, lrin,  \
-                                    (double*)ws, B, T);                                                        \
-        else hipLaunchKernelGGL((wdf::clipper_mlp_row_bwd_kernel<NL_, false>), dim3(grid), dim3(64), 0,           \
-                                (hipStream_t)stream, x, r, theta2, w, hidden, fs, zstash, gy, gb, ain, lrin,      \
-                                (double*)ws, B, T);                                                            \
+        ok = dispatch([&](auto NL, auto DYN) {
+            hipLaunchKernelGGL((wdf::clipper_mlp_row_bwd_kernel<NL(), DYN()>), dim3(grid), dim3(64), 0, (hipStream_t)stream, x, r, theta2, w,
+                               hidden, fs, zstash, gy, gb, ain, lrin, (double*)ws, B, T);
+        }, MlpDepths{n_tanh_layers}, Bools{dyn});
     }
-        WDF_ROW_BWD(3) WDF_ROW_BWD(4) WDF_ROW_BWD(5)
-#undef WDF_ROW_BWD
-    }
+    if (!ok) return no_kernel("wdf_clipper_mlp_bwd");
     rc = check_launch("wdf_clipper_mlp_bwd");
     if (rc) return rc;
     hipLaunchKernelGGL(wdf::clipper_mlp_grad_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
@@ -473,11 +455,6 @@ static unsigned mlp_wgrad_blocks(int64_t S)
 
 // (wdf_clipper_mlp_wgrad: wdf_capi_mlp_step.hip, next to the matrix-core accumulators it shares with the resident step)
 
-#define WDF_EVAL_CASE(H_, NL_)                                                                                \
-    if (hidden == H_ && n_tanh_layers == NL_)                                                                 \
-        hipLaunchKernelGGL((wdf::mlp_eval_kernel<H_, NL_>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, ain, lrin, w, \
-                           out, S);
-
 int wdf_mlp_eval(const float* ain, const float* lrin, const float* w, int hidden, int n_tanh_layers, float* out,
                  int64_t S, void* stream)
 {
@@ -486,16 +463,11 @@ int wdf_mlp_eval(const float* ain, const float* lrin, const float* w, int hidden
     if (!mlp_arch_ok(hidden, n_tanh_layers))
         return fail(WDF_EUNSUPPORTED, "MLP root: unsupported network (width %d, %d tanh layers)", hidden, n_tanh_layers);
     const unsigned nblk = mlp_wgrad_blocks(S);
-    WDF_EVAL_CASE(4, 3) WDF_EVAL_CASE(8, 3) WDF_EVAL_CASE(16, 3) WDF_EVAL_CASE(4, 4) WDF_EVAL_CASE(8, 4)
-    WDF_EVAL_CASE(4, 5) WDF_EVAL_CASE(8, 5)
-    return check_launch("wdf_mlp_eval");
+    const bool ok = dispatch_arch([&](auto H, auto NL) {
+        hipLaunchKernelGGL((wdf::mlp_eval_kernel<H(), NL()>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, ain, lrin, w, out, S);
+    }, hidden, n_tanh_layers);
+    return ok ? check_launch("wdf_mlp_eval") : no_kernel("wdf_mlp_eval");
 }
-
-#define WDF_FIT_CASE(H_, NL_)                                                                                 \
-    if (hidden == H_ && n_tanh_layers == NL_)                                                                 \
-        hipLaunchKernelGGL((wdf::mlp_fit_epoch_kernel<H_, NL_>), dim3(1), dim3(64 * wdf::Mlp<H_, NL_>::kParts), 0,   \
-                           (hipStream_t)stream, xa, xl, ys, S, batch, w, m, v, step, lr, beta1, beta2, eps, esr_n,   \
-                           eps_energy, loss_sum);
 
 int wdf_mlp_fit_epoch(const float* xa, const float* xl, const float* ys, int64_t S, int batch, float* w, float* m,
                       float* v, int32_t* step, float lr, float beta1, float beta2, float eps, float esr_n,
@@ -507,9 +479,11 @@ int wdf_mlp_fit_epoch(const float* xa, const float* xl, const float* ys, int64_t
     if (!(esr_n > 0.0f)) return fail(WDF_EINVAL, "esr_n must be positive");
     if (!mlp_arch_ok(hidden, n_tanh_layers))
         return fail(WDF_EUNSUPPORTED, "MLP root: unsupported network (width %d, %d tanh layers)", hidden, n_tanh_layers);
-    WDF_FIT_CASE(4, 3) WDF_FIT_CASE(8, 3) WDF_FIT_CASE(16, 3) WDF_FIT_CASE(4, 4) WDF_FIT_CASE(8, 4)
-    WDF_FIT_CASE(4, 5) WDF_FIT_CASE(8, 5)
-    return check_launch("wdf_mlp_fit_epoch");
+    const bool ok = dispatch_arch([&](auto H, auto NL) {
+        hipLaunchKernelGGL((wdf::mlp_fit_epoch_kernel<H(), NL()>), dim3(1), dim3(64 * wdf::Mlp<H(), NL()>::kParts), 0, (hipStream_t)stream, xa, xl,
+                           ys, S, batch, w, m, v, step, lr, beta1, beta2, eps, esr_n, eps_energy, loss_sum);
+    }, hidden, n_tanh_layers);
+    return ok ? check_launch("wdf_mlp_fit_epoch") : no_kernel("wdf_mlp_fit_epoch");
 }
 
 }  // extern "C"

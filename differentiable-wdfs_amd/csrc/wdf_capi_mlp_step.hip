@@ -1,4 +1,4 @@
-// wdf_capi_mlp_step.hip -- C ABI part 5 of 6: the resident training step of the MLP-root pot clipper
+// wdf_capi_mlp_step.hip -- C ABI of the resident training step of the MLP-root pot clipper
 // (csrc/wdf_mlp_step.h): state layout, plan upload, template dispatch and the five launches of a step.
 #include <cstdlib>
 #include <vector>
@@ -16,8 +16,6 @@ struct StepLayout {
     int64_t lw;
 };
 
-size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 bool step_arch_ok(int hidden, int n_layers, int activation)
 {
     return (hidden == 4 || hidden == 8 || hidden == 16) && n_layers >= 3 && n_layers <= 5 && (activation == 0 || activation == 1);
@@ -29,13 +27,12 @@ StepLayout step_layout(int hidden, int n_layers, int64_t B, int64_t T, int n_ite
 {
     StepLayout L{};
     L.n_cols = (int)((B + 15) / 16);
-    int64_t lw = (T + wgrad_chunks - 1) / wgrad_chunks;
-    lw = (lw + 15) / 16 * 16;
-    L.lw = lw;
-    L.kw = (int)((T + lw - 1) / lw);
+    const ChunkGeom gw = chunk_geom(T, wgrad_chunks, 16);
+    L.lw = gw.L;
+    L.kw = gw.K;
     const size_t nc = (size_t)L.n_cols, ni = (size_t)n_items, nb = (size_t)(T / 16);
     size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = up(o + bytes, 256); return at; };
+    auto take = [&o](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 256); return at; };
     L.ctl = take(sizeof(wdf::MlpStepCtl));
     L.items = take(ni * sizeof(wdf::MlpStepItem));
     L.cols = take(nc * sizeof(wdf::MlpStepCol));
@@ -237,7 +234,7 @@ int wdf_clipper_mlp_step(const float* x, const float* p, const float* lr, const 
     if ((phase & WDF_MLP_STEP_SUMS) && !sums) return fail(WDF_EINVAL, "WDF_MLP_STEP_SUMS needs sums");
     if ((phase & WDF_MLP_STEP_GLOBAL_SUMS) && !sums) return fail(WDF_EINVAL, "WDF_MLP_STEP_GLOBAL_SUMS needs sums");
     if ((phase & WDF_MLP_STEP_BWD) && !gw) return fail(WDF_EINVAL, "WDF_MLP_STEP_BWD needs gw");
-    if (adam_m && (!adam_v || !adam_step || !adam_lr)) return fail(WDF_EINVAL, "Adam needs m, v, step, lr");
+    if ((rc = adam_check(adam_m, adam_v, adam_step, adam_lr))) return rc;
     const StepLayout L = step_layout(hidden, n_layers, B, T, n_items, wgrad_chunks);
     char* base = (char*)state;
     wdf::MlpStepArgs A{};
@@ -315,12 +312,11 @@ int wdf_clipper_mlp_wgrad(const float* ain, const float* lrin, const float* gb, 
     const int count = step_weight_count(hidden, n_tanh_layers);
     const int64_t per_wave = list_per_wave(S), nwg = list_workgroups(S);
     hipStream_t s = (hipStream_t)stream;
-#define WDF_LIST_CASE(NL_)                                                                                                     \
-    if (n_tanh_layers == NL_)                                                                                                  \
-        hipLaunchKernelGGL((wdf::mlp_wgrad_list_kernel<NL_>), dim3((unsigned)nwg), dim3(256), 0, s, ain, lrin, gb, theta2, fs, w, hidden, S,  \
-                           per_wave, (float*)ws);
-    WDF_LIST_CASE(3) WDF_LIST_CASE(4) WDF_LIST_CASE(5)
-#undef WDF_LIST_CASE
+    if (!dispatch([&](auto NL) {
+            hipLaunchKernelGGL((wdf::mlp_wgrad_list_kernel<NL()>), dim3((unsigned)nwg), dim3(256), 0, s, ain, lrin, gb, theta2, fs, w, hidden, S,
+                               per_wave, (float*)ws);
+        }, Values<int, 3, 4, 5>{n_tanh_layers}))
+        return no_kernel("wdf_clipper_mlp_wgrad");
     int rc = check_launch("wdf_clipper_mlp_wgrad");
     if (rc) return rc;
     hipLaunchKernelGGL(wdf::mlp_wgrad_reduce_wide_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64, 16), 0, s, (const float*)ws, (int)nwg,

@@ -1,4 +1,4 @@
-// wdf_capi_ss_dyn.hip -- C ABI part 7 of 7: the state-space recursion with per-sample coefficient rows and the MLP root on
+// wdf_capi_ss_dyn.hip -- C ABI of the state-space recursion with per-sample coefficient rows and the MLP root on
 // any small tree (csrc/wdf_ss_dyn.h): argument checking, template dispatch, launches.
 #include "wdf_capi_common.h"
 #include "wdf_ss_dyn.h"
@@ -34,61 +34,57 @@ int dyn_check(const char* who, const float* x, const float* crow, int ns, int ni
 
 }  // namespace
 
+namespace {
+
+constexpr int kUnit = 8;                     // chunk lengths: multiples of 8 steps
+
+// The instantiation a call's root selects: only a diode pair can be asymmetric and only a network has a depth, so the other
+// roots take SYM = true and NL = 3 and no kernel is built for the combinations dyn_built() leaves out.
+struct DynKind { int root; bool sym; int nl; };
+DynKind dyn_kind(int root, int n_up, int n_down, int n_tanh_layers)
+{
+    return {root, root != WDF_ROOT_DIODE_PAIR || n_up == n_down, root == WDF_ROOT_MLP && n_tanh_layers != 3 ? 5 : 3};
+}
+constexpr bool dyn_built(int root, bool sym, int nl) { return (root == wdf::kDynRootDiode || sym) && (root == wdf::kDynRootMlp || nl == 3); }
+using DynRoots = Values<int, wdf::kDynRootNone, wdf::kDynRootDiode, wdf::kDynRootMlp>;
+using DynDepths = Values<int, 3, 5>;
+using DynSlots = Values<int, 4, 8>;          // state slots the kernel is compiled for (4: trees of up to four capacitors; 8: five to eight)
+
+// grid.x: one lane per sequence, or -- the network root, evaluated in 16-lane rows (wdf_ss_dyn.h DynLanes) -- four sequences per wave
+unsigned dyn_grid_x(bool rows, int64_t B) { return (unsigned)(rows ? (B + 3) / 4 : waves64(B)); }
+
+template <class... A> bool launch_dyn_fwd(DynKind k, int ns, int64_t B, int gy, hipStream_t s, A... args)
+{
+    const dim3 grid(dyn_grid_x(k.root == WDF_ROOT_MLP, B), (unsigned)gy);
+    return dispatch([&](auto ROOT, auto SYM, auto NL, auto MS) {
+        if constexpr (!dyn_built(ROOT(), SYM(), NL())) return false;
+        else {
+            hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<ROOT(), SYM(), 16, NL(), MS()>), grid, dim3(64), 0, s, args...);
+            return true;
+        }
+    }, DynRoots{k.root}, Bools{k.sym}, DynDepths{k.nl}, DynSlots{ns > 4 ? 8 : 4});
+}
+
+// the reverse sweep's kernel in one of its modes (0: sequential, 1: chunk maps + root partials, 2: the emitting pass -- no root
+// code in it, so one instantiation per root kind and a lane per sequence)
+template <int MODE, class... A> bool launch_dyn_bwd(DynKind k, int ns, int64_t B, int gy, hipStream_t s, A... args)
+{
+    if (MODE == 2) k = DynKind{k.root, true, 3};
+    const dim3 grid(dyn_grid_x(MODE != 2 && k.root == WDF_ROOT_MLP, B), (unsigned)gy);
+    return dispatch([&](auto ROOT, auto SYM, auto NL, auto MS) {
+        if constexpr (!dyn_built(ROOT(), SYM(), NL()) || (MODE == 2 && (!SYM() || NL() != 3))) return false;
+        else {
+            hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<ROOT(), SYM(), 16, NL(), MODE, MS()>), grid, dim3(64), 0, s, args...);
+            return true;
+        }
+    }, DynRoots{k.root}, Bools{k.sym}, DynDepths{k.nl}, DynSlots{ns > 4 ? 8 : 4});
+}
+
+}  // namespace
+
 extern "C" {
 
 int wdf_ss_dyn_row_len(int ns, int ni) { return dyn_ok(ns, ni) ? wdf::DynLayout(ns, ni).n : 0; }
-
-// grid.x: one lane per sequence, or -- the network root, evaluated in 16-lane rows (wdf_ss_dyn.h DynLanes) -- four sequences per wave
-#define WDF_DYN_GRIDX(ROW_) ((unsigned)((ROW_) ? (B + 3) / 4 : (B + 63) / 64))
-
-// MS_: state slots the kernel is compiled for (4: trees of up to four capacitors; 8: five to eight)
-#define WDF_DYN_FWD_MS(MS_, GY_, ...)                                                                                         \
-    do {                                                                                                                     \
-        const dim3 grid(WDF_DYN_GRIDX(root == WDF_ROOT_MLP), (unsigned)(GY_));                                               \
-        if (root == WDF_ROOT_NONE) hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<wdf::kDynRootNone, true, 16, 3, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden); \
-        else if (root == WDF_ROOT_DIODE_PAIR && n_up == n_down)                                                              \
-            hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<wdf::kDynRootDiode, true, 16, 3, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden);   \
-        else if (root == WDF_ROOT_DIODE_PAIR)                                                                                \
-            hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<wdf::kDynRootDiode, false, 16, 3, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden);  \
-        else if (n_tanh_layers == 3) hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<wdf::kDynRootMlp, true, 16, 3, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden); \
-        else hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<wdf::kDynRootMlp, true, 16, 5, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden);     \
-    } while (0)
-#define WDF_DYN_FWD(GY_, ...) do { if (ns > 4) WDF_DYN_FWD_MS(8, GY_, __VA_ARGS__); else WDF_DYN_FWD_MS(4, GY_, __VA_ARGS__); } while (0)
-
-// the reverse sweep's kernel in one of its modes (0: sequential, 1: chunk maps + root partials; 2 -- no root code in it -- below)
-#define WDF_DYN_BWD_MS(MS_, MODE_, GY_, ...)                                                                                  \
-    do {                                                                                                                     \
-        const dim3 grid(WDF_DYN_GRIDX(root == WDF_ROOT_MLP), (unsigned)(GY_));                                               \
-        if (root == WDF_ROOT_NONE) hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootNone, true, 16, 3, MODE_, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc); \
-        else if (root == WDF_ROOT_DIODE_PAIR && n_up == n_down)                                                              \
-            hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootDiode, true, 16, 3, MODE_, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc);   \
-        else if (root == WDF_ROOT_DIODE_PAIR)                                                                                \
-            hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootDiode, false, 16, 3, MODE_, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc);  \
-        else if (n_tanh_layers == 3) hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootMlp, true, 16, 3, MODE_, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc); \
-        else hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootMlp, true, 16, 5, MODE_, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc);     \
-    } while (0)
-#define WDF_DYN_BWD(MODE_, GY_, ...) do { if (ns > 4) WDF_DYN_BWD_MS(8, MODE_, GY_, __VA_ARGS__); else WDF_DYN_BWD_MS(4, MODE_, GY_, __VA_ARGS__); } while (0)
-
-#define WDF_DYN_BWD_EMIT_MS(MS_, GY_, ...)                                                                                    \
-    do {                                                                                                                     \
-        const dim3 grid(WDF_DYN_GRIDX(false), (unsigned)(GY_));                                                              \
-        if (root == WDF_ROOT_NONE) hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootNone, true, 16, 3, 2, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc); \
-        else if (root == WDF_ROOT_DIODE_PAIR) hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootDiode, true, 16, 3, 2, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc); \
-        else hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<wdf::kDynRootMlp, true, 16, 3, 2, MS_>), grid, dim3(64), 0, s, __VA_ARGS__, hidden, acc);          \
-    } while (0)
-#define WDF_DYN_BWD_EMIT(GY_, ...) do { if (ns > 4) WDF_DYN_BWD_EMIT_MS(8, GY_, __VA_ARGS__); else WDF_DYN_BWD_EMIT_MS(4, GY_, __VA_ARGS__); } while (0)
-
-namespace {
-// chunk length (a multiple of 8) and count for n_chunks requested; false when the count does not tile T that way
-bool dyn_geom(int64_t T, int n_chunks, int64_t& L, int& K)
-{
-    if (n_chunks < 1) return false;
-    L = (T + n_chunks - 1) / n_chunks;
-    L = (L + 7) / 8 * 8;
-    K = (int)((T + L - 1) / L);
-    return K == n_chunks;
-}
-}  // namespace
 
 int wdf_ss_dyn_fwd(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
                    int hidden, int n_tanh_layers, int n_up, int n_down, float* y, float* zstash, const float* z0, float* zT,
@@ -101,15 +97,16 @@ int wdf_ss_dyn_fwd(const float* x, const float* rows, int per_sample, int ns, in
     const int64_t cs = per_sample ? B : 1, ts = per_sample == 1 ? n * B : 0, bs = per_sample ? 1 : 0;   // (2: rows [n][B], the same row at every step)
     hipStream_t s = (hipStream_t)stream;
     EventBracket bracket(s);
-    WDF_DYN_FWD(1, x, rows, cs, ts, bs, rootp, w, n_up, n_down, y, zstash, z0, zT, ns, ni, B, T, T, (int64_t)0,
-                (float*)nullptr, (float*)nullptr, (const unsigned*)nullptr, (const float*)nullptr);
+    if (!launch_dyn_fwd(dyn_kind(root, n_up, n_down, n_tanh_layers), ns, B, 1, s, x, rows, cs, ts, bs, rootp, w, n_up, n_down, y, zstash, z0, zT,
+                        ns, ni, B, T, T, (int64_t)0, (float*)nullptr, (float*)nullptr, (const unsigned*)nullptr, (const float*)nullptr, hidden))
+        return no_kernel("wdf_ss_dyn_fwd");
     return check_launch("wdf_ss_dyn_fwd");
 }
 
 size_t wdf_ss_dyn_fwd_tp_ws_bytes(int ns, int64_t B, int n_chunks)
 {
     if (ns < 0 || B <= 0 || n_chunks <= 0) return 0;
-    return (size_t)2 * (size_t)n_chunks * (size_t)(ns > 0 ? ns : 1) * (size_t)B * sizeof(float) + (size_t)((B + 63) / 64) * sizeof(unsigned);
+    return (size_t)2 * (size_t)n_chunks * (size_t)(ns > 0 ? ns : 1) * (size_t)B * sizeof(float) + waves64(B) * sizeof(unsigned);
 }
 
 int wdf_ss_dyn_fwd_tp(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
@@ -121,32 +118,36 @@ int wdf_ss_dyn_fwd_tp(const float* x, const float* rows, int per_sample, int ns,
     if (!y || !ws || !status) return fail(WDF_EINVAL, "wdf_ss_dyn_fwd_tp: null y / ws / status");
     if (ns < 1) return fail(WDF_EINVAL, "wdf_ss_dyn_fwd_tp: a tree without states has no chunks to verify: use wdf_ss_dyn_fwd");
     if (warmup < 0 || !(tol >= 0.0f)) return fail(WDF_EINVAL, "wdf_ss_dyn_fwd_tp: warmup >= 0, tol >= 0");
-    int64_t Lc;
-    int K;
-    if (!dyn_geom(T, n_chunks, Lc, K)) return fail(WDF_EINVAL, "wdf_ss_dyn_fwd_tp: n_chunks = %d does not tile T = %lld in 8-step units (%d does)", n_chunks, (long long)T, K);
+    if (n_chunks < 1) return fail(WDF_EINVAL, "wdf_ss_dyn_fwd_tp: n_chunks >= 1");
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
+    const int K = g.K;
+    const int64_t Lc = g.L;
     const int64_t n = wdf::DynLayout(ns, ni).n;
     const int64_t cs = per_sample ? B : 1, ts = per_sample == 1 ? n * B : 0, bs = per_sample ? 1 : 0;   // (2: rows [n][B], the same row at every step)
     float* zwarm = (float*)ws;
     float* zend = zwarm + (size_t)K * (size_t)ns * (size_t)B;
     unsigned* gate = (unsigned*)(zend + (size_t)K * (size_t)ns * (size_t)B);
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(status, 0, sizeof(wdf::SsTpStatus), s) != hipSuccess) return fail(WDF_ELAUNCH, "wdf_ss_dyn_fwd_tp: memset failed");
+    if ((rc = memset_async(status, 0, sizeof(wdf::SsTpStatus), s))) return rc;
+    const DynKind kind = dyn_kind(root, n_up, n_down, n_tanh_layers);
+    bool ok;
     {
         EventBracket bracket(s);
-        WDF_DYN_FWD(K, x, rows, cs, ts, bs, rootp, w, n_up, n_down, y, zstash, z0, zT, ns, ni, B, T, Lc,
-                    (int64_t)warmup, zwarm, zend, (const unsigned*)nullptr, zinit);
+        ok = launch_dyn_fwd(kind, ns, B, K, s, x, rows, cs, ts, bs, rootp, w, n_up, n_down, y, zstash, z0, zT, ns, ni, B, T, Lc,
+                            (int64_t)warmup, zwarm, zend, (const unsigned*)nullptr, zinit, hidden);
     }
-    if (K > 1) {
-        hipLaunchKernelGGL(wdf::ss_tp_verify_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const float*)zwarm, (const float*)zend, ns,
+    if (ok && K > 1) {
+        hipLaunchKernelGGL(wdf::ss_tp_verify_kernel, dim3(waves64(B)), dim3(64), 0, s, (const float*)zwarm, (const float*)zend, ns,
                            B, (int64_t)K, tol, gate, (wdf::SsTpStatus*)status);
         // the 64-sequence groups with a miss again, sequentially (the gate lets the others leave at once)
-        WDF_DYN_FWD(1, x, rows, cs, ts, bs, rootp, w, n_up, n_down, y, zstash, z0, zT, ns, ni, B, T, T, (int64_t)0,
-                    (float*)nullptr, (float*)nullptr, (const unsigned*)gate, (const float*)nullptr);
+        ok = launch_dyn_fwd(kind, ns, B, 1, s, x, rows, cs, ts, bs, rootp, w, n_up, n_down, y, zstash, z0, zT, ns, ni, B, T, T, (int64_t)0,
+                            (float*)nullptr, (float*)nullptr, (const unsigned*)gate, (const float*)nullptr, hidden);
     }
-    return check_launch("wdf_ss_dyn_fwd_tp");
+    return ok ? check_launch("wdf_ss_dyn_fwd_tp") : no_kernel("wdf_ss_dyn_fwd_tp");
 }
 
-size_t wdf_ss_dyn_bwd_ws_bytes(int64_t B) { return B > 0 ? (size_t)((B + 63) / 64) * 2 * sizeof(double) : 0; }
+size_t wdf_ss_dyn_bwd_ws_bytes(int64_t B) { return B > 0 ? waves64(B) * 2 * sizeof(double) : 0; }
 
 int wdf_ss_dyn_bwd(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
                    int hidden, int n_tanh_layers, int n_up, int n_down, const float* zstash, const float* gy, float* grows,
@@ -161,8 +162,9 @@ int wdf_ss_dyn_bwd(const float* x, const float* rows, int per_sample, int ns, in
     hipStream_t s = (hipStream_t)stream;
     const int acc = per_sample != 1;       // rows that do not change in time: dL/d(row) summed over the steps -> grows [1][n][B]
     EventBracket bracket(s);
-    WDF_DYN_BWD(0, 1, x, rows, cs, ts, bs, rootp, w, n_up, n_down, zstash, gy, grows, (double*)ws, gb, ain, lrin, gz0, ns, ni, B, T, T,
-                (float*)nullptr, (float*)nullptr, (const float*)nullptr);
+    if (!launch_dyn_bwd<0>(dyn_kind(root, n_up, n_down, n_tanh_layers), ns, B, 1, s, x, rows, cs, ts, bs, rootp, w, n_up, n_down, zstash, gy, grows,
+                           (double*)ws, gb, ain, lrin, gz0, ns, ni, B, T, T, (float*)nullptr, (float*)nullptr, (const float*)nullptr, hidden, acc))
+        return no_kernel("wdf_ss_dyn_bwd");
     return check_launch("wdf_ss_dyn_bwd");
 }
 
@@ -170,7 +172,7 @@ int wdf_ss_dyn_bwd(const float* x, const float* rows, int per_sample, int ns, in
 size_t wdf_ss_dyn_bwd_tp_ws_bytes(int ns, int64_t B, int64_t T, int n_chunks)
 {
     if (ns < 0 || B <= 0 || T <= 0 || n_chunks <= 0) return 0;
-    const size_t nsa = ns > 0 ? ns : 1, waves = (size_t)((B + 63) / 64);
+    const size_t nsa = ns > 0 ? ns : 1, waves = waves64(B);
     return (size_t)n_chunks * waves * 2 * sizeof(double) +
            ((size_t)n_chunks * (nsa + 1) * nsa + (size_t)n_chunks * nsa + (size_t)T * wdf::kDynRpart) * (size_t)B * sizeof(float);
 }
@@ -184,26 +186,32 @@ int wdf_ss_dyn_bwd_tp(const float* x, const float* rows, int per_sample, int ns,
     if (!gy || !grows || !ws || !zstash) return fail(WDF_EINVAL, "wdf_ss_dyn_bwd_tp: null gy / grows / ws / zstash");
     if (ns < 1) return fail(WDF_EINVAL, "wdf_ss_dyn_bwd_tp: a tree without states has no adjoint to chunk: use wdf_ss_dyn_bwd");
     if (root == WDF_ROOT_MLP && (!gb || !ain || !lrin)) return fail(WDF_EINVAL, "wdf_ss_dyn_bwd_tp: the MLP root needs gb / ain / lrin [T][B]");
-    int64_t Lc;
-    int K;
-    if (!dyn_geom(T, n_chunks, Lc, K)) return fail(WDF_EINVAL, "wdf_ss_dyn_bwd_tp: n_chunks = %d does not tile T = %lld in 8-step units (%d does)", n_chunks, (long long)T, K);
+    if (n_chunks < 1) return fail(WDF_EINVAL, "wdf_ss_dyn_bwd_tp: n_chunks >= 1");
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
+    const int K = g.K;
+    const int64_t Lc = g.L;
     const int64_t n = wdf::DynLayout(ns, ni).n;
     const int64_t cs = per_sample ? B : 1, ts = per_sample == 1 ? n * B : 0, bs = per_sample ? 1 : 0;   // (2: rows [n][B], the same row at every step)
-    const size_t waves = (size_t)((B + 63) / 64);
+    const size_t waves = waves64(B);
     double* part = (double*)ws;
     float* rec = (float*)(part + (size_t)K * waves * 2);
     float* lam_in = rec + (size_t)K * (size_t)(ns + 1) * (size_t)ns * (size_t)B;
     float* rpart = lam_in + (size_t)K * (size_t)ns * (size_t)B;
     hipStream_t s = (hipStream_t)stream;
     const int acc = per_sample != 1;       // (grows [K][n][B] then: one partial per chunk, added up by the caller)
+    const DynKind kind = dyn_kind(root, n_up, n_down, n_tanh_layers);
+    bool ok;
     {
         EventBracket bracket(s);
-        WDF_DYN_BWD(1, K, x, rows, cs, ts, bs, rootp, w, n_up, n_down, zstash, gy, grows, part, gb, ain, lrin, gz0, ns, ni, B, T, Lc, rpart, rec,
-                    (const float*)nullptr);
+        ok = launch_dyn_bwd<1>(kind, ns, B, K, s, x, rows, cs, ts, bs, rootp, w, n_up, n_down, zstash, gy, grows, part, gb, ain, lrin, gz0, ns, ni,
+                               B, T, Lc, rpart, rec, (const float*)nullptr, hidden, acc);
     }
+    if (!ok) return no_kernel("wdf_ss_dyn_bwd_tp");
     hipLaunchKernelGGL(wdf::ss_dyn_bwd_combine_kernel, dim3((unsigned)waves), dim3(64), 0, s, (const float*)rec, lam_in, ns, B, (int64_t)K);
-    WDF_DYN_BWD_EMIT(K, x, rows, cs, ts, bs, rootp, w, n_up, n_down, zstash, gy, grows, part, gb, ain, lrin, gz0, ns, ni, B, T, Lc, rpart, rec,
-                     (const float*)lam_in);
+    if (!launch_dyn_bwd<2>(kind, ns, B, K, s, x, rows, cs, ts, bs, rootp, w, n_up, n_down, zstash, gy, grows, part, gb, ain, lrin, gz0, ns, ni, B, T,
+                           Lc, rpart, rec, (const float*)lam_in, hidden, acc))
+        return no_kernel("wdf_ss_dyn_bwd_tp");
     return check_launch("wdf_ss_dyn_bwd_tp");
 }
 
@@ -272,7 +280,7 @@ int wdf_ss_dyn_rows(const int32_t* tape_ops, int n_ops, const double* consts, in
     if (rc) return rc;
     if ((rc = rows_args("wdf_ss_dyn_rows", params, n_params, chan, r, B, T))) return rc;
     if (!rows) return fail(WDF_EINVAL, "wdf_ss_dyn_rows: null rows");
-    const dim3 grid((unsigned)((B + 63) / 64), (unsigned)rows_blocks_t(T));
+    const dim3 grid(waves64(B), (unsigned)rows_blocks_t(T));
     const size_t lds = (size_t)n_ops * 64 * sizeof(double);
     if ((rc = rows_lds_limit("wdf_ss_dyn_rows", (const void*)wdf::ss_dyn_rows_kernel, lds))) return rc;
     hipLaunchKernelGGL(wdf::ss_dyn_rows_kernel, grid, dim3(64), lds, (hipStream_t)stream, tp, params, r, rows, B, T);
@@ -282,7 +290,7 @@ int wdf_ss_dyn_rows(const int32_t* tape_ops, int n_ops, const double* consts, in
 size_t wdf_ss_dyn_rows_bwd_ws_bytes(int n_params, int64_t B, int64_t T)
 {
     if (B <= 0 || T <= 0 || n_params < 1 || n_params > wdf::kRowsMaxParams) return 0;
-    return (size_t)((B + 63) / 64) * (size_t)rows_blocks_t(T) * (size_t)n_params * sizeof(double);
+    return waves64(B) * (size_t)rows_blocks_t(T) * (size_t)n_params * sizeof(double);
 }
 
 int wdf_ss_dyn_rows_bwd(const int32_t* tape_ops, int n_ops, const double* consts, int n_consts, const int32_t* outs, int n_out,
@@ -295,7 +303,7 @@ int wdf_ss_dyn_rows_bwd(const int32_t* tape_ops, int n_ops, const double* consts
     if ((rc = rows_args("wdf_ss_dyn_rows_bwd", params, n_params, chan, r, B, T))) return rc;
     if (n_params < 1) return fail(WDF_EINVAL, "wdf_ss_dyn_rows_bwd: no component values to differentiate");
     if (!grows || !ws || !gparams) return fail(WDF_EINVAL, "wdf_ss_dyn_rows_bwd: null grows / ws / gparams");
-    const dim3 grid((unsigned)((B + 63) / 64), (unsigned)rows_blocks_t(T));
+    const dim3 grid(waves64(B), (unsigned)rows_blocks_t(T));
     const size_t lds = (size_t)n_ops * 64 * (sizeof(double) + sizeof(float)) + (size_t)n_params * 64 * sizeof(double);
     if ((rc = rows_lds_limit("wdf_ss_dyn_rows_bwd", (const void*)wdf::ss_dyn_rows_bwd_kernel, lds))) return rc;
     hipStream_t s = (hipStream_t)stream;

@@ -1,4 +1,4 @@
-// wdf_capi_ss_step.hip -- C ABI part 6 of 6: the one-pass MSE step of small state-space trees with a diode-pair root
+// wdf_capi_ss_step.hip -- C ABI of the one-pass MSE step of small state-space trees with a diode-pair root
 // (csrc/wdf_ss_nl_step.h): workspace layout, plan, template dispatch and the two launches of a step.
 #include "wdf_capi_common.h"
 #include "wdf_ss_nl_step.h"
@@ -12,15 +12,7 @@ int nl_nt(int ns, int ni) { return ns * ns + ns * ni + ns + ns + ni + 2; }
 int nl_nrec(int ns, int ni) { return 2 * ns + ns * ns + nl_nt(ns, ni) * ns + ns; }
 int nl_nsnap(int ns, int ni) { return ns + nl_nt(ns, ni) * ns + ns * ns; }
 
-void nl_geom(int64_t T, int n_chunks, int64_t& L, int& K)
-{
-    if (n_chunks < 1) n_chunks = 1;
-    L = (T + n_chunks - 1) / n_chunks;
-    L = (L + 31) / 32 * 32;
-    K = (int)((T + L - 1) / L);
-}
-
-size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr int kUnit = 32;                    // chunk lengths: multiples of 32 steps
 
 struct NlLayout {
     size_t ctl, ticket, coef_prev, rec, snap, gpart, part, total;
@@ -32,17 +24,19 @@ struct NlLayout {
 NlLayout nl_layout(int ns, int ni, int64_t B, int64_t T, int n_chunks)
 {
     NlLayout l{};
-    nl_geom(T, n_chunks, l.L, l.K);
-    l.groups_max = (int)((B + 63) / 64);
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    l.L = g.L;
+    l.K = g.K;
+    l.groups_max = (int)waves64(B);
     const size_t ng1 = (size_t)nl_kn(ns, ni) + 3;
     l.ctl = 0;
     l.ticket = 128;
     l.coef_prev = 256;
     l.rec = 512;
-    l.snap = up(l.rec + (size_t)l.K * nl_nrec(ns, ni) * (size_t)B * sizeof(float), 256);
-    l.gpart = up(l.snap + (size_t)2 * l.K * nl_nsnap(ns, ni) * (size_t)B * sizeof(float), 256);
-    l.part = up(l.gpart + (size_t)l.K * l.groups_max * ng1 * sizeof(double), 256);
-    l.total = up(l.part + (size_t)l.groups_max * (ng1 + 2) * sizeof(double), 256);   // (+ bad boundaries, largest miss)
+    l.snap = round_up(l.rec + (size_t)l.K * nl_nrec(ns, ni) * (size_t)B * sizeof(float), 256);
+    l.gpart = round_up(l.snap + (size_t)2 * l.K * nl_nsnap(ns, ni) * (size_t)B * sizeof(float), 256);
+    l.part = round_up(l.gpart + (size_t)l.K * l.groups_max * ng1 * sizeof(double), 256);
+    l.total = round_up(l.part + (size_t)l.groups_max * (ng1 + 2) * sizeof(double), 256);   // (+ bad boundaries, largest miss)
     return l;
 }
 
@@ -90,10 +84,7 @@ size_t wdf_ss_nl_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunk
 
 int wdf_ss_nl_step_chunk_len(int64_t T, int n_chunks)
 {
-    if (T <= 0 || n_chunks < 1) return 0;
-    int64_t L; int K;
-    nl_geom(T, n_chunks, L, K);
-    return (int)L;
+    return (T > 0 && n_chunks >= 1) ? (int)chunk_geom(T, n_chunks, kUnit).L : 0;
 }
 
 // cold_warmup: the warm-up of the first call (chunks start from z = 0); warm_warmup: where that call takes the snapshots the
@@ -110,7 +101,7 @@ int wdf_ss_nl_step_plan(void* ws, int ns, int ni, int64_t B, int64_t T, int n_ch
         return fail(WDF_EINVAL, "wdf_ss_nl_step_plan: warm-ups are multiples of 8, 8 <= w_min <= w_max, warm_warmup <= the chunk length %lld, tol > 0",
                     (long long)l.L);
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(ws, 0, l.rec, s) != hipSuccess) return fail(WDF_ELAUNCH, "wdf_ss_nl_step_plan: memset failed");
+    if (int rc = memset_async(ws, 0, l.rec, s)) return rc;
     hipLaunchKernelGGL(nl_plan_kernel, dim3(1), dim3(1), 0, s, (wdf::NlStepCtl*)ws, (unsigned*)((char*)ws + l.ticket), cold_warmup,
                        warm_warmup, w_min, w_max, tol);
     return check_launch("wdf_ss_nl_step_plan");
@@ -167,22 +158,16 @@ int wdf_ss_nl_step_mse(const float* x, const float* coef, const float* params, c
     const int64_t units = (int64_t)a.groups * a.K;
     const dim3 grid((unsigned)((units + 3) / 4));
     hipStream_t s = (hipStream_t)stream;
-#define WDF_NL_V(NS_, NI_, SYM_, V_, WD_)                                                                          \
-    {                                                                                                              \
-        {                                                                                                          \
-            EventBracket bracket(s);                                                                               \
-            hipLaunchKernelGGL((wdf::ss_nl_step_kernel<NS_, NI_, SYM_, V_>), grid, dim3(256), 0, s, a);            \
-        }                                                                                                          \
-        hipLaunchKernelGGL((wdf::ss_nl_step_finish_kernel<NS_, NI_, SYM_, WD_>), dim3(a.groups), dim3(64 * WD_ * wdf::NlTile<NS_, WD_>::n), 0, s, a); \
-    }
-#define WDF_NL(NS_, NI_)                                                                                           \
-    if (ns == NS_ && ni == NI_) {                                                                                  \
-        if (sym) { if (pair) WDF_NL_V(NS_, NI_, true, wdf::v2f, 2) else WDF_NL_V(NS_, NI_, true, float, 1) }       \
-        else { if (pair) WDF_NL_V(NS_, NI_, false, wdf::v2f, 2) else WDF_NL_V(NS_, NI_, false, float, 1) }         \
-    }
-    WDF_NL(1, 1) WDF_NL(1, 2) WDF_NL(2, 1) WDF_NL(2, 2)
-#undef WDF_NL
-#undef WDF_NL_V
+    const bool ok = dispatch([&](auto NS, auto NI, auto SYM, auto PAIR) {
+        using V = std::conditional_t<PAIR(), wdf::v2f, float>;
+        constexpr int WD = PAIR() ? 2 : 1;
+        {
+            EventBracket bracket(s);
+            hipLaunchKernelGGL((wdf::ss_nl_step_kernel<NS(), NI(), SYM(), V>), grid, dim3(256), 0, s, a);
+        }
+        hipLaunchKernelGGL((wdf::ss_nl_step_finish_kernel<NS(), NI(), SYM(), WD>), dim3(a.groups), dim3(64 * WD * wdf::NlTile<NS(), WD>::n), 0, s, a);
+    }, Values<int, 1, 2>{ns}, Values<int, 1, 2>{ni}, Bools{sym}, Bools{pair});
+    if (!ok) return no_kernel("wdf_ss_nl_step_mse");
     return check_launch("wdf_ss_nl_step_mse");
 }
 

@@ -421,7 +421,7 @@ class TpWarmState:
         """max_warm_tiles / min_warm_tiles: in warm-start units of warm_unit() steps (16)."""
         L = lib()
         self.K = L.wdf_clipper_tp_chunks(int(T), int(n_chunks))
-        chunk_len = -(-(-(-int(T) // max(1, int(n_chunks)))) // 32) * 32        # as the library rounds it
+        chunk_len = chunk_geom(T, n_chunks, 32)[0]
         # snapshots reach back at most three quarters of a chunk: the one-pass step may shorten the younger chunks by a quarter
         # (skewed spans, csrc/wdf_clipper_fused.h chunk_span) and they must still hold every snapshot
         self.unit = warm_unit()
@@ -445,6 +445,15 @@ class TpWarmState:
         i, f = c.view(torch.int32), c.view(torch.float32)
         return {"valid": int(i[0]), "next_warm_tiles": int(i[2]), "last_warm_tiles": int(i[3]),
                 "last_miss": float(f[12]), "n_calls": int(i[13]), "warm_unit_steps": self.unit, "cold_hold": int(i[20])}
+
+
+def chunk_geom(T, n_chunks, unit):
+    """(L, K): T steps in at most n_chunks chunks of L steps, L a multiple of `unit` -- csrc/wdf_capi_common.h chunk_geom, for
+    the families whose count the library does not export (it does: wdf_clipper_tp_chunks, wdf_ss_tp_chunks,
+    wdf_clipper_mlp_tp_chunks, wdf_ss_nl_step_chunk_len)."""
+    T, unit = int(T), int(unit)
+    L = -(-(-(-T // max(1, int(n_chunks)))) // unit) * unit
+    return L, -(-T // L)
 
 
 def warm_unit():
@@ -1028,8 +1037,7 @@ def clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, tol=1e-12, max_it
     if theta6.numel() != 6:
         raise WdfHipError("theta6 must hold {Is_up, nVt_up, Is_down, nVt_down, R, C}")
     B, T = x.shape
-    Lc = -(-(-(-T // max(1, int(n_chunks)))) // 8) * 8
-    K = -(-T // Lc)
+    K = asym_chunks(T, n_chunks)
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, B), dtype=torch.float32, device=x.device) if want_stash else None
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
@@ -1066,8 +1074,7 @@ def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None,
     B, T = x.shape
     if tuple(gy.shape) != (T, B) or tuple(zstash.shape) != (T, B) or zT is None or zT.numel() != B:
         raise WdfHipError(f"gy / zstash must be [T,B] = [{T},{B}], zT [{B}]")
-    Lc = -(-(-(-T // max(1, int(n_chunks)))) // 8) * 8
-    K = -(-T // Lc)
+    K = asym_chunks(T, n_chunks)
     need = lib().wdf_clipper_asym_bwd_tp_ws_bytes(B, K)
     if ws is None or ws.numel() < need:
         ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
@@ -1081,8 +1088,7 @@ def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None,
 
 def asym_chunks(T, n_chunks):
     """The chunk count the asym kernels accept for T: n_chunks rounded to one that tiles T in 8-step units."""
-    Lc = -(-(-(-int(T) // max(1, int(n_chunks)))) // 8) * 8
-    return -(-int(T) // Lc)
+    return chunk_geom(T, n_chunks, 8)[1]
 
 
 def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, y=None,
@@ -1313,12 +1319,11 @@ def ss_dyn_bwd(x, rows, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, w=N
 
 def dyn_chunks(T, n_chunks):
     """The chunk count wdf_ss_dyn_*_tp accept for a requested one: chunks are whole 8-step units."""
-    Lc = -(-(-(-int(T) // max(1, int(n_chunks)))) // 8) * 8
-    return -(-int(T) // Lc)
+    return chunk_geom(T, n_chunks, 8)[1]
 
 
 def dyn_chunk_len(T, n_chunks):
-    return -(-(-(-int(T) // max(1, int(n_chunks)))) // 8) * 8
+    return chunk_geom(T, n_chunks, 8)[0]
 
 
 def ss_dyn_fwd_tp(x, rows, ns, ni, n_chunks, warmup, tol=1.0e-6, root_kind=ROOT_NONE, rootp=None, w=None, hidden=0, n_tanh=0, n_up=1,

@@ -216,8 +216,7 @@ def segment_plan(B, T, R_slowest, C, fs, tol=1.0e-6):
     K = min(T // max(2 * W, 64), -(-engine.N_SIMD // waves))
     if K < 2:
         return None
-    L = -(-(-(-T // K)) // 8) * 8
-    K = -(-T // L)
+    L, K = binding.chunk_geom(T, K, 8)
     return (K, L, W) if K >= 2 and L >= W else None
 
 

@@ -121,3 +121,152 @@ def test_no_gpu_means_error_not_fallback():
         pytest.skip("GPU present")
     with pytest.raises(binding.WdfHipError):
         binding.clipper_fwd(torch.zeros(2, 8), torch.zeros(4), 48000.0)
+
+
+# ---- argument validation of the chunked entry-point families (no GPU: every call below fails its checks first) ----------
+ONE = C.c_void_p(256)      # a non-null, 16-byte aligned pointer that no check dereferences
+
+
+def _call(lib, name, order, **kw):
+    return getattr(lib, name)(*[kw[k] for k in order])
+
+
+def _cases(lib, name, order, good, bad):
+    """every entry of bad: (overrides, expected return code, bytes the message holds or None)"""
+    for over, code, text in bad:
+        rc = _call(lib, name, order, **{**good, **over})
+        assert rc == code, (name, over, rc, lib.wdf_last_error())
+        if text:
+            assert text in lib.wdf_last_error(), (name, over, lib.wdf_last_error())
+
+
+def test_asym_argument_validation_without_gpu(lib):
+    fwd = "x theta6 fs mode tol max_iter y zstash z0 zT iters B T stream".split()
+    good = dict(x=ONE, theta6=ONE, fs=48000.0, mode=1, tol=1e-12, max_iter=50, y=ONE, zstash=None, z0=None, zT=None, iters=None, B=4, T=64,
+                stream=None)
+    _cases(lib, "wdf_clipper_asym_fwd", fwd, good,
+           [(dict(x=None), -1, b"null"), (dict(y=None), -1, b"null"), (dict(B=0), -1, None), (dict(T=0), -1, None), (dict(fs=0.0), -1, None),
+            (dict(mode=7), -1, b"mode"), (dict(mode=-1), -1, b"mode"), (dict(tol=0.0), -1, b"tol"), (dict(mode=2, max_iter=0), -1, b"max_iter")])
+    tp = "x theta6 fs mode tol max_iter y zstash z0 zT B T n_chunks warmup verify_tol ws status stream".split()
+    good = dict(x=ONE, theta6=ONE, fs=48000.0, mode=2, tol=1e-12, max_iter=50, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64, n_chunks=4,
+                warmup=8, verify_tol=1e-6, ws=ONE, status=ONE, stream=None)
+    _cases(lib, "wdf_clipper_asym_fwd_tp", tp, good,
+           [(dict(ws=None), -1, b"null"), (dict(status=None), -1, b"null"), (dict(B=0), -1, None), (dict(mode=3), -1, b"mode"),
+            (dict(n_chunks=0), -1, b"n_chunks"), (dict(n_chunks=5), -1, b"does not tile"), (dict(n_chunks=7, T=65), -1, b"does not tile"),
+            (dict(warmup=-1), -1, b"warmup"), (dict(verify_tol=-1.0), -1, None), (dict(tol=-1.0), -1, b"tol")])
+    bwd = "x theta6 fs tol max_iter zstash gy ws gtheta6 B T stream".split()
+    good = dict(x=ONE, theta6=ONE, fs=48000.0, tol=1e-12, max_iter=50, zstash=ONE, gy=ONE, ws=ONE, gtheta6=ONE, B=4, T=64, stream=None)
+    _cases(lib, "wdf_clipper_asym_bwd", bwd, good,
+           [(dict(zstash=None), -1, b"null"), (dict(gtheta6=None), -1, b"null"), (dict(B=0), -1, None), (dict(max_iter=0), -1, None)])
+    btp = "x theta6 fs mode zstash zT gy gzT ws gtheta6 gz0 B T n_chunks stream".split()
+    good = dict(x=ONE, theta6=ONE, fs=48000.0, mode=1, zstash=ONE, zT=ONE, gy=ONE, gzT=None, ws=ONE, gtheta6=ONE, gz0=None, B=4, T=64,
+                n_chunks=4, stream=None)
+    _cases(lib, "wdf_clipper_asym_bwd_tp", btp, good,
+           [(dict(zT=None), -1, b"null"), (dict(B=0), -1, None), (dict(mode=9), -1, b"mode"), (dict(n_chunks=0), -1, None),
+            (dict(n_chunks=5), -1, b"does not tile")])
+    step = ("x theta6 fs mode tol max_iter target gscale y z0 zT B T n_chunks warmup verify_tol ws status out7 m v step lr beta1 beta2 eps lo hi "
+            "stream").split()
+    good = dict(x=ONE, theta6=ONE, fs=48000.0, mode=2, tol=1e-12, max_iter=50, target=ONE, gscale=1.0, y=ONE, z0=None, zT=None, B=4, T=64,
+                n_chunks=4, warmup=8, verify_tol=1e-6, ws=ONE, status=ONE, out7=ONE, m=None, v=None, step=None, lr=None, beta1=0.9, beta2=0.999,
+                eps=1e-8, lo=None, hi=None, stream=None)
+    _cases(lib, "wdf_clipper_asym_step_mse", step, good,
+           [(dict(out7=None), -1, b"null"), (dict(B=0), -1, None), (dict(mode=0), -1, b"mode 0"), (dict(mode=5), -1, b"mode"),
+            (dict(n_chunks=5), -1, b"does not tile"), (dict(n_chunks=70000), -1, None), (dict(m=ONE), -1, b"Adam"),
+            (dict(m=ONE, v=ONE, step=ONE), -1, b"Adam"), (dict(z0=ONE, zT=ONE), -1, b"alias")])
+    root = "a theta6 fs mode tol max_iter b n stream".split()
+    good = dict(a=ONE, theta6=ONE, fs=48000.0, mode=2, tol=1e-12, max_iter=50, b=ONE, n=8, stream=None)
+    _cases(lib, "wdf_asym_root", root, good, [(dict(a=None), -1, None), (dict(n=0), -1, None), (dict(mode=4), -1, b"mode"), (dict(tol=0.0), -1, None)])
+
+
+def test_state_space_chunked_argument_validation_without_gpu(lib):
+    tp = "x coef rootp ns ni n_up n_down y zstash z0 zT B T n_chunks warmup tol zinit ws status stream".split()
+    good = dict(x=ONE, coef=ONE, rootp=ONE, ns=2, ni=1, n_up=1, n_down=1, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64, n_chunks=4, warmup=8,
+                tol=1e-6, zinit=None, ws=ONE, status=ONE, stream=None)
+    _cases(lib, "wdf_ss_fwd_tp", tp, good,
+           [(dict(x=None), -1, b"null"), (dict(ws=None), -1, b"null"), (dict(rootp=None), -1, None), (dict(B=0), -1, None), (dict(ns=5), -3, None),
+            (dict(ni=3), -3, None), (dict(ns=0), -1, None), (dict(n_up=0), -1, None), (dict(n_chunks=0), -1, None),
+            (dict(n_chunks=5), -1, b"wdf_ss_tp_chunks"), (dict(warmup=-1), -1, None), (dict(tol=-1.0), -1, None)])
+    starts = (C.c_int64 * 8)()
+    assert lib.wdf_ss_tp_starts(64, 5, 8, starts) == -1 and b"does not tile" in lib.wdf_last_error()
+    assert lib.wdf_ss_tp_starts(64, 4, 8, None) == -1
+    assert lib.wdf_ss_tp_starts(64, 4, 8, starts) == 0 and list(starts)[:4] == [0, 8, 24, 40]
+    plan = "ws ns ni B T n_chunks cold_warmup warm_warmup w_min w_max tol stream".split()
+    good = dict(ws=ONE, ns=1, ni=1, B=4, T=256, n_chunks=4, cold_warmup=64, warm_warmup=16, w_min=8, w_max=64, tol=1e-5, stream=None)
+    _cases(lib, "wdf_ss_nl_step_plan", plan, good,
+           [(dict(ws=None), -1, b"null"), (dict(ns=3), -3, None), (dict(ns=0), -3, None), (dict(ni=3), -3, None), (dict(B=0), -1, None),
+            (dict(n_chunks=0), -1, None), (dict(cold_warmup=12), -1, None), (dict(warm_warmup=128), -1, b"chunk length 64"),
+            (dict(w_min=16, w_max=8), -1, None), (dict(tol=0.0), -1, None)])
+    nl = "x coef params jac n_tree ns ni n_up n_down target gscale y ws out loss_out B T n_chunks stream".split()
+    good = dict(x=ONE, coef=ONE, params=ONE, jac=ONE, n_tree=2, ns=1, ni=1, n_up=1, n_down=1, target=ONE, gscale=1.0, y=ONE, ws=ONE, out=ONE,
+                loss_out=None, B=4, T=256, n_chunks=4, stream=None)
+    _cases(lib, "wdf_ss_nl_step_mse", nl, good,
+           [(dict(jac=None), -1, b"null"), (dict(out=None), -1, b"null"), (dict(ns=3), -3, None), (dict(B=0), -1, None), (dict(n_chunks=0), -1, None),
+            (dict(n_tree=0), -1, None), (dict(n_tree=99), -1, None), (dict(n_down=0), -1, None)])
+    lin = "x coef jac n_params ns ni target gscale y ws out loss_out gcoef_out B T n_chunks z0 zT stream".split()
+    good = dict(x=ONE, coef=ONE, jac=ONE, n_params=2, ns=1, ni=1, target=ONE, gscale=1.0, y=ONE, ws=ONE, out=ONE, loss_out=None, gcoef_out=None,
+                B=4, T=256, n_chunks=4, z0=None, zT=None, stream=None)
+    _cases(lib, "wdf_ss_lin_step_mse", lin, good,
+           [(dict(x=None), -1, b"null"), (dict(ws=None), -1, b"null"), (dict(ns=3), -3, None), (dict(ni=0), -3, None), (dict(B=0), -1, None),
+            (dict(n_chunks=0), -1, None), (dict(n_params=0), -1, None), (dict(z0=ONE, zT=ONE), -1, b"alias")])
+    dyn = ("x rows per_sample ns ni root rootp w hidden n_tanh_layers n_up n_down y zstash z0 zT B T n_chunks warmup tol zinit ws status "
+           "stream").split()
+    good = dict(x=ONE, rows=ONE, per_sample=1, ns=2, ni=1, root=0, rootp=None, w=None, hidden=0, n_tanh_layers=0, n_up=1, n_down=1, y=ONE,
+                zstash=None, z0=None, zT=None, B=4, T=64, n_chunks=4, warmup=8, tol=1e-6, zinit=None, ws=ONE, status=ONE, stream=None)
+    _cases(lib, "wdf_ss_dyn_fwd_tp", dyn, good,
+           [(dict(rows=None), -1, b"null"), (dict(status=None), -1, b"null"), (dict(B=0), -1, None), (dict(ns=9), -3, None), (dict(ni=0), -3, None),
+            (dict(ns=0), -1, None), (dict(per_sample=3), -1, None), (dict(root=1), -1, b"root"), (dict(root=2), -1, b"rootp"),
+            (dict(root=3, w=ONE, hidden=5, n_tanh_layers=3), -3, None), (dict(root=3, w=None, hidden=8, n_tanh_layers=3), -1, None),
+            (dict(n_chunks=5), -1, b"does not tile"), (dict(warmup=-1), -1, None)])
+
+
+def test_mlp_chunked_argument_validation_without_gpu(lib):
+    tp = "x r theta2 w hidden n_tanh_layers fs y zstash z0 zT B T n_chunks warmup warmup_per_wave tol ws status stream".split()
+    good = dict(x=ONE, r=None, theta2=ONE, w=ONE, hidden=8, n_tanh_layers=3, fs=48000.0, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64,
+                n_chunks=4, warmup=16, warmup_per_wave=None, tol=1e-6, ws=ONE, status=ONE, stream=None)
+    _cases(lib, "wdf_clipper_mlp_fwd_tp", tp, good,
+           [(dict(w=None), -1, b"null"), (dict(ws=None), -1, b"null"), (dict(B=0), -1, None), (dict(fs=0.0), -1, None), (dict(hidden=5), -3, None),
+            (dict(hidden=16, n_tanh_layers=5), -3, None), (dict(n_tanh_layers=2), -3, None), (dict(n_chunks=0), -1, None),
+            (dict(warmup=-1), -1, None), (dict(tol=-1.0), -1, None)])
+
+
+# ---- chunk geometry: what every export promises, whatever rule computes it ---------------------------------------------------
+GEOM_T = [1, 7, 8, 31, 32, 33, 257, 2048, 4095, 4096]
+GEOM_N = [1, 2, 3, 5, 32, 47, 1000]
+CHUNK_EXPORTS = [("wdf_clipper_tp_chunks", 32), ("wdf_ss_tp_chunks", 8), ("wdf_clipper_mlp_tp_chunks", 16)]
+
+
+@pytest.mark.parametrize("name,unit", CHUNK_EXPORTS)
+def test_chunk_count_exports_tile_T(lib, name, unit):
+    chunks = getattr(lib, name)
+    for T in GEOM_T:
+        for n in GEOM_N:
+            K = chunks(T, n)
+            assert 1 <= K <= n, (T, n, K)
+            L = -(-T // (K * unit)) * unit                       # the shortest whole-unit chunk that covers T in K chunks ...
+            assert L % unit == 0 and (K - 1) * L < T <= K * L, (T, n, K, L)      # ... leaves none of the K empty
+            assert chunks(T, K) == K, (T, n, K)                  # a count the library returned is one it accepts
+    assert chunks(0, 4) == 0
+
+
+def test_nl_step_chunk_len_tiles_T(lib):
+    unit = 32
+    for T in GEOM_T:
+        for n in GEOM_N:
+            L = lib.wdf_ss_nl_step_chunk_len(T, n)
+            K = -(-T // L)
+            assert L % unit == 0 and K <= n and (K - 1) * L < T <= K * L, (T, n, L, K)
+            assert (L - unit) * n < T, (T, n, L)                 # no shorter whole-unit chunk covers T in n chunks
+            assert lib.wdf_ss_nl_step_chunk_len(T, K) == L, (T, n, L, K)
+    assert lib.wdf_ss_nl_step_chunk_len(0, 4) == 0 and lib.wdf_ss_nl_step_chunk_len(64, 0) == 0
+
+
+def test_binding_chunk_geom_agrees_with_the_library(lib):
+    from wdf_hip import binding
+    for T in [1, 31, 257, 2048, 4096] + GEOM_T:
+        for n in [1, 2, 5, 32, 47]:
+            for name, unit in CHUNK_EXPORTS:
+                assert binding.chunk_geom(T, n, unit)[1] == getattr(lib, name)(T, n), (name, T, n)
+            assert binding.chunk_geom(T, n, 32)[0] == lib.wdf_ss_nl_step_chunk_len(T, n), (T, n)
+            assert binding.asym_chunks(T, n) == binding.dyn_chunks(T, n) == lib.wdf_ss_tp_chunks(T, n)
+            L, K = binding.chunk_geom(T, n, 8)
+            assert L % 8 == 0 and K <= n and (K - 1) * L < T <= K * L and binding.dyn_chunk_len(T, n) == L
