@@ -1,4 +1,5 @@
-// wdf_asym_step.h -- the MSE training step of the two-different-diode clipper (wdf_asym.h) in ONE pass over the data:
+// wdf_asym_step.h -- the training step of the two-different-diode clipper (wdf_asym.h) in ONE pass over the data, for the
+// MSE loss (LOSS = 0) and for the scripts' MSE + ESR loss past `skip` samples (LOSS = 1):
 // forward, loss and gradient with x and the target read once and y written once, no state stash, one root solve per sample.
 // Both Newton modes; the closed form (mode 0) is a model approximation and keeps the kernel pair.
 //
@@ -18,8 +19,20 @@
 // warm-up.  A chunk whose start state missed the verification never reaches the gradient: the flagged waves are re-run by a
 // gated launch of the same kernel with one chunk, whose record (slot 0) replaces the wave's K chunked ones.
 //
+// MSE + ESR (clipper_pot.py:146-156,177,232,248): loss = S/n + sqrt(S / (E + eps) / n), S = sum e^2, E = sum y^2 over the rows
+// t >= skip.  dLoss/dy = ga e + gb y with ga, gb functions of the GLOBAL S and E (esr_coef_kernel's formulas), so the pass
+// carries BOTH tangent-weighted sums, gP_i = sum e dy_i = d(S/2)/d parameter and gQ_i = sum y dy_i = d(E/2)/d parameter; a
+// chunk records, next to the above,
+//     A_Q = sum_t y_t (m_t' + m_t) / 2     gQ's sums = A_Q tau_in + betaQ_i
+// and E.  Rows before skip add nothing to S, E, A, A_Q, beta, betaQ (e and y enter the sums as zero: a wave-uniform select);
+// state, y, tau and m advance on them as on any other row.  The finish kernel hands back {S, E, gP[6], gQ[6]} of this call
+// in theta-space (the chain rule is linear: applied to gP and gQ separately), which is what several ranks all-reduce, and
+// finishes the step itself as a single rank when asked.
+//
 // Precision as the reverse sweep's: partials in fp32 (their inputs are fp32), recurrence and sums in fp64.
-// rec: double [K][15][B] = {P, A, S, q[6], beta[6]}.   L and W are multiples of 8.
+// rec, LOSS = 0: double [K][15][B] = {P, A, S, q[6], beta[6]};
+//      LOSS = 1: double [K][23][B] = {P, A, S, q[6], beta[6], A_Q, E, betaQ[6]} (rows 0..14 as LOSS = 0).
+// L and W are multiples of 8.
 #pragma once
 
 #include "wdf_asym.h"
@@ -28,10 +41,14 @@
 namespace wdf {
 
 constexpr int kAsymStepRec = 15;
+constexpr int kAsymStepRecEsr = 23;
+constexpr int kAsymStepPart = 8;                 // doubles per wave partial, LOSS = 0: {S, G[6], 0}
+constexpr int kAsymStepPartEsr = 16;             //                           LOSS = 1: {S, E, gP[6], gQ[6], 0, 0}
 
 // gate == nullptr: the chunked launch, grid = (waves, K); it also clears status and the finish kernel's ticket.
 // gate != nullptr: the repair launch, grid = (waves, 1) with L >= T: flagged waves only.
-template <int MODE, bool VEC4>
+// skip: LOSS = 1 only (rows before it count for nothing); anywhere in 0..T-1, inside a block or a later chunk.
+template <int MODE, bool VEC4, int LOSS = 0>
 __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __restrict__ x, const float* __restrict__ theta6, float fs,
                                                                const float* __restrict__ target, float* __restrict__ y,
                                                                const float* __restrict__ z0, float* __restrict__ zT,
@@ -39,7 +56,7 @@ __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __re
                                                                double* __restrict__ rec, double tol, int max_iter,
                                                                AsymTpStatus* __restrict__ status, unsigned* __restrict__ ticket,
                                                                const unsigned* __restrict__ gate, int64_t B, int64_t T, int64_t L,
-                                                               int64_t W)
+                                                               int64_t W, int64_t skip = 0)
 {
     using S = typename AsymStep<MODE>::S;
     if (gate != nullptr) {
@@ -60,6 +77,7 @@ __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __re
     S z = (tw == 0 && z0) ? (S)z0[b] : (S)0;
     double tau[6] = {0, 0, 0, 0, 0, 0}, be[6] = {0, 0, 0, 0, 0, 0};
     double m = 1.0, A = 0.0, sse = 0.0;
+    double bq[LOSS ? 6 : 1] = {}, AQ = 0.0, en = 0.0;            // LOSS = 1: betaQ, A_Q, E
     constexpr int kB = 8;
     float xc[kB], xn[kB], tc[kB], tn[kB];
     auto load_x = [&](int64_t t, float(&v)[kB]) {                // [B][T]: two float4 per lane where the block is whole
@@ -108,29 +126,56 @@ __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __re
 #pragma unroll
                     for (int q = 0; q < 5; ++q) cth[q] = (double)cf[q];
                     cth[5] = -(1.0 + Da) * bd;
-                    const double e = (double)yv - (double)tc[i], eh = 0.5 * e;
-                    sse = fma(e, e, sse);
+                    if constexpr (LOSS == 0) {
+                        const double e = (double)yv - (double)tc[i], eh = 0.5 * e;
+                        sse = fma(e, e, sse);
 #pragma unroll
-                    for (int q = 0; q < 6; ++q) {
-                        const double t_new = fma(kap, tau[q], cth[q]);
-                        be[q] = fma(eh, t_new + tau[q], be[q]);
-                        tau[q] = t_new;
+                        for (int q = 0; q < 6; ++q) {
+                            const double t_new = fma(kap, tau[q], cth[q]);
+                            be[q] = fma(eh, t_new + tau[q], be[q]);
+                            tau[q] = t_new;
+                        }
+                        const double m_new = kap * m;
+                        A = fma(eh, m_new + m, A);
+                        m = m_new;
+                    } else {
+                        const bool counted = tb + i >= skip;     // wave-uniform: a select, no branch
+                        const double yd = counted ? (double)yv : 0.0;
+                        const double e = counted ? (double)yv - (double)tc[i] : 0.0;
+                        const double eh = 0.5 * e, yh = 0.5 * yd;
+                        sse = fma(e, e, sse);
+                        en = fma(yd, yd, en);
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) {
+                            const double t_new = fma(kap, tau[q], cth[q]);
+                            const double dy2 = t_new + tau[q];
+                            be[q] = fma(eh, dy2, be[q]);
+                            bq[q] = fma(yh, dy2, bq[q]);
+                            tau[q] = t_new;
+                        }
+                        const double m_new = kap * m, dm2 = m_new + m;
+                        A = fma(eh, dm2, A);
+                        AQ = fma(yh, dm2, AQ);
+                        m = m_new;
                     }
-                    const double m_new = kap * m;
-                    A = fma(eh, m_new + m, A);
-                    m = m_new;
                 }
             }
         }
     }
     zend[k * B + b] = (float)z;
     if (zT && t1 == T) zT[b] = (float)z;
-    double* __restrict__ r = rec + (k * kAsymStepRec) * B + b;
+    double* __restrict__ r = rec + (k * (LOSS ? kAsymStepRecEsr : kAsymStepRec)) * B + b;
     r[0] = m;
     r[B] = A;
     r[2 * B] = sse;
 #pragma unroll
     for (int q = 0; q < 6; ++q) { r[(3 + q) * B] = tau[q]; r[(9 + q) * B] = be[q]; }
+    if constexpr (LOSS != 0) {
+        r[15 * B] = AQ;
+        r[16 * B] = en;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) r[(17 + q) * B] = bq[q];
+    }
 }
 
 // Adam with clip bounds on theta6 in the finish kernel's last wave (adam_clip_kernel's rule, wdf_optim.h); m == nullptr: none
@@ -146,61 +191,97 @@ __device__ __forceinline__ double asym_wave_sum_all(double v)
     return v;
 }
 
-// One lane per sequence: the K records first to last (one record where the wave was repaired), the wave's sums -> part[wave][8]
-// = {S, G[6], 0}; the wave that finishes LAST sums the partials in a fixed order (lane i takes waves i, i + 64, ...; then
-// the shuffle tree), applies the chain rule Rp, p -> R, C (clipper_asym_grad_reduce_kernel's formulas) and gscale:
-// out7 = {sse, d(gscale/2 sse)/d{Is1, V1, Is2, V2, R, C}}; then Adam, if asked for.
-static __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const double* __restrict__ rec, const unsigned* __restrict__ gate,
-                                                                             double* part, unsigned* ticket, float* theta6, float fs,
-                                                                             float gscale, float* __restrict__ out7, AsymStepAdam adam,
-                                                                             int64_t B, int64_t K)
+// What the MSE + ESR finish hands back (LOSS = 1): sums14 = {S, E, gP[6], gQ[6]} of THIS call in theta-space; gtheta6 != nullptr:
+// the step finished as a single rank -- ga, gb, mse, esr from S, E, n_global and eps (esr_coef_kernel's formulas),
+// gtheta6 = ga gP + gb gQ, loss3 = {mse, esr, mse + esr} (optional), then Adam, if asked for.
+struct AsymStepEsrOut {
+    double n_global, eps; float* sums14; float* gtheta6; float* loss3;
+};
+
+// the chain rule Rp, p -> R, C of a pair of sums (clipper_asym_grad_reduce_kernel's formulas)
+__device__ __forceinline__ void asym_step_chain_rule(double SRp, double Sp, double R, double C, float fs, double& gR, double& gC)
 {
+    const double G1 = 1.0 / R, G2 = C * (2.0 * (double)fs), Rp = 1.0 / (G1 + G2), p = G1 * Rp;
+    gR = SRp * Rp * Rp * G1 * G1 - Sp * G1 * G1 * Rp * (1.0 - p);
+    gC = -2.0 * (double)fs * (SRp * Rp * Rp + Sp * p * Rp);
+}
+
+// One lane per sequence: the K records first to last (one record where the wave was repaired), the wave's sums -> part[wave][8]
+// = {S, G[6], 0} (LOSS = 1: part[wave][16] = {S, E, gP[6], gQ[6], 0, 0}, both families walked with the same tangent:
+// gP_i += A tau_i + beta_i, gQ_i += A_Q tau_i + betaQ_i, tau_i <- P tau_i + q_i); the wave that finishes LAST sums the
+// partials in a fixed order (lane i takes waves i, i + 64, ...; then the shuffle tree), applies the chain rule Rp, p -> R, C
+// and, LOSS = 0, gscale: out7 = {sse, d(gscale/2 sse)/d{Is1, V1, Is2, V2, R, C}}; LOSS = 1: AsymStepEsrOut; then Adam, if asked for.
+template <int LOSS>
+__global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const double* __restrict__ rec, const unsigned* __restrict__ gate,
+                                                                      double* part, unsigned* ticket, float* theta6, float fs,
+                                                                      float gscale, float* __restrict__ out7, AsymStepEsrOut esr,
+                                                                      AsymStepAdam adam, int64_t B, int64_t K)
+{
+    constexpr int NREC = LOSS ? kAsymStepRecEsr : kAsymStepRec, NP = LOSS ? kAsymStepPartEsr : kAsymStepPart;
+    constexpr int NS = LOSS ? 14 : 7, GP = LOSS ? 2 : 1, GQ = 8;            // sums; where gP (and, LOSS = 1, gQ) start in them
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool live = b_raw < B;
     const int64_t b = live ? b_raw : B - 1;
     const int64_t kn = (gate != nullptr && gate[blockIdx.x] != 0u) ? 1 : K;
-    double tau[6] = {0, 0, 0, 0, 0, 0}, s[7] = {0, 0, 0, 0, 0, 0, 0};
+    double tau[6] = {0, 0, 0, 0, 0, 0}, s[NS] = {};
     for (int64_t k = 0; k < kn; ++k) {
-        const double* __restrict__ r = rec + (k * kAsymStepRec) * B + b;
+        const double* __restrict__ r = rec + (k * NREC) * B + b;
         const double P = r[0], A = r[B];
         s[0] += r[2 * B];
+        double AQ = 0.0;
+        if constexpr (LOSS != 0) { AQ = r[15 * B]; s[1] += r[16 * B]; }
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            s[1 + q] += fma(A, tau[q], r[(9 + q) * B]);
+            s[GP + q] += fma(A, tau[q], r[(9 + q) * B]);
+            if constexpr (LOSS != 0) s[GQ + q] += fma(AQ, tau[q], r[(17 + q) * B]);
             tau[q] = fma(P, tau[q], r[(3 + q) * B]);
         }
     }
     const unsigned nwaves = gridDim.x;
-    double w[7];
+    double w[NS];
 #pragma unroll
-    for (int i = 0; i < 7; ++i) w[i] = asym_wave_sum_all(live ? s[i] : 0.0);
+    for (int i = 0; i < NS; ++i) w[i] = asym_wave_sum_all(live ? s[i] : 0.0);
     unsigned done = 0;
     if (threadIdx.x == 0) {
-        double* o = part + (int64_t)blockIdx.x * 8;
+        double* o = part + (int64_t)blockIdx.x * NP;
 #pragma unroll
-        for (int i = 0; i < 7; ++i) __hip_atomic_store(o + i, w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < NS; ++i) __hip_atomic_store(o + i, w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the partial has landed before the count moves
         done = atomicAdd(ticket, 1u);
     }
     done = __builtin_amdgcn_readfirstlane(done);
     if (done != nwaves - 1) return;
-    double t[7] = {0, 0, 0, 0, 0, 0, 0};
+    double t[NS] = {};
     for (unsigned i = threadIdx.x; i < nwaves; i += 64)
 #pragma unroll
-        for (int j = 0; j < 7; ++j) t[j] += __hip_atomic_load(part + (int64_t)i * 8 + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int j = 0; j < NS; ++j) t[j] += __hip_atomic_load(part + (int64_t)i * NP + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-    for (int j = 0; j < 7; ++j) t[j] = asym_wave_sum_all(t[j]);
+    for (int j = 0; j < NS; ++j) t[j] = asym_wave_sum_all(t[j]);
     // every lane forms the chain rule, lanes 0..5 keep their component
     const double R = theta6[4], C = theta6[5];
-    const double G1 = 1.0 / R, G2 = C * (2.0 * (double)fs), Rp = 1.0 / (G1 + G2), p = G1 * Rp;
-    const double SRp = t[5], Sp = t[6];
-    const double gR = SRp * Rp * Rp * G1 * G1 - Sp * G1 * G1 * Rp * (1.0 - p);
-    const double gC = -2.0 * (double)fs * (SRp * Rp * Rp + Sp * p * Rp);
+    double gR, gC;
+    asym_step_chain_rule(t[GP + 4], t[GP + 5], R, C, fs, gR, gC);
     const int i = threadIdx.x < 6 ? threadIdx.x : 5;
-    const double gi = i == 0 ? t[1] : (i == 1 ? t[2] : (i == 2 ? t[3] : (i == 3 ? t[4] : (i == 4 ? gR : gC))));
-    const float g = (float)((double)gscale * gi);
-    if (threadIdx.x == 0) out7[0] = (float)t[0];
-    if (threadIdx.x < 6) out7[1 + threadIdx.x] = g;
+    const double gi = i == 0 ? t[GP] : (i == 1 ? t[GP + 1] : (i == 2 ? t[GP + 2] : (i == 3 ? t[GP + 3] : (i == 4 ? gR : gC))));
+    float g;
+    if constexpr (LOSS == 0) {
+        g = (float)((double)gscale * gi);
+        if (threadIdx.x == 0) out7[0] = (float)t[0];
+        if (threadIdx.x < 6) out7[1 + threadIdx.x] = g;
+    } else {
+        double qR, qC;
+        asym_step_chain_rule(t[GQ + 4], t[GQ + 5], R, C, fs, qR, qC);
+        const double qi = i == 0 ? t[GQ] : (i == 1 ? t[GQ + 1] : (i == 2 ? t[GQ + 2] : (i == 3 ? t[GQ + 3] : (i == 4 ? qR : qC))));
+        if (threadIdx.x == 0) { esr.sums14[0] = (float)t[0]; esr.sums14[1] = (float)t[1]; }
+        if (threadIdx.x < 6) { esr.sums14[2 + threadIdx.x] = (float)gi; esr.sums14[8 + threadIdx.x] = (float)qi; }
+        if (esr.gtheta6 == nullptr) return;
+        const double n = esr.n_global, S = t[0], E = t[1] + esr.eps;
+        const double mse = S / n, er = sqrt(S / E / n);
+        const double ga = 2.0 / n + (er > 0.0 ? 1.0 / (er * E * n) : 0.0), gb = -er / E;
+        g = (float)(ga * gi + gb * qi);
+        if (threadIdx.x < 6) esr.gtheta6[threadIdx.x] = g;
+        if (threadIdx.x == 0 && esr.loss3) { esr.loss3[0] = (float)mse; esr.loss3[1] = (float)er; esr.loss3[2] = (float)(mse + er); }
+    }
     if (adam.m == nullptr) return;
     const int n = *adam.step + 1;                                // (one wave: every lane has read it before lane 0 writes)
     if (threadIdx.x == 0) *adam.step = n;
@@ -215,6 +296,17 @@ static __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(con
     if (adam.lo) th = fmaxf(th, adam.lo[i]);
     if (adam.hi) th = fminf(th, adam.hi[i]);
     theta6[i] = th;
+}
+
+// Several ranks: sums14 summed over the ranks -> the global loss and gradient (the single-rank finish's formulas, on the floats)
+static __global__ void asym_esr_finish_kernel(const float* __restrict__ sums14, double n, double eps, float* __restrict__ gtheta6,
+                                              float* __restrict__ loss3)
+{
+    const double S = sums14[0], E = (double)sums14[1] + eps;
+    const double mse = S / n, esr = sqrt(S / E / n);
+    const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0), gb = -esr / E;
+    for (int k = 0; k < 6; ++k) gtheta6[k] = (float)(ga * (double)sums14[2 + k] + gb * (double)sums14[8 + k]);
+    if (loss3) { loss3[0] = (float)mse; loss3[1] = (float)esr; loss3[2] = (float)(mse + esr); }
 }
 
 }  // namespace wdf

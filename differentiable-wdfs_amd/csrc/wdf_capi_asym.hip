@@ -1,5 +1,5 @@
 // wdf_capi_asym.hip -- C ABI of the two-different-diode (asymmetric) clipper (csrc/wdf_asym.h, csrc/wdf_asym_step.h): sequential and
-// time-parallel forward / reverse sweep, the stand-alone root, the one-pass MSE step.  Argument checking, workspace layouts,
+// time-parallel forward / reverse sweep, the stand-alone root, the one-pass MSE and MSE + ESR steps.  Argument checking, workspace layouts,
 // template dispatch and launches.
 #include "wdf_capi_common.h"
 #include "wdf_asym.h"
@@ -56,19 +56,72 @@ AsymBwdWs asym_bwd_ws(void* ws, int64_t B, int K)
 }
 
 // [records double K x 15 x B][per-wave partials double waves x 8][zwarm, zend float K x B each][gate unsigned waves][ticket]
+// (the MSE + ESR step: K x 23 x B and waves x 16)
 struct AsymStepWs { double* rec; double* part; float* zwarm; float* zend; unsigned* gate; unsigned* ticket; size_t bytes; };
-AsymStepWs asym_step_ws(void* ws, int64_t B, int K)
+AsymStepWs asym_step_ws(void* ws, int64_t B, int K, bool esr = false)
 {
     Carver c(ws);
     AsymStepWs w;
-    w.rec = c.take<double>((size_t)K * (size_t)wdf::kAsymStepRec * (size_t)B);
-    w.part = c.take<double>(waves64(B) * 8);
+    w.rec = c.take<double>((size_t)K * (size_t)(esr ? wdf::kAsymStepRecEsr : wdf::kAsymStepRec) * (size_t)B);
+    w.part = c.take<double>(waves64(B) * (size_t)(esr ? wdf::kAsymStepPartEsr : wdf::kAsymStepPart));
     w.zwarm = c.take<float>((size_t)K * (size_t)B);
     w.zend = c.take<float>((size_t)K * (size_t)B);
     w.gate = c.take<unsigned>(waves64(B));
     w.ticket = c.take<unsigned>(2);
     w.bytes = c.off;
     return w;
+}
+
+// The one-pass steps' common part: the checks both share, the chunked launch, the verification, the gated repair launch and
+// the finish.  LOSS = 0: MSE (gscale, out7); LOSS = 1: MSE + ESR (skip, esr).
+template <int LOSS>
+int asym_step_common(const float* x, float* theta6, float fs, int mode, double tol, int max_iter, const float* target, float gscale,
+                     int64_t skip, float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                     float verify_tol, void* ws, void* status, float* out7, const wdf::AsymStepEsrOut& esr, float* m, float* v,
+                     int32_t* step, const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream,
+                     const char* what)
+{
+    int rc = asym_check(B, T, fs, mode);
+    if (rc) return rc;
+    if (mode == WDF_ASYM_OMEGA_F32)
+        return fail(WDF_EINVAL, "mode 0 (the closed form) has no one-pass step: use wdf_clipper_asym_fwd_tp + wdf_clipper_asym_bwd_tp");
+    if ((rc = newton_check(tol, max_iter))) return rc;
+    if (n_chunks < 1 || n_chunks > 65535 || warmup < 0 || !(verify_tol >= 0.0f))
+        return fail(WDF_EINVAL, "n_chunks in 1..65535, warmup >= 0, verify_tol >= 0");
+    if (!aligned8(ws)) return fail(WDF_EINVAL, "ws must be 8-byte aligned");
+    if (z0 && z0 == zT) return fail(WDF_EINVAL, "zT must not alias z0 (every chunk that starts at t = 0 reads z0)");
+    if (LOSS != 0 && (skip < 0 || skip >= T)) return fail(WDF_EINVAL, "skip must be in 0..T-1");
+    if ((rc = adam_check(m, v, step, lr))) return rc;
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
+    const int64_t W = round_up((int64_t)warmup, kUnit);
+    const int64_t Lall = round_up(T, kUnit);                    // one chunk: the repair launch
+    const AsymStepWs w = asym_step_ws(ws, B, g.K, LOSS != 0);
+    const dim3 grid(waves64(B), (unsigned)g.K);
+    hipStream_t s = (hipStream_t)stream;
+    const bool v4 = (T % 4 == 0) && aligned16(x);
+    const wdf::AsymStepAdam adam{m, v, step, lr, lo, hi, beta1, beta2, eps};
+    const auto launch = [&](dim3 gr, const unsigned* gate, int64_t L) {
+        return dispatch([&](auto md, auto vv) {
+            hipLaunchKernelGGL((wdf::clipper_asym_step_kernel<md(), vv(), LOSS>), gr, dim3(64), 0, s, x, (const float*)theta6, fs, target, y, z0, zT,
+                               w.zwarm, w.zend, w.rec, tol, max_iter, (wdf::AsymTpStatus*)status, w.ticket, gate, B, T, L, W, skip);
+        }, Values<int, wdf::kAsymNewton64, wdf::kAsymNewton32>{mode}, Bools{v4});
+    };
+    bool ok;
+    {
+        EventBracket bracket(s);
+        ok = launch(grid, nullptr, g.L);
+    }
+    if (ok && g.K > 1) {
+        // every boundary checked on the device; the waves where one missed run again, exactly, as one chunk
+        hipLaunchKernelGGL(wdf::asym_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, w.zwarm, w.zend, B, (int64_t)g.K, verify_tol, w.gate,
+                           (wdf::AsymTpStatus*)status);
+        ok = launch(dim3(grid.x), w.gate, Lall);
+    }
+    if (!ok) return no_kernel(what);
+    hipLaunchKernelGGL(wdf::clipper_asym_step_finish_kernel<LOSS>, dim3(grid.x), dim3(64), 0, s, (const double*)w.rec,
+                       (const unsigned*)(g.K > 1 ? w.gate : nullptr), w.part, w.ticket, theta6, fs, gscale, out7, esr, adam, B, (int64_t)g.K);
+    return check_launch(what);
 }
 
 }  // namespace
@@ -178,7 +231,7 @@ int wdf_asym_root(const float* a, const float* theta6, float fs, int mode, doubl
     return ok ? check_launch("wdf_asym_root") : no_kernel("wdf_asym_root");
 }
 
-// ---- the one-pass MSE step (wdf_asym_step.h) ------------------------------------------------------------------------------
+// ---- the one-pass MSE and MSE + ESR steps (wdf_asym_step.h) -----------------------------------------------------------------
 size_t wdf_clipper_asym_step_mse_ws_bytes(int64_t B, int n_chunks)
 {
     return (B > 0 && n_chunks > 0) ? asym_step_ws(nullptr, B, n_chunks).bytes : 0;
@@ -190,46 +243,37 @@ int wdf_clipper_asym_step_mse(const float* x, float* theta6, float fs, int mode,
                               const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream)
 {
     if (!x || !theta6 || !target || !y || !ws || !status || !out7) return fail(WDF_EINVAL, "null x/theta6/target/y/ws/status/out7");
-    int rc = asym_check(B, T, fs, mode);
-    if (rc) return rc;
-    if (mode == WDF_ASYM_OMEGA_F32)
-        return fail(WDF_EINVAL, "mode 0 (the closed form) has no one-pass step: use wdf_clipper_asym_fwd_tp + wdf_clipper_asym_bwd_tp");
-    if ((rc = newton_check(tol, max_iter))) return rc;
-    if (n_chunks < 1 || n_chunks > 65535 || warmup < 0 || !(verify_tol >= 0.0f))
-        return fail(WDF_EINVAL, "n_chunks in 1..65535, warmup >= 0, verify_tol >= 0");
-    if (!aligned8(ws)) return fail(WDF_EINVAL, "ws must be 8-byte aligned");
-    if (z0 && z0 == zT) return fail(WDF_EINVAL, "zT must not alias z0 (every chunk that starts at t = 0 reads z0)");
-    if ((rc = adam_check(m, v, step, lr))) return rc;
-    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
-    if ((rc = check_tiles(g, n_chunks, T, kUnit, nullptr))) return rc;
-    const int64_t W = round_up((int64_t)warmup, kUnit);
-    const int64_t Lall = round_up(T, kUnit);                    // one chunk: the repair launch
-    const AsymStepWs w = asym_step_ws(ws, B, g.K);
-    const dim3 grid(waves64(B), (unsigned)g.K);
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = (T % 4 == 0) && aligned16(x);
-    const wdf::AsymStepAdam adam{m, v, step, lr, lo, hi, beta1, beta2, eps};
-    const auto launch = [&](dim3 gr, const unsigned* gate, int64_t L) {
-        return dispatch([&](auto md, auto vv) {
-            hipLaunchKernelGGL((wdf::clipper_asym_step_kernel<md(), vv()>), gr, dim3(64), 0, s, x, (const float*)theta6, fs, target, y, z0, zT,
-                               w.zwarm, w.zend, w.rec, tol, max_iter, (wdf::AsymTpStatus*)status, w.ticket, gate, B, T, L, W);
-        }, Values<int, wdf::kAsymNewton64, wdf::kAsymNewton32>{mode}, Bools{v4});
-    };
-    bool ok;
-    {
-        EventBracket bracket(s);
-        ok = launch(grid, nullptr, g.L);
-    }
-    if (ok && g.K > 1) {
-        // every boundary checked on the device; the waves where one missed run again, exactly, as one chunk
-        hipLaunchKernelGGL(wdf::asym_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, w.zwarm, w.zend, B, (int64_t)g.K, verify_tol, w.gate,
-                           (wdf::AsymTpStatus*)status);
-        ok = launch(dim3(grid.x), w.gate, Lall);
-    }
-    if (!ok) return no_kernel("wdf_clipper_asym_step_mse");
-    hipLaunchKernelGGL(wdf::clipper_asym_step_finish_kernel, dim3(grid.x), dim3(64), 0, s, (const double*)w.rec,
-                       (const unsigned*)(g.K > 1 ? w.gate : nullptr), w.part, w.ticket, theta6, fs, gscale, out7, adam, B, (int64_t)g.K);
-    return check_launch("wdf_clipper_asym_step_mse");
+    return asym_step_common<0>(x, theta6, fs, mode, tol, max_iter, target, gscale, 0, y, z0, zT, B, T, n_chunks, warmup, verify_tol, ws,
+                               status, out7, wdf::AsymStepEsrOut{0.0, 0.0, nullptr, nullptr, nullptr}, m, v, step, lr, beta1, beta2, eps,
+                               lo, hi, stream, "wdf_clipper_asym_step_mse");
+}
+
+size_t wdf_clipper_asym_step_esr_ws_bytes(int64_t B, int n_chunks)
+{
+    return (B > 0 && n_chunks > 0) ? asym_step_ws(nullptr, B, n_chunks, true).bytes : 0;
+}
+
+int wdf_clipper_asym_step_esr(const float* x, float* theta6, float fs, int mode, double tol, int max_iter, const float* target,
+                              double n_global, double eps_energy, int64_t skip, float* y, const float* z0, float* zT, int64_t B,
+                              int64_t T, int n_chunks, int warmup, float verify_tol, void* ws, void* status, float* sums14,
+                              float* gtheta6, float* loss3, float* m, float* v, int32_t* step, const float* lr, float beta1,
+                              float beta2, float eps, const float* lo, const float* hi, void* stream)
+{
+    if (!x || !theta6 || !target || !y || !ws || !status || !sums14) return fail(WDF_EINVAL, "null x/theta6/target/y/ws/status/sums14");
+    if (!(n_global > 0.0)) return fail(WDF_EINVAL, "n_global must be positive");
+    if (!(eps_energy >= 0.0)) return fail(WDF_EINVAL, "eps_energy must not be negative");
+    if (m && !gtheta6) return fail(WDF_EINVAL, "Adam: the update reads the gradient from gtheta6");
+    return asym_step_common<1>(x, theta6, fs, mode, tol, max_iter, target, 0.0f, skip, y, z0, zT, B, T, n_chunks, warmup, verify_tol, ws,
+                               status, nullptr, wdf::AsymStepEsrOut{n_global, eps_energy, sums14, gtheta6, loss3}, m, v, step, lr, beta1,
+                               beta2, eps, lo, hi, stream, "wdf_clipper_asym_step_esr");
+}
+
+int wdf_asym_esr_finish(const float* sums14, double n_global, double eps_energy, float* gtheta6, float* loss3, void* stream)
+{
+    if (!sums14 || !gtheta6 || !(n_global > 0.0) || !(eps_energy >= 0.0))
+        return fail(WDF_EINVAL, "wdf_asym_esr_finish: null sums14/gtheta6, n_global <= 0 or eps_energy < 0");
+    hipLaunchKernelGGL(wdf::asym_esr_finish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sums14, n_global, eps_energy, gtheta6, loss3);
+    return check_launch("wdf_asym_esr_finish");
 }
 
 }  // extern "C"

@@ -13,8 +13,8 @@ New surface (not in the reference):
       protocol Toms917DiodePair.h:21-59) with trainable Is and nVt;
   AsymDiodePair(next, Is_up, Is_down, Vt=25.85e-3, nDiodes_up=1, nDiodes_down=1, trainable=False, solver="newton_f32")
       two DIFFERENT antiparallel diodes, the exact Shockley pair solved by Newton (csrc/wdf_asym.h); a root for
-      Circuit on the diode-clipper tree, trainable Is and nVt per diode; with a Newton solver Circuit.mse is a one-pass
-      training step (forward, loss and six gradients in one sweep: csrc/wdf_asym_step.h);
+      Circuit on the diode-clipper tree, trainable Is and nVt per diode; with a Newton solver Circuit.mse and
+      Circuit.mse_esr are one-pass training steps (forward, loss and six gradients in one sweep: csrc/wdf_asym_step.h);
   Circuit(top, root, probe) / run(...) / Circuit.mse(x, target)
       the fast tier: lowers the WHOLE per-sample loop the scripts own (lpf.py:39-46,
       clipper_pot.py:113-124) to one HIP kernel launch, and its tape.gradient to one reverse
@@ -264,8 +264,9 @@ class AsymDiodePair(_Element):
     The root runs inside tf_wdf.Circuit on the diode-clipper tree (Parallel(ResistiveVoltageSource, Capacitor), probe = the
     capacitor): the fused loop takes the source's R and the capacitor's C, not a port resistance, so there is no
     element-wise reflected().  Circuit.mse(x, target) with a Newton solver runs forward, loss and the gradients of all six
-    Variables in ONE pass over the data (wdf_clipper_asym_step_mse: no stash, no reverse sweep); "omega_f32", mse_esr()
-    and circ(x) keep the forward kernel and the reverse sweep.'''
+    Variables in ONE pass over the data (wdf_clipper_asym_step_mse: no stash, no reverse sweep), and so does
+    Circuit.mse_esr(x, target, skip) for the scripts' MSE + ESR loss past `skip` samples (wdf_clipper_asym_step_esr), with or
+    without z0 / carry_state; "omega_f32" and circ(x) keep the forward kernel and the reverse sweep.'''
 
     SOLVERS = {"omega_f32": 0, "newton_f64": 1, "newton_f32": 2}          # wdf_hip.binding.ASYM_*
 

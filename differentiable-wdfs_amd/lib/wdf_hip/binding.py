@@ -166,6 +166,13 @@ def lib():
     L.wdf_clipper_asym_step_mse.restype = ci
     L.wdf_clipper_asym_step_mse.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, cf, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, fp,
                                             fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
+    L.wdf_clipper_asym_step_esr_ws_bytes.restype = C.c_size_t
+    L.wdf_clipper_asym_step_esr_ws_bytes.argtypes = [i64, ci]
+    L.wdf_clipper_asym_step_esr.restype = ci
+    L.wdf_clipper_asym_step_esr.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, C.c_double, C.c_double, i64, fp, fp, fp, i64, i64, ci, ci,
+                                            cf, vp, vp, fp, fp, fp, fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
+    L.wdf_asym_esr_finish.restype = ci
+    L.wdf_asym_esr_finish.argtypes = [fp, C.c_double, C.c_double, fp, fp, vp]
     L.wdf_asym_root.restype = ci
     L.wdf_asym_root.argtypes = [fp, fp, cf, ci, C.c_double, ci, vp, i64, vp]
     L.wdf_mlp_weight_count.restype = ci
@@ -300,6 +307,7 @@ EXPORTED_SYMBOLS = (
     "wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp_ws_bytes", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_ws_bytes", "wdf_clipper_asym_bwd",
     "wdf_clipper_asym_bwd_tp_ws_bytes", "wdf_clipper_asym_bwd_tp", "wdf_asym_root",
     "wdf_clipper_asym_step_mse_ws_bytes", "wdf_clipper_asym_step_mse",
+    "wdf_clipper_asym_step_esr_ws_bytes", "wdf_clipper_asym_step_esr", "wdf_asym_esr_finish",
     "wdf_ss_dyn_row_len", "wdf_ss_dyn_fwd", "wdf_ss_dyn_bwd_ws_bytes", "wdf_ss_dyn_bwd", "wdf_clipper_mlp_wgrad_matrix_core_chunks",
     "wdf_ss_dyn_fwd_tp_ws_bytes", "wdf_ss_dyn_fwd_tp", "wdf_ss_dyn_bwd_tp_ws_bytes", "wdf_ss_dyn_bwd_tp",
     "wdf_ss_dyn_rows", "wdf_ss_dyn_rows_bwd_ws_bytes", "wdf_ss_dyn_rows_bwd",
@@ -1135,6 +1143,84 @@ def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup,
         None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
     _check(rc, "wdf_clipper_asym_step_mse")
     return y, zT, out7, status
+
+
+def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup, tol=1e-12, max_iter=50,
+                          verify_tol=1e-6, y=None, z0=None, want_zT=False, ws=None, status=None, sums14=None, gtheta6=None, loss3=None,
+                          finish=True, opt=None):
+    """The MSE + ESR training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_esr):
+    loss = S/n + sqrt(S / (E + eps_energy) / n) on the rows past `skip`, S = sum (y - target)^2, E = sum y^2, n = n_global.
+    x [B,T] and target [T,B] read once, y written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is
+    rounded like asym_chunks(); y, ws, status, sums14, gtheta6, loss3 can be preallocated.  finish=True: a single rank -- the
+    kernel forms gtheta6 = dloss/d{Is_up, nVt_up, Is_down, nVt_down, R, C} and loss3 = {mse, esr, mse + esr} itself, and
+    opt (a binding.Adam(6, ...)) updates theta6 in the same last launch.  finish=False: one shard of several -- only sums14 =
+    {S, E, gP[6], gQ[6]} of this call comes back (gtheta6 and loss3 are None): all-reduce it and call asym_esr_finish().
+    -> y [T,B], zT [B] | None, sums14, gtheta6, loss3, status (int32[4]; read with mlp_tp_status())."""
+    require_gpu()
+    x, theta6, target, z0 = _f32_dev(x, "x"), _f32_dev(theta6, "theta6"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
+    if theta6.numel() != 6:
+        raise WdfHipError("theta6 must hold {Is_up, nVt_up, Is_down, nVt_down, R, C}")
+    B, T = x.shape
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if z0 is not None and z0.numel() != B:
+        raise WdfHipError(f"z0 must hold one state per sequence ({B})")
+    if opt is not None and (opt.n != 6 or not finish):
+        raise WdfHipError("clipper_asym_step_esr: the optimizer holds {Is_up, nVt_up, Is_down, nVt_down, R, C} and needs finish=True")
+    K = asym_chunks(T, n_chunks)
+    if y is None:
+        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
+    elif tuple(_f32_dev(y, "y").shape) != (T, B):
+        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
+    need = lib().wdf_clipper_asym_step_esr_ws_bytes(B, K)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
+    if status is None:
+        status = torch.empty((4,), dtype=torch.int32, device=x.device)
+    if sums14 is None:
+        sums14 = torch.empty((14,), dtype=torch.float32, device=x.device)
+    elif _f32_dev(sums14, "sums14").numel() != 14:
+        raise WdfHipError("sums14 must hold {S, E, gP[6], gQ[6]}")
+    if not finish:
+        gtheta6 = loss3 = None
+    else:
+        if gtheta6 is None:
+            gtheta6 = torch.empty((6,), dtype=torch.float32, device=x.device)
+        elif _f32_dev(gtheta6, "gtheta6").numel() != 6:
+            raise WdfHipError("gtheta6 must hold six gradients")
+        if loss3 is None:
+            loss3 = torch.empty((3,), dtype=torch.float32, device=x.device)
+        elif _f32_dev(loss3, "loss3").numel() != 3:
+            raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
+    o = opt
+    rc = lib().wdf_clipper_asym_step_esr(
+        _ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(n_global), float(eps_energy),
+        int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(sums14),
+        _ptr(gtheta6), _ptr(loss3),
+        *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
+        0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
+        None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
+    _check(rc, "wdf_clipper_asym_step_esr")
+    return y, zT, sums14, gtheta6, loss3, status
+
+
+def asym_esr_finish(sums14, n_global, eps_energy, gtheta6=None, loss3=None):
+    """Several ranks: sums14 = {S, E, gP[6], gQ[6]} summed over the ranks -> (gtheta6, loss3 = {mse, esr, mse + esr}), the
+    global loss and its gradient (wdf_asym_esr_finish: the single-rank step's own formulas)."""
+    require_gpu()
+    sums14 = _f32_dev(sums14, "sums14")
+    if sums14.numel() != 14:
+        raise WdfHipError("sums14 must hold {S, E, gP[6], gQ[6]}")
+    if gtheta6 is None:
+        gtheta6 = torch.empty((6,), dtype=torch.float32, device=sums14.device)
+    if loss3 is None:
+        loss3 = torch.empty((3,), dtype=torch.float32, device=sums14.device)
+    _check(lib().wdf_asym_esr_finish(_ptr(sums14), float(n_global), float(eps_energy), _ptr(gtheta6), _ptr(loss3), _stream()),
+           "wdf_asym_esr_finish")
+    return gtheta6, loss3
 
 
 def asym_root(a, theta6, fs, mode, tol=1e-12, max_iter=50):

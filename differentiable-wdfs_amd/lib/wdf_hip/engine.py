@@ -331,6 +331,97 @@ def clipper_asym_mse(theta6, x, target, fs, tp=None, mode=None, z0=None, return_
     return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state))
 
 
+class AsymEsrStep:
+    """The MSE + ESR training step of the two-different-diode clipper in one pass over the data (csrc/wdf_asym_step.h,
+    binding.clipper_asym_step_esr): loss = S/n + sqrt(S / (E + eps) / n) on the rows past `skip` (clipper_pot.py:146-156,177,
+    232,248), S = sum (y - target)^2, E = sum y^2, n = n_global (default: the rows counted x B).  Buffers are allocated once;
+    step_fused() returns device tensors (loss3[3] = {mse, esr, mse + esr}, gtheta6[6] = d(mse + esr)/dtheta6) and nothing
+    synchronises; self.sums = {S, E, gP[6], gQ[6]} of this batch is what several ranks all-reduce (finish=False leaves loss3
+    and gtheta6 alone: binding.asym_esr_finish forms them from the global sums).  tp, mode: as AsymMseStep."""
+
+    def __init__(self, B, T, fs, tp, device, mode=None, skip=0, n_global=None, eps_energy=None, tol=1.0e-12, max_iter=50):
+        self.mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
+        if self.mode not in (binding.ASYM_NEWTON_F32, binding.ASYM_NEWTON_F64):
+            raise binding.WdfHipError(f"AsymEsrStep: mode {self.mode} has no one-pass step (the Newton modes have)")
+        self.B, self.T, self.fs, self.tp, self.skip = int(B), int(T), float(fs), tp, int(skip)
+        if not 0 <= self.skip < self.T:
+            raise binding.WdfHipError(f"AsymEsrStep: skip must be in 0..T-1 = 0..{self.T - 1}, got {self.skip}")
+        self.tol, self.max_iter = float(tol), int(max_iter)
+        self.n_global = float(n_global if n_global is not None else self.B * (self.T - self.skip))
+        self.eps_energy = float(torch.finfo(torch.float64).eps if eps_energy is None else eps_energy)
+        k, self.warmup, self.verify_tol = (tp.k_fwd, tp.warmup, tp.tol) if tp is not None else (1, 0, 1.0e-6)
+        self.k = binding.asym_chunks(self.T, k)
+        self.ws = torch.empty((binding.lib().wdf_clipper_asym_step_esr_ws_bytes(self.B, self.k),), dtype=torch.uint8, device=device)
+        self.status = torch.zeros((4,), dtype=torch.int32, device=device)
+        self.sums = torch.zeros((14,), dtype=torch.float32, device=device)     # {S, E, gP[6], gQ[6]}
+        self.gtheta = torch.zeros((6,), dtype=torch.float32, device=device)
+        self.loss3 = torch.zeros((3,), dtype=torch.float32, device=device)     # {mse, esr, mse + esr}
+        self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=device)
+        self.zT = None
+
+    def step_fused(self, theta6, x, target, adam=None, z0=None, want_zT=False, finish=True):
+        """adam: a binding.Adam(6, ...) to update theta6 in the step's own last launch; otherwise the caller applies its
+        optimizer to self.gtheta.  z0 [B]: the state the call starts from, a constant of it; want_zT: self.zT <- the state
+        it ends in.  Fills self.y, self.sums, self.status and -- finish -- self.loss3, self.gtheta."""
+        _, self.zT, _, _, _, _ = binding.clipper_asym_step_esr(
+            x, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy, self.skip, self.k, self.warmup, tol=self.tol,
+            max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws, status=self.status,
+            sums14=self.sums, gtheta6=self.gtheta, loss3=self.loss3, finish=finish, opt=adam)
+        return self.loss3, self.gtheta
+
+
+class _ClipperAsymEsrFn(torch.autograd.Function):
+    """MSE + ESR of clipper_asym(theta6, x) against target past `skip` as the one-pass step (AsymEsrStep.step_fused; one
+    stepper per shape, buffers reused); backward only scales the stored gradient.  keep: -> (loss, y [T,B], zT [B]), the
+    call's own output and final state, detached; otherwise the loss alone (y stays in the stepper's buffer: no copy)."""
+    _steppers = {}
+
+    @staticmethod
+    def stepper(B, T, fs, tp, mode, skip, device):
+        key = (B, T, float(fs), tp, mode, int(skip), device)
+        st = _ClipperAsymEsrFn._steppers.get(key)
+        if st is None:
+            if len(_ClipperAsymEsrFn._steppers) > 8:
+                _ClipperAsymEsrFn._steppers.clear()
+            st = _ClipperAsymEsrFn._steppers[key] = AsymEsrStep(B, T, fs, tp, device, mode=mode, skip=skip)
+        return st
+
+    @staticmethod
+    def forward(ctx, theta6, x, target, fs, skip, tp, mode, z0, keep):
+        B, T = x.shape
+        st = _ClipperAsymEsrFn.stepper(B, T, fs, tp, mode, skip, x.device)
+        LAST_TP_STATUS["status"] = st.status
+        st.step_fused(theta6.detach().contiguous(), x, target, z0=z0, want_zT=keep)
+        ctx.save_for_backward(st.gtheta.clone())
+        loss = st.loss3[2].clone()
+        if not keep:
+            return loss
+        y, zT = st.y.clone(), st.zT        # (the stepper's y is overwritten by the next call of this shape)
+        ctx.mark_non_differentiable(y, zT)
+        return loss, y, zT
+
+    @staticmethod
+    def backward(ctx, gl, *_):
+        (g,) = ctx.saved_tensors
+        return gl * g, None, None, None, None, None, None, None, None
+
+
+def clipper_asym_mse_esr(theta6, x, target, fs, skip=0, tp=None, mode=None, z0=None, return_state=False):
+    """The scripts' training loss (clipper_pot.py:146-156,177: mean((y - t)^2) + sqrt(sum((y - t)^2) / (sum(y^2) + eps) / n)
+    on the rows past `skip`) of the two-different-diode clipper's output against target [T,B], differentiable w.r.t.
+    theta6 = {Is_up, nVt_up, Is_down, nVt_down, R, C} (float32[6] on the device), as ONE pass over the data
+    (wdf_clipper_asym_step_esr): no stash, no torch reductions, no reverse sweep.  mode: binding.ASYM_NEWTON_F32
+    (default) or binding.ASYM_NEWTON_F64.  tp: a TpPlan (plan_asym_time_parallel) or None for one chunk.
+    z0 [B]: the state the loop starts from, a constant of the call.
+    -> loss, or (loss, y [T,B], zT [B]) with return_state: the call's output and final state, detached."""
+    mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
+    if z0 is not None:
+        z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        if z0.numel() != x.shape[0]:
+            raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    return _ClipperAsymEsrFn.apply(theta6, x, target, float(fs), int(skip), tp, mode, z0, bool(return_state))
+
+
 class MseStep:
     """Fused training step for the mean-squared-error loss (lpf.py:78, clipper_pot.py:176):
     forward, loss and reverse sweep in two kernel launches + three tiny ones, all buffers

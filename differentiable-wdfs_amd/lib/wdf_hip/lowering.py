@@ -829,12 +829,19 @@ class Circuit:
         mean((y - t)^2) + sqrt(sum((y - t)^2) / (sum(y^2) + eps) / n)  -- the scripts call esr_loss(outs, train_Y) on a
         function declared (target, predicted), so the normalising energy is the OUTPUT's.  target: [T,B] like the output.
         A resident diode-pair clipper (to_device()) evaluates loss and gradient in one pass over the data
-        (wdf_clipper_step_esr_tp); anything else composes it from the forward.
+        (wdf_clipper_step_esr_tp), and so does the clipper under an AsymDiodePair root with a Newton solver
+        (wdf_clipper_asym_step_esr: forward, both loss sums and the six gradients in one sweep, with or without z0 /
+        carry_state; `circ.last_output` is then the step's own y buffer, valid until the next call of the same shape, and a
+        tensor of its own on stateful calls); anything else composes it from the forward.
         z0 / carry_state: as in mse() -- the state the call starts from, or the one the previous carry_state call ended in
         (`circ.last_state`); composed from __call__(x, z0, return_state) (the resident one-pass steps start from zero state,
         which is what clipper_pot.py:110-111 does before every forward)."""
         binding.require_gpu()
         stateful = (z0 is not None or carry_state) and self.ns > 0
+        if self.root_kind == "AsymDiodePair" and self.root.mode != binding.ASYM_OMEGA_F32 and 0 <= int(skip) < int(np.shape(x)[1]):
+            if carry_state and z0 is None:
+                z0 = getattr(self, "last_state", None)
+            return self._mse_esr_clipper_asym(x, target, int(skip), z0, stateful)      # the Newton solvers: the one-pass step
         if stateful:
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
@@ -1269,6 +1276,40 @@ class Circuit:
         if not stateful:
             return engine.clipper_asym_mse(theta6, xv, tgt, float(cap.FS), tp=tp, mode=dp.mode).as_subclass(tf.Tensor)
         loss, y, zT = engine.clipper_asym_mse(theta6, xv, tgt, float(cap.FS), tp=tp, mode=dp.mode, z0=z0t, return_state=True)
+        self.last_state, self.last_output = zT.reshape(1, -1), y.as_subclass(tf.Tensor)
+        return loss.as_subclass(tf.Tensor)
+
+    def _mse_esr_clipper_asym(self, x, target, skip, z0, stateful):
+        """mse_esr() on the clipper tree under an AsymDiodePair root with a Newton solver: forward, the loss sums S and E past
+        `skip` and the six gradients in one pass over the data (engine.clipper_asym_mse_esr) -- no stash, no torch
+        reductions, no reverse sweep.  State in and out as _mse_clipper_asym handles it."""
+        from . import engine
+        anchor = x if isinstance(x, torch.Tensor) else None
+        x = torch.as_tensor(x).as_subclass(torch.Tensor)
+        x = (x if x.is_cuda else x.cuda()).float()
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        if x.dim() != 3 or x.shape[2] != 1:
+            raise binding.WdfHipError(f"x must be [B,T,1] (or [B,T] for one channel), got {tuple(x.shape)}")
+        dp, vs, cap = self.root, self.top.P1, self.top.P2
+        Rv = vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R))
+        parts = [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, Rv, cap.C]
+        theta6 = self._theta(parts, x.device)
+        xv, _ = engine.split_channels(x, False, anchor=anchor)
+        B, T = xv.shape
+        tgt = torch.as_tensor(target).as_subclass(torch.Tensor).to(x.device).float().reshape(T, B).contiguous()
+        tp = self.time_parallel
+        if tp == "auto":
+            tp = engine.plan_asym_time_parallel(B, T, float(parts[4]), float(parts[5]), float(cap.FS))
+        elif not isinstance(tp, engine.TpPlan):
+            tp = None
+        z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor)
+        if not stateful:
+            loss = engine.clipper_asym_mse_esr(theta6, xv, tgt, float(cap.FS), skip=skip, tp=tp, mode=dp.mode)
+            self.last_output = engine._ClipperAsymEsrFn.stepper(B, T, float(cap.FS), tp, dp.mode, skip, xv.device).y.as_subclass(tf.Tensor)
+            return loss.as_subclass(tf.Tensor)
+        loss, y, zT = engine.clipper_asym_mse_esr(theta6, xv, tgt, float(cap.FS), skip=skip, tp=tp, mode=dp.mode, z0=z0t,
+                                                  return_state=True)
         self.last_state, self.last_output = zT.reshape(1, -1), y.as_subclass(tf.Tensor)
         return loss.as_subclass(tf.Tensor)
 

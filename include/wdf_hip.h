@@ -618,6 +618,24 @@ int wdf_clipper_asym_step_mse(const float* x, float* theta6, float fs, int mode,
                               float verify_tol, void* ws, void* status, float* out7, float* m, float* v, int32_t* step,
                               const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream);
 
+/* The same one-pass step for the scripts' training loss, MSE + ESR on the samples past `skip` (clipper_pot.py:146-156,177,232,248):
+ * loss = S/n + sqrt(S / (E + eps_energy) / n), S = sum (y - target)^2, E = sum y^2 over the rows t >= skip, n = n_global.
+ * dLoss/dy = ga (y - target) + gb y needs the GLOBAL S and E, so the pass carries both tangent-weighted sums and hands back
+ * sums14 (device float[14]) = {S, E, gP[6], gQ[6]} of this call's batch (gP = d(S/2)/dtheta6, gQ = d(E/2)/dtheta6, theta6 order):
+ * with several ranks all-reduce the fourteen floats and call wdf_asym_esr_finish (-> gtheta6 = ga gP + gb gQ and
+ * loss3 = {mse, esr, mse + esr}), then wdf_adam_step.  With gtheta6 != NULL the kernel finishes the step itself as a single
+ * rank (same formulas; loss3 optional; Adam when m != NULL, which needs gtheta6).  Rows before skip (0 <= skip < T, anywhere in a
+ * chunk) count for nothing; state and y run over them as over any row.  Modes, chunks, verification, status, z0 / zT as
+ * wdf_clipper_asym_step_mse.  ws: wdf_clipper_asym_step_esr_ws_bytes bytes (larger than the MSE step's: 23 doubles per chunk and
+ * sequence), 8-byte aligned, no initialisation needed.  An addition to ABI 6: no existing signature changed. */
+size_t wdf_clipper_asym_step_esr_ws_bytes(int64_t B, int n_chunks);
+int wdf_clipper_asym_step_esr(const float* x, float* theta6, float fs, int mode, double tol, int max_iter, const float* target,
+                              double n_global, double eps_energy, int64_t skip, float* y, const float* z0, float* zT, int64_t B,
+                              int64_t T, int n_chunks, int warmup, float verify_tol, void* ws, void* status, float* sums14,
+                              float* gtheta6, float* loss3, float* m, float* v, int32_t* step, const float* lr, float beta1,
+                              float beta2, float eps, const float* lo, const float* hi, void* stream);
+int wdf_asym_esr_finish(const float* sums14, double n_global, double eps_energy, float* gtheta6, float* loss3, void* stream);
+
 /* Element-wise diode-pair root and Wright omega on device arrays (n elements): the
  * building blocks above, exposed for parity tests against diode_pretraining.py:39-60 /
  * toms917.cpp.  R_port is the port resistance seen by the root (P1.R).
