@@ -57,6 +57,34 @@ __device__ __forceinline__ AsymConsts asym_load(const float* __restrict__ th, fl
     return c;
 }
 
+// One pot resistance per SEQUENCE (clipper_pot.py's recordings: dataimport.py:96): the same formulas with R = rseq[b] in place
+// of theta6[4], which is not read.  p, Rp, l1, l2 are then per-lane values (VGPRs), evaluated once per lane ahead of the time
+// loop: nothing about the pot is evaluated per step -- no reciprocal, no logarithm.  The kernels below take it as a
+// compile-time flag RSEQ (last template parameter, default false) and rseq [B] (last argument; unused when RSEQ is false): the
+// RSEQ = false instantiations are the code they were before the flag existed (tools/lib_digest.py: the same sha256 per kernel;
+// the flag and the argument show in the mangled names).
+__device__ __forceinline__ AsymConsts asym_load_seq(const float* __restrict__ th, float fs, float R)
+{
+    AsymConsts c;
+    c.Is1 = th[0]; c.V1 = th[1]; c.Is2 = th[2]; c.V2 = th[3];
+    const float C = th[5];
+    const float G1 = 1.0f / R, G2 = C * (2.0f * fs), G = G1 + G2;
+    c.Rp = 1.0f / G;
+    c.p = G1 / G;
+    c.l1 = logf(c.Rp * c.Is1 / c.V1);
+    c.l2 = logf(c.Rp * c.Is2 / c.V2);
+    return c;
+}
+
+// The chain rule Rp, p -> C of ONE sequence's pair of sums under its own pot R_b: G1 = 1/R_b, G2 = 2 C fs, Rp = 1/(G1 + G2),
+// p = G1 Rp, gC = -2 fs (S_Rp Rp^2 + S_p p Rp) -- clipper_asym_grad_reduce_kernel's formula for C, per lane.  The pot is
+// data, not a parameter: it has no gradient.
+__device__ __forceinline__ double asym_seq_chain_rule(double SRp, double Sp, double R, double C, float fs)
+{
+    const double G1 = 1.0 / R, G2 = C * (2.0 * (double)fs), Rp = 1.0 / (G1 + G2), p = G1 * Rp;
+    return -2.0 * (double)fs * (SRp * Rp * Rp + Sp * p * Rp);
+}
+
 __device__ __forceinline__ float asym_omega_root(const AsymConsts& c, float a)
 {
     const float lam = vsign(a);
@@ -258,20 +286,21 @@ struct AsymStep<kAsymNewton32> {
 };
 
 // x [B][T] -> y [T][B]; theta6 = {Is1, V1, Is2, V2, R, C}; iters_out: optional int64[gridDim.x]
-template <int MODE, bool VEC4>
+template <int MODE, bool VEC4, bool RSEQ = false>
 __global__ __launch_bounds__(64) void clipper_asym_fwd_kernel(const float* __restrict__ x,
                                                               const float* __restrict__ theta6, float fs,
                                                               float* __restrict__ y, float* __restrict__ zstash,
                                                               const float* __restrict__ z0,
                                                               float* __restrict__ zT, double tol, int max_iter,
                                                               long long* __restrict__ iters_out, int64_t B, int64_t T,
-                                                              const unsigned* __restrict__ gate = nullptr)
+                                                              const unsigned* __restrict__ gate = nullptr,
+                                                              const float* __restrict__ rseq = nullptr)
 {
     using S = typename AsymStep<MODE>::S;
     if (gate != nullptr && gate[blockIdx.x] == 0u) return;    // sequential re-run behind a time-parallel pass: flagged waves only
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t b = b_raw < B ? b_raw : B - 1;
-    const AsymConsts c = asym_load(theta6, fs);
+    const AsymConsts c = RSEQ ? asym_load_seq(theta6, fs, rseq[b]) : asym_load(theta6, fs);
     float* __restrict__ yp = y + b;
     float* __restrict__ zp = zstash ? zstash + b : nullptr;   // state BEFORE each step, for clipper_asym_bwd_kernel
     int iters = 0;
@@ -320,13 +349,14 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_kernel(const float* __res
 // launched GATED and re-runs exactly those waves.  L and W are multiples of 8.
 struct AsymTpStatus { int n_bad; float max_miss; int gated_waves; int pad; };
 
-template <int MODE>
+template <int MODE, bool RSEQ = false>
 __global__ __launch_bounds__(64) void clipper_asym_fwd_tp_kernel(const float* __restrict__ x, const float* __restrict__ theta6,
                                                                  float fs, float* __restrict__ y, float* __restrict__ zstash,
                                                                  const float* __restrict__ z0, float* __restrict__ zT,
                                                                  float* __restrict__ zwarm, float* __restrict__ zend, double tol,
                                                                  int max_iter, AsymTpStatus* __restrict__ status, int64_t B,
-                                                                 int64_t T, int64_t L, int64_t W)
+                                                                 int64_t T, int64_t L, int64_t W,
+                                                                 const float* __restrict__ rseq = nullptr)
 {
     using S = typename AsymStep<MODE>::S;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *status = AsymTpStatus{0, 0.0f, 0, 0};   // the verify kernel adds
@@ -335,7 +365,7 @@ __global__ __launch_bounds__(64) void clipper_asym_fwd_tp_kernel(const float* __
     const int64_t k = blockIdx.y;
     const int64_t t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
     const int64_t tw = (k > 0 && t0 > W) ? t0 - W : 0;
-    const AsymConsts c = asym_load(theta6, fs);
+    const AsymConsts c = RSEQ ? asym_load_seq(theta6, fs, rseq[b]) : asym_load(theta6, fs);
     const float* __restrict__ xp = x + b * T;
     int iters = 0;
     S z = (tw == 0 && z0) ? (S)z0[b] : (S)0;
@@ -453,6 +483,8 @@ static __global__ __launch_bounds__(64) void clipper_asym_bwd_kernel(const float
 }
 
 // fixed-order sum over the waves + chain rule Rp = 1/(G1+G2), p = G1 Rp (G1 = 1/R, G2 = 2 C fs) -> gtheta6
+// RSEQ: the combine kernel has applied the chain rule per sequence (slot 5 holds dL/dC, slot 4 zero): nothing is left to do
+template <bool RSEQ = false>
 static __global__ __launch_bounds__(256) void clipper_asym_grad_reduce_kernel(const double* __restrict__ ws, int nparts,
                                                                               const float* __restrict__ theta6, float fs,
                                                                               float* __restrict__ gtheta6)
@@ -472,13 +504,20 @@ static __global__ __launch_bounds__(256) void clipper_asym_grad_reduce_kernel(co
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const double R = theta6[4], C = theta6[5];
-        const double G1 = 1.0 / R, G2 = C * (2.0 * (double)fs), Rp = 1.0 / (G1 + G2), p = G1 * Rp;
-        const double SRp = sh[0][4], Sp = sh[0][5];
+        if constexpr (RSEQ) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) gtheta6[q] = (float)sh[0][q];
-        gtheta6[4] = (float)(SRp * Rp * Rp * G1 * G1 - Sp * G1 * G1 * Rp * (1.0 - p));
-        gtheta6[5] = (float)(-2.0 * (double)fs * (SRp * Rp * Rp + Sp * p * Rp));
+            for (int q = 0; q < 4; ++q) gtheta6[q] = (float)sh[0][q];
+            gtheta6[4] = 0.0f;
+            gtheta6[5] = (float)sh[0][5];
+        } else {
+            const double R = theta6[4], C = theta6[5];
+            const double G1 = 1.0 / R, G2 = C * (2.0 * (double)fs), Rp = 1.0 / (G1 + G2), p = G1 * Rp;
+            const double SRp = sh[0][4], Sp = sh[0][5];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) gtheta6[q] = (float)sh[0][q];
+            gtheta6[4] = (float)(SRp * Rp * Rp * G1 * G1 - Sp * G1 * G1 * Rp * (1.0 - p));
+            gtheta6[5] = (float)(-2.0 * (double)fs * (SRp * Rp * Rp + Sp * p * Rp));
+        }
     }
 }
 
@@ -520,17 +559,18 @@ __device__ __forceinline__ void asym_newton_partials(const AsymConsts& c, float 
     cf[4] = k2 * fmaf(c.Is1, e1 - 1.0f, -c.Is2 * (e2 - 1.0f));
 }
 
-template <bool NEWTON, bool VEC4>
+template <bool NEWTON, bool VEC4, bool RSEQ = false>
 __global__ __launch_bounds__(64) void clipper_asym_bwd_tp_kernel(const float* __restrict__ x, const float* __restrict__ theta6,
                                                                  float fs, const float* __restrict__ zstash,
                                                                  const float* __restrict__ zT, const float* __restrict__ gy,
-                                                                 double* __restrict__ rec, int64_t B, int64_t T, int64_t L)
+                                                                 double* __restrict__ rec, int64_t B, int64_t T, int64_t L,
+                                                                 const float* __restrict__ rseq = nullptr)
 {
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t b = b_raw < B ? b_raw : B - 1;
     const int64_t k = blockIdx.y;
     const int64_t t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
-    const AsymConsts c = asym_load(theta6, fs);
+    const AsymConsts c = RSEQ ? asym_load_seq(theta6, fs, rseq[b]) : asym_load(theta6, fs);
     const double p = c.p;
     double m = 1.0, g0 = 0.0;
     double al[6] = {0, 0, 0, 0, 0, 0}, be[6] = {0, 0, 0, 0, 0, 0};
@@ -616,9 +656,13 @@ __global__ __launch_bounds__(64) void clipper_asym_bwd_tp_kernel(const float* __
 
 // one lane per sequence: the K records last to first (Lam = gzT or 0 enters the last chunk), then the wave's sums ->
 // ws[wave][8] (clipper_asym_grad_reduce_kernel finishes); gz0 (optional): dL/dz0
+// RSEQ: the sums over sequences of S_Rp and S_p mean nothing when Rp and p differ from lane to lane, so every lane applies the
+// chain rule with its own pot (asym_seq_chain_rule) ahead of the wave sum: slot 5 <- dL/dC of this sequence, slot 4 <- 0.
+template <bool RSEQ = false>
 static __global__ __launch_bounds__(64) void clipper_asym_bwd_combine_kernel(const double* __restrict__ rec, const float* __restrict__ gzT,
                                                                              double* __restrict__ ws, float* __restrict__ gz0,
-                                                                             int64_t B, int64_t K)
+                                                                             int64_t B, int64_t K, const float* __restrict__ theta6 = nullptr,
+                                                                             float fs = 0.0f, const float* __restrict__ rseq = nullptr)
 {
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool live = b_raw < B;
@@ -632,6 +676,10 @@ static __global__ __launch_bounds__(64) void clipper_asym_bwd_combine_kernel(con
         lam = fma(r[0], lam, r[B]);
     }
     if (gz0 && live) gz0[b] = (float)lam;
+    if constexpr (RSEQ) {
+        s[5] = asym_seq_chain_rule(s[4], s[5], (double)rseq[b], (double)theta6[5], fs);
+        s[4] = 0.0;
+    }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         double v = live ? s[i] : 0.0;

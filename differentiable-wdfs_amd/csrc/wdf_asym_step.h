@@ -29,6 +29,11 @@
 // in theta-space (the chain rule is linear: applied to gP and gQ separately), which is what several ranks all-reduce, and
 // finishes the step itself as a single rank when asked.
 //
+// One pot resistance per sequence (RSEQ, rseq [B]; wdf_clipper_asym_step_{mse,esr}_rseq): the port constants are the lane's own
+// (asym_load_seq), the tangents and records are unchanged, and the chain rule Rp, p -> C moves from the last wave into every
+// lane of the finish kernel, ahead of the wave sum.  The R component of every gradient is exactly 0 and theta6[4] is never
+// read or written, by Adam either.
+//
 // Precision as the reverse sweep's: partials in fp32 (their inputs are fp32), recurrence and sums in fp64.
 // rec, LOSS = 0: double [K][15][B] = {P, A, S, q[6], beta[6]};
 //      LOSS = 1: double [K][23][B] = {P, A, S, q[6], beta[6], A_Q, E, betaQ[6]} (rows 0..14 as LOSS = 0).
@@ -48,7 +53,9 @@ constexpr int kAsymStepPartEsr = 16;             //                           LO
 // gate == nullptr: the chunked launch, grid = (waves, K); it also clears status and the finish kernel's ticket.
 // gate != nullptr: the repair launch, grid = (waves, 1) with L >= T: flagged waves only.
 // skip: LOSS = 1 only (rows before it count for nothing); anywhere in 0..T-1, inside a block or a later chunk.
-template <int MODE, bool VEC4, int LOSS = 0>
+// RSEQ (last template parameter) and rseq [B] (last argument): one pot resistance per sequence (wdf_asym.h asym_load_seq) -- the
+// constants are then this lane's; the six tangents stay {Is1, V1, Is2, V2, Rp, p}, the records keep their layout.
+template <int MODE, bool VEC4, int LOSS = 0, bool RSEQ = false>
 __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __restrict__ x, const float* __restrict__ theta6, float fs,
                                                                const float* __restrict__ target, float* __restrict__ y,
                                                                const float* __restrict__ z0, float* __restrict__ zT,
@@ -56,7 +63,7 @@ __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __re
                                                                double* __restrict__ rec, double tol, int max_iter,
                                                                AsymTpStatus* __restrict__ status, unsigned* __restrict__ ticket,
                                                                const unsigned* __restrict__ gate, int64_t B, int64_t T, int64_t L,
-                                                               int64_t W, int64_t skip = 0)
+                                                               int64_t W, int64_t skip = 0, const float* __restrict__ rseq = nullptr)
 {
     using S = typename AsymStep<MODE>::S;
     if (gate != nullptr) {
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(64) void clipper_asym_step_kernel(const float* __re
     const int64_t k = blockIdx.y;
     const int64_t t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
     const int64_t tw = (k > 0 && t0 > W) ? t0 - W : 0;
-    const AsymConsts c = asym_load(theta6, fs);
+    const AsymConsts c = RSEQ ? asym_load_seq(theta6, fs, rseq[b]) : asym_load(theta6, fs);
     const double p = c.p;
     const float* __restrict__ xp = x + b * T;
     int iters = 0;
@@ -211,11 +218,18 @@ __device__ __forceinline__ void asym_step_chain_rule(double SRp, double Sp, doub
 // gP_i += A tau_i + beta_i, gQ_i += A_Q tau_i + betaQ_i, tau_i <- P tau_i + q_i); the wave that finishes LAST sums the
 // partials in a fixed order (lane i takes waves i, i + 64, ...; then the shuffle tree), applies the chain rule Rp, p -> R, C
 // and, LOSS = 0, gscale: out7 = {sse, d(gscale/2 sse)/d{Is1, V1, Is2, V2, R, C}}; LOSS = 1: AsymStepEsrOut; then Adam, if asked for.
-template <int LOSS>
+// RSEQ: one pot per sequence.  Rp and p differ from lane to lane, so their sums over sequences mean nothing: each lane applies
+// the chain rule to its own {S_Rp, S_p} with its own R_b (asym_seq_chain_rule) behind its record walk and ahead of the wave sum,
+// for gP and, LOSS = 1, gQ alike.  Slot 5 then carries dC, slot 4 exactly 0 (the pot is data, not a parameter), and the last
+// wave skips its own chain rule: out7, sums14 and gtheta6 keep their layouts with component 4 equal to 0.0f.  Adam leaves
+// theta6[4] bit-for-bit as it was: a zero gradient on zero moments moves nothing, and so that a clip bound, a moment left by
+// static steps or eps = 0 cannot either, its lane leaves before it touches value or moments.
+template <int LOSS, bool RSEQ = false>
 __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const double* __restrict__ rec, const unsigned* __restrict__ gate,
                                                                       double* part, unsigned* ticket, float* theta6, float fs,
                                                                       float gscale, float* __restrict__ out7, AsymStepEsrOut esr,
-                                                                      AsymStepAdam adam, int64_t B, int64_t K)
+                                                                      AsymStepAdam adam, int64_t B, int64_t K,
+                                                                      const float* __restrict__ rseq = nullptr)
 {
     constexpr int NREC = LOSS ? kAsymStepRecEsr : kAsymStepRec, NP = LOSS ? kAsymStepPartEsr : kAsymStepPart;
     constexpr int NS = LOSS ? 14 : 7, GP = LOSS ? 2 : 1, GQ = 8;            // sums; where gP (and, LOSS = 1, gQ) start in them
@@ -235,6 +249,15 @@ __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const doub
             s[GP + q] += fma(A, tau[q], r[(9 + q) * B]);
             if constexpr (LOSS != 0) s[GQ + q] += fma(AQ, tau[q], r[(17 + q) * B]);
             tau[q] = fma(P, tau[q], r[(3 + q) * B]);
+        }
+    }
+    if constexpr (RSEQ) {
+        const double Rb = (double)rseq[b], Cb = (double)theta6[5];
+        s[GP + 5] = asym_seq_chain_rule(s[GP + 4], s[GP + 5], Rb, Cb, fs);
+        s[GP + 4] = 0.0;
+        if constexpr (LOSS != 0) {
+            s[GQ + 5] = asym_seq_chain_rule(s[GQ + 4], s[GQ + 5], Rb, Cb, fs);
+            s[GQ + 4] = 0.0;
         }
     }
     const unsigned nwaves = gridDim.x;
@@ -260,7 +283,8 @@ __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const doub
     // every lane forms the chain rule, lanes 0..5 keep their component
     const double R = theta6[4], C = theta6[5];
     double gR, gC;
-    asym_step_chain_rule(t[GP + 4], t[GP + 5], R, C, fs, gR, gC);
+    if constexpr (RSEQ) { gR = 0.0; gC = t[GP + 5]; }
+    else asym_step_chain_rule(t[GP + 4], t[GP + 5], R, C, fs, gR, gC);
     const int i = threadIdx.x < 6 ? threadIdx.x : 5;
     const double gi = i == 0 ? t[GP] : (i == 1 ? t[GP + 1] : (i == 2 ? t[GP + 2] : (i == 3 ? t[GP + 3] : (i == 4 ? gR : gC))));
     float g;
@@ -270,7 +294,8 @@ __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const doub
         if (threadIdx.x < 6) out7[1 + threadIdx.x] = g;
     } else {
         double qR, qC;
-        asym_step_chain_rule(t[GQ + 4], t[GQ + 5], R, C, fs, qR, qC);
+        if constexpr (RSEQ) { qR = 0.0; qC = t[GQ + 5]; }
+        else asym_step_chain_rule(t[GQ + 4], t[GQ + 5], R, C, fs, qR, qC);
         const double qi = i == 0 ? t[GQ] : (i == 1 ? t[GQ + 1] : (i == 2 ? t[GQ + 2] : (i == 3 ? t[GQ + 3] : (i == 4 ? qR : qC))));
         if (threadIdx.x == 0) { esr.sums14[0] = (float)t[0]; esr.sums14[1] = (float)t[1]; }
         if (threadIdx.x < 6) { esr.sums14[2 + threadIdx.x] = (float)gi; esr.sums14[8 + threadIdx.x] = (float)qi; }
@@ -286,6 +311,7 @@ __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const doub
     const int n = *adam.step + 1;                                // (one wave: every lane has read it before lane 0 writes)
     if (threadIdx.x == 0) *adam.step = n;
     if (threadIdx.x >= 6) return;
+    if (RSEQ && threadIdx.x == 4) return;                        // theta6[4] is not a parameter of this call: never written
     const double c1 = 1.0 - ipow((double)adam.b1, n), c2 = 1.0 - ipow((double)adam.b2, n);
     const float mi = adam.b1 * adam.m[i] + (1.0f - adam.b1) * g;
     const float vi = adam.b2 * adam.v[i] + (1.0f - adam.b2) * g * g;

@@ -266,7 +266,13 @@ class AsymDiodePair(_Element):
     element-wise reflected().  Circuit.mse(x, target) with a Newton solver runs forward, loss and the gradients of all six
     Variables in ONE pass over the data (wdf_clipper_asym_step_mse: no stash, no reverse sweep), and so does
     Circuit.mse_esr(x, target, skip) for the scripts' MSE + ESR loss past `skip` samples (wdf_clipper_asym_step_esr), with or
-    without z0 / carry_state; "omega_f32" and circ(x) keep the forward kernel and the reverse sweep.'''
+    without z0 / carry_state; "omega_f32" and circ(x) keep the forward kernel and the reverse sweep.
+
+    A pot that is constant along every recording (clipper_pot.py's dataset: input [B,T,2] = (Vin, R), dataimport.py:96) goes in
+    as Circuit(..., per_sequence_R=vs) with vs the tree's ResistiveVoltageSource and a Newton solver: circ(x), mse and mse_esr
+    then run the same kernels with one resistance per sequence (the wdf_clipper_asym_*_rseq entry points); the trainable values
+    are Is_up, nVt_up, Is_down, nVt_down and C -- vs.R receives no gradient: the pot is data.  A channel that moves inside a
+    sequence raises; per_sample_R stays unsupported under this root.'''
 
     SOLVERS = {"omega_f32": 0, "newton_f64": 1, "newton_f32": 2}          # wdf_hip.binding.ASYM_*
 

@@ -173,6 +173,12 @@ def lib():
                                             cf, vp, vp, fp, fp, fp, fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
     L.wdf_asym_esr_finish.restype = ci
     L.wdf_asym_esr_finish.argtypes = [fp, C.c_double, C.c_double, fp, fp, vp]
+    # one pot resistance per sequence: the static twins' argument lists with rseq behind x
+    for twin in ("wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_tp", "wdf_clipper_asym_step_mse",
+                 "wdf_clipper_asym_step_esr"):
+        fn, st = getattr(L, twin + "_rseq"), getattr(L, twin)
+        fn.restype = ci
+        fn.argtypes = [st.argtypes[0], fp] + list(st.argtypes[1:])
     L.wdf_asym_root.restype = ci
     L.wdf_asym_root.argtypes = [fp, fp, cf, ci, C.c_double, ci, vp, i64, vp]
     L.wdf_mlp_weight_count.restype = ci
@@ -308,6 +314,8 @@ EXPORTED_SYMBOLS = (
     "wdf_clipper_asym_bwd_tp_ws_bytes", "wdf_clipper_asym_bwd_tp", "wdf_asym_root",
     "wdf_clipper_asym_step_mse_ws_bytes", "wdf_clipper_asym_step_mse",
     "wdf_clipper_asym_step_esr_ws_bytes", "wdf_clipper_asym_step_esr", "wdf_asym_esr_finish",
+    "wdf_clipper_asym_fwd_rseq", "wdf_clipper_asym_fwd_tp_rseq", "wdf_clipper_asym_bwd_tp_rseq",
+    "wdf_clipper_asym_step_mse_rseq", "wdf_clipper_asym_step_esr_rseq",
     "wdf_ss_dyn_row_len", "wdf_ss_dyn_fwd", "wdf_ss_dyn_bwd_ws_bytes", "wdf_ss_dyn_bwd", "wdf_clipper_mlp_wgrad_matrix_core_chunks",
     "wdf_ss_dyn_fwd_tp_ws_bytes", "wdf_ss_dyn_fwd_tp", "wdf_ss_dyn_bwd_tp_ws_bytes", "wdf_ss_dyn_bwd_tp",
     "wdf_ss_dyn_rows", "wdf_ss_dyn_rows_bwd_ws_bytes", "wdf_ss_dyn_rows_bwd",
@@ -531,6 +539,7 @@ def clipper_bwd_mse_tp_adam(x, theta, fs, zstash, zT, target, gscale, n_chunks, 
 
 
 _R_SEQ_CACHE = ObjectMemo(64)       # (r, layout) -> bool
+_R_VEC_CACHE = ObjectMemo(64)       # r [B,T] -> its [B] vector of per-sequence values (r_per_sequence)
 R_PER_SEQUENCE = os.environ.get("WDF_R_PER_SEQUENCE", "1") not in ("", "0")     # (0: always the per-sample evaluation, for A/B runs and tests)
 
 
@@ -1016,7 +1025,77 @@ def clipper_mlp_wgrad(ain, lrin, gb, theta2, w, hidden, n_tanh, fs):
 ASYM_OMEGA_F32, ASYM_NEWTON_F64, ASYM_NEWTON_F32 = 0, 1, 2
 
 
-def clipper_asym_fwd(x, theta6, fs, mode, tol=1e-12, max_iter=50, z0=None, want_zT=False, want_iters=False, want_stash=False):
+def _asym_call(name, rseq, x, *rest):
+    """wdf_<name>(x, ...) or, with a pot per sequence, wdf_<name>_rseq(x, rseq, ...): the twins share every other argument."""
+    if rseq is None:
+        return getattr(lib(), name)(_ptr(x), *rest), name
+    return getattr(lib(), name + "_rseq")(_ptr(x), _ptr(_f32_dev(rseq, "rseq")), *rest), name + "_rseq"
+
+
+def _rseq_arg(rseq, x, mode, who):
+    """What every *_rseq wrapper checks before anything is launched: one resistance per sequence, a Newton mode."""
+    B = int(x.shape[0])
+    if not isinstance(rseq, torch.Tensor) or rseq.dtype != torch.float32 or rseq.dim() != 1 or rseq.numel() != B:
+        raise WdfHipError(f"{who}: rseq must be a float32 tensor [B] = [{B}] (one resistance per sequence), got "
+                          f"{type(rseq).__name__} {tuple(getattr(rseq, 'shape', ()))} {getattr(rseq, 'dtype', None)}")
+    if int(mode) == ASYM_OMEGA_F32:
+        raise WdfHipError(f"{who}: mode 0 (the closed form, a model approximation kept for comparison) has no per-sequence pot: "
+                          "use ASYM_NEWTON_F32 or ASYM_NEWTON_F64")
+    return rseq
+
+
+def r_per_sequence(r):
+    """A pot channel r [B,T] (clipper_pot.py:68-70: channel 1 of the input) -> the [B] vector of its per-sequence values
+    (contiguous, cached with the channel); WdfHipError if the channel moves inside a sequence: the two-different-diode kernels
+    take one resistance per sequence.  One cached comparison per tensor (r_is_per_sequence)."""
+    if not isinstance(r, torch.Tensor) or r.dim() != 2:
+        raise WdfHipError(f"r_per_sequence: expected a [B,T] tensor, got {type(r).__name__} {tuple(getattr(r, 'shape', ()))}")
+    hit = _R_VEC_CACHE.get(r)
+    if hit is not None:
+        return hit
+    const = r_is_per_sequence(r, False)
+    if not const and not (r.is_cuda and torch.cuda.is_current_stream_capturing()):
+        const = bool((r == r[:, 0:1]).all())       # (WDF_R_PER_SEQUENCE=0 switches the cached answer off, not this contract)
+    if not const:
+        raise WdfHipError("the two-different-diode clipper takes one resistance per sequence (clipper_pot.py's recordings: "
+                          "dataimport.py:96); this channel moves inside a sequence (or could not be looked at during stream capture)")
+    return _R_VEC_CACHE.put(r, r[:, 0].float().contiguous())
+
+
+def clipper_asym_fwd_rseq(x, rseq, theta6, fs, mode, **kw):
+    """clipper_asym_fwd with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_fwd_rseq): theta6[4] is ignored."""
+    return clipper_asym_fwd(x, theta6, fs, mode, _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_fwd_rseq"), **kw)
+
+
+def clipper_asym_fwd_tp_rseq(x, rseq, theta6, fs, mode, n_chunks, warmup, **kw):
+    """clipper_asym_fwd_tp with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_fwd_tp_rseq): theta6[4] is ignored;
+    the warm-up has to outlast the LARGEST pot's memory."""
+    return clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_fwd_tp_rseq"), **kw)
+
+
+def clipper_asym_bwd_tp_rseq(x, rseq, theta6, fs, mode, zstash, zT, gy, n_chunks, **kw):
+    """clipper_asym_bwd_tp with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_bwd_tp_rseq): component 4 of the
+    gradient is exactly 0 (the pot is data), component 5 is dL/dC with the chain rule applied per sequence."""
+    return clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks,
+                               _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_bwd_tp_rseq"), **kw)
+
+
+def clipper_asym_step_mse_rseq(x, rseq, theta6, fs, mode, target, gscale, n_chunks, warmup, **kw):
+    """clipper_asym_step_mse with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_step_mse_rseq): out7[5] (dR) is
+    exactly 0 and opt never writes theta6[4]."""
+    return clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup,
+                                 _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_step_mse_rseq"), **kw)
+
+
+def clipper_asym_step_esr_rseq(x, rseq, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup, **kw):
+    """clipper_asym_step_esr with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_step_esr_rseq): component 4 of
+    gP, gQ and gtheta6 is exactly 0 and opt never writes theta6[4]."""
+    return clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup,
+                                 _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_step_esr_rseq"), **kw)
+
+
+def clipper_asym_fwd(x, theta6, fs, mode, tol=1e-12, max_iter=50, z0=None, want_zT=False, want_iters=False, want_stash=False,
+                     _rseq=None):
     """Two-different-diode clipper forward.  Returns y [T,B], zT | None, iters (int64 per wave) | None
     (and the state stash [T,B] as a fourth value when want_stash)."""
     require_gpu()
@@ -1030,14 +1109,14 @@ def clipper_asym_fwd(x, theta6, fs, mode, tol=1e-12, max_iter=50, z0=None, want_
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
     it = torch.zeros(((B + 63) // 64,), dtype=torch.int64, device=x.device) if want_iters else None
     zs = torch.empty((T, B), dtype=torch.float32, device=x.device) if want_stash else None
-    rc = lib().wdf_clipper_asym_fwd(_ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
-                                    _ptr(zs), _ptr(z0), _ptr(zT), _ptr(it), B, T, _stream())
-    _check(rc, "wdf_clipper_asym_fwd")
+    rc, name = _asym_call("wdf_clipper_asym_fwd", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
+                          _ptr(zs), _ptr(z0), _ptr(zT), _ptr(it), B, T, _stream())
+    _check(rc, name)
     return (y, zT, it, zs) if want_stash else (y, zT, it)
 
 
 def clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, z0=None, want_zT=False,
-                        want_stash=False):
+                        want_stash=False, _rseq=None):
     """Time-parallel two-different-diode clipper forward (wdf_clipper_asym_fwd_tp).  n_chunks is rounded to a count that
     tiles T in 8-step units.  -> y [T,B], zT | None, zstash | None, status (int32[4]; read with mlp_tp_status())."""
     require_gpu()
@@ -1051,9 +1130,9 @@ def clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, tol=1e-12, max_it
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
     ws = torch.empty((lib().wdf_clipper_asym_fwd_tp_ws_bytes(B, K),), dtype=torch.uint8, device=x.device)
     status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    rc = lib().wdf_clipper_asym_fwd_tp(_ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y), _ptr(zs),
-                                       _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _stream())
-    _check(rc, "wdf_clipper_asym_fwd_tp")
+    rc, name = _asym_call("wdf_clipper_asym_fwd_tp", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
+                          _ptr(zs), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _stream())
+    _check(rc, name)
     return y, zT, zs, status
 
 
@@ -1072,7 +1151,7 @@ def clipper_asym_bwd(x, theta6, fs, zstash, gy, tol=1e-12, max_iter=50):
     return g
 
 
-def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None, want_gz0=False, ws=None):
+def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None, want_gz0=False, ws=None, _rseq=None):
     """Time-parallel reverse sweep of the two-different-diode clipper, any mode (wdf_clipper_asym_bwd_tp): no root
     re-solve (consecutive stash entries give b), chunks composed exactly.  zT [B]: the forward's final state.
     -> gtheta6 (and dL/dz0 [B] when want_gz0)."""
@@ -1088,9 +1167,9 @@ def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None,
         ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
     g = torch.empty((6,), dtype=torch.float32, device=x.device)
     gz0 = torch.empty((B,), dtype=torch.float32, device=x.device) if want_gz0 else None
-    rc = lib().wdf_clipper_asym_bwd_tp(_ptr(x), _ptr(theta6), float(fs), int(mode), _ptr(zstash), _ptr(zT), _ptr(gy), _ptr(gzT),
-                                       _ptr(ws), _ptr(g), _ptr(gz0), B, T, K, _stream())
-    _check(rc, "wdf_clipper_asym_bwd_tp")
+    rc, name = _asym_call("wdf_clipper_asym_bwd_tp", _rseq, x, _ptr(theta6), float(fs), int(mode), _ptr(zstash), _ptr(zT), _ptr(gy),
+                          _ptr(gzT), _ptr(ws), _ptr(g), _ptr(gz0), B, T, K, _stream())
+    _check(rc, name)
     return (g, gz0) if want_gz0 else g
 
 
@@ -1100,7 +1179,7 @@ def asym_chunks(T, n_chunks):
 
 
 def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, y=None,
-                          z0=None, want_zT=False, ws=None, status=None, out7=None, opt=None):
+                          z0=None, want_zT=False, ws=None, status=None, out7=None, opt=None, _rseq=None):
     """The MSE training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_mse): forward,
     loss and d(gscale/2 sum (y - target)^2)/d{Is_up, nVt_up, Is_down, nVt_down, R, C}, x [B,T] and target [T,B] read once, y
     written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is rounded like asym_chunks(); y, ws, status,
@@ -1135,19 +1214,19 @@ def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup,
     elif _f32_dev(out7, "out7").numel() != 7:
         raise WdfHipError("out7 must hold {sse, gtheta6}")
     o = opt
-    rc = lib().wdf_clipper_asym_step_mse(
-        _ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(gscale), _ptr(y), _ptr(z0),
+    rc, name = _asym_call(
+        "wdf_clipper_asym_step_mse", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(gscale), _ptr(y), _ptr(z0),
         _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(out7),
         *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
         0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
         None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
-    _check(rc, "wdf_clipper_asym_step_mse")
+    _check(rc, name)
     return y, zT, out7, status
 
 
 def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup, tol=1e-12, max_iter=50,
                           verify_tol=1e-6, y=None, z0=None, want_zT=False, ws=None, status=None, sums14=None, gtheta6=None, loss3=None,
-                          finish=True, opt=None):
+                          finish=True, opt=None, _rseq=None):
     """The MSE + ESR training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_esr):
     loss = S/n + sqrt(S / (E + eps_energy) / n) on the rows past `skip`, S = sum (y - target)^2, E = sum y^2, n = n_global.
     x [B,T] and target [T,B] read once, y written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is
@@ -1196,14 +1275,14 @@ def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, ski
         elif _f32_dev(loss3, "loss3").numel() != 3:
             raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
     o = opt
-    rc = lib().wdf_clipper_asym_step_esr(
-        _ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(n_global), float(eps_energy),
+    rc, name = _asym_call(
+        "wdf_clipper_asym_step_esr", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(n_global), float(eps_energy),
         int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(sums14),
         _ptr(gtheta6), _ptr(loss3),
         *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
         0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
         None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
-    _check(rc, "wdf_clipper_asym_step_esr")
+    _check(rc, name)
     return y, zT, sums14, gtheta6, loss3, status
 
 

@@ -201,9 +201,17 @@ class _ClipperAsymFn(torch.autograd.Function):
     other modes then run the time-parallel sweep with one chunk).  z0 is a constant of the call, zT comes back detached."""
 
     @staticmethod
-    def forward(ctx, theta6, x, fs, tol, max_iter, tp, mode, z0):
+    def forward(ctx, theta6, x, fs, tol, max_iter, tp, mode, z0, rseq=None):
         th = theta6.detach().contiguous()
-        if tp is not None and tp.k_fwd > 1:      # time chunks, verified on the device (wdf_clipper_asym_fwd_tp)
+        if rseq is not None:                     # one pot per sequence (the *_rseq entry points): theta6[4] is ignored
+            if tp is not None and tp.k_fwd > 1:
+                y, zT, zs, st = binding.clipper_asym_fwd_tp_rseq(x, rseq, th, fs, mode, tp.k_fwd, tp.warmup, tol=tol, max_iter=max_iter,
+                                                                 verify_tol=tp.tol, z0=z0, want_stash=True, want_zT=True)
+                LAST_TP_STATUS["status"] = st
+            else:
+                y, zT, _, zs = binding.clipper_asym_fwd_rseq(x, rseq, th, fs, mode, tol=tol, max_iter=max_iter, z0=z0, want_stash=True,
+                                                             want_zT=True)
+        elif tp is not None and tp.k_fwd > 1:    # time chunks, verified on the device (wdf_clipper_asym_fwd_tp)
             y, zT, zs, st = binding.clipper_asym_fwd_tp(x, th, fs, mode, tp.k_fwd, tp.warmup, tol=tol, max_iter=max_iter,
                                                         verify_tol=tp.tol, z0=z0, want_stash=True, want_zT=True)
             LAST_TP_STATUS["status"] = st
@@ -216,22 +224,36 @@ class _ClipperAsymFn(torch.autograd.Function):
         else:                                    # as many chunks as give every SIMD ~2 waves, none shorter than 64 steps
             k_bwd = max(1, min(T // 64, (2 * N_SIMD) // max(1, -(-B // 64))))
         ctx.cfg = (fs, tol, max_iter, mode, k_bwd)
-        ctx.save_for_backward(th, x, zs, zT)
+        ctx.save_for_backward(th, x, zs, zT, *([rseq] if rseq is not None else []))
         ctx.mark_non_differentiable(zT)
         return y, zT
 
     @staticmethod
     def backward(ctx, gy, _gzT):
         fs, tol, max_iter, mode, k_bwd = ctx.cfg
-        th, x, zs, zT = ctx.saved_tensors
-        if k_bwd < 1 and mode == binding.ASYM_NEWTON_F64:
+        th, x, zs, zT = ctx.saved_tensors[:4]
+        if len(ctx.saved_tensors) > 4:           # a pot per sequence: the time-parallel sweep (one exact chunk at the least)
+            g = binding.clipper_asym_bwd_tp_rseq(x, ctx.saved_tensors[4], th, fs, mode, zs, zT, gy.contiguous(), max(1, k_bwd))
+        elif k_bwd < 1 and mode == binding.ASYM_NEWTON_F64:
             g = binding.clipper_asym_bwd(x, th, fs, zs, gy.contiguous(), tol=tol, max_iter=max_iter)
         else:
             g = binding.clipper_asym_bwd_tp(x, th, fs, mode, zs, zT, gy.contiguous(), max(1, k_bwd))
-        return g, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None
 
 
-def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None, z0=None, return_state=False):
+def _rseq_of(r, x):
+    """r: None, a pot channel [B,T] or its [B] vector -> None or the [B] vector the *_rseq entry points take."""
+    if r is None:
+        return None
+    if r.dim() == 2:
+        r = binding.r_per_sequence(r)
+    if r.dim() != 1 or r.numel() != x.shape[0]:
+        raise binding.WdfHipError(f"r must hold one resistance per sequence ([{x.shape[0]}], or a [B,T] channel constant along T), "
+                                  f"got {tuple(r.shape)}")
+    return r.detach().to(device=x.device, dtype=torch.float32).contiguous()
+
+
+def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None, z0=None, return_state=False, r=None):
     """Two-different-diode clipper loop (BASELINE config 5) with gradients to all six parameters.
     mode: binding.ASYM_NEWTON_F64 (default: the exact model in fp64), binding.ASYM_NEWTON_F32 (the exact model in fp32: the
     fast one; tol is floored at 4 FLT_EPSILON) or binding.ASYM_OMEGA_F32 (the fp32 closed form: a model approximation, kept
@@ -239,13 +261,18 @@ def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None, z0
     tp: a TpPlan (plan_asym_time_parallel with the circuit's R, C) -> the forward runs in k_fwd verified time chunks and the
     reverse sweep in k_bwd exact ones (k_bwd = 0: the sequential sweep, fp64 Newton mode; one exact chunk otherwise).
     z0 [B]: the capacitor state the loop starts from (default zero), a constant of the call: no gradient flows into it.
-    return_state: -> (y, zT), zT [B] the state the loop ended in, detached."""
+    return_state: -> (y, zT), zT [B] the state the loop ended in, detached.
+    r: one pot resistance per sequence -- [B], or a [B,T] channel constant along T (binding.r_per_sequence) -- in place of
+    theta6[4], which is then ignored and receives a zero gradient (Newton modes; plan with engine.resistance_max(r))."""
     mode = binding.ASYM_NEWTON_F64 if mode is None else int(mode)
     if z0 is not None:
         z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
         if z0.numel() != x.shape[0]:
             raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
-    y, zT = _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode, z0)
+    if r is not None:
+        y, zT = _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode, z0, _rseq_of(r, x))
+    else:
+        y, zT = _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode, z0)
     return (y, zT) if return_state else y
 
 
@@ -275,13 +302,18 @@ class AsymMseStep:
         self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=device)
         self.zT = None
 
-    def step_fused(self, theta6, x, target, adam=None, z0=None, want_zT=False):
+    def step_fused(self, theta6, x, target, adam=None, z0=None, want_zT=False, r=None):
         """adam: a binding.Adam(6, ...) to update theta6 in the step's own last launch; otherwise the caller applies its
         optimizer to self.gtheta.  z0 [B]: the state the call starts from, a constant of it; want_zT: self.zT <- the state
-        it ends in.  Fills self.y, self.out, self.status."""
-        _, self.zT, _, _ = binding.clipper_asym_step_mse(
-            x, theta6, self.fs, self.mode, target, self.gscale, self.k, self.warmup, tol=self.tol, max_iter=self.max_iter,
-            verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws, status=self.status, out7=self.out, opt=adam)
+        it ends in.  r [B]: one pot resistance per sequence in place of theta6[4] (dR is then exactly 0 and adam never writes
+        theta6[4]; the stepper's plan must come from the largest pot).  Fills self.y, self.out, self.status."""
+        kw = dict(tol=self.tol, max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws,
+                  status=self.status, out7=self.out, opt=adam)
+        if r is None:
+            _, self.zT, _, _ = binding.clipper_asym_step_mse(x, theta6, self.fs, self.mode, target, self.gscale, self.k, self.warmup, **kw)
+        else:
+            _, self.zT, _, _ = binding.clipper_asym_step_mse_rseq(x, r, theta6, self.fs, self.mode, target, self.gscale, self.k,
+                                                                  self.warmup, **kw)
         return self.sse, self.gtheta
 
 
@@ -292,16 +324,16 @@ class _ClipperAsymMseFn(torch.autograd.Function):
     _steppers = {}
 
     @staticmethod
-    def forward(ctx, theta6, x, target, fs, tp, mode, z0, keep):
+    def forward(ctx, theta6, x, target, fs, tp, mode, z0, keep, rseq=None):
         B, T = x.shape
-        key = (B, T, float(fs), tp, mode, x.device)
+        key = (B, T, float(fs), tp, mode, x.device, rseq is not None)
         st = _ClipperAsymMseFn._steppers.get(key)
         if st is None:
             if len(_ClipperAsymMseFn._steppers) > 8:
                 _ClipperAsymMseFn._steppers.clear()
             st = _ClipperAsymMseFn._steppers[key] = AsymMseStep(B, T, fs, tp, x.device, mode=mode)
         LAST_TP_STATUS["status"] = st.status
-        st.step_fused(theta6.detach().contiguous(), x, target, z0=z0, want_zT=keep)
+        st.step_fused(theta6.detach().contiguous(), x, target, z0=z0, want_zT=keep, r=rseq)
         out = st.out.clone()
         ctx.save_for_backward(out)
         if not keep:
@@ -313,21 +345,24 @@ class _ClipperAsymMseFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gl, *_):
         (out,) = ctx.saved_tensors
-        return gl * out[1:7], None, None, None, None, None, None, None
+        return gl * out[1:7], None, None, None, None, None, None, None, None
 
 
-def clipper_asym_mse(theta6, x, target, fs, tp=None, mode=None, z0=None, return_state=False):
+def clipper_asym_mse(theta6, x, target, fs, tp=None, mode=None, z0=None, return_state=False, r=None):
     """Scalar mean-squared error of the two-different-diode clipper's output against target [T,B], differentiable w.r.t.
     theta6 = {Is_up, nVt_up, Is_down, nVt_down, R, C} (float32[6] on the device), as ONE pass over the data
     (wdf_clipper_asym_step_mse): no stash, no torch loss temporaries, no reverse sweep.  mode: binding.ASYM_NEWTON_F32
     (default) or binding.ASYM_NEWTON_F64.  tp: a TpPlan (plan_asym_time_parallel) or None for one chunk.
     z0 [B]: the state the loop starts from, a constant of the call.
+    r: one pot resistance per sequence ([B], or a [B,T] channel constant along T) in place of theta6[4], as in clipper_asym.
     -> loss, or (loss, y [T,B], zT [B]) with return_state: the call's output and final state, detached."""
     mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
     if z0 is not None:
         z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
         if z0.numel() != x.shape[0]:
             raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    if r is not None:
+        return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state), _rseq_of(r, x))
     return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state))
 
 
@@ -359,14 +394,19 @@ class AsymEsrStep:
         self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=device)
         self.zT = None
 
-    def step_fused(self, theta6, x, target, adam=None, z0=None, want_zT=False, finish=True):
+    def step_fused(self, theta6, x, target, adam=None, z0=None, want_zT=False, finish=True, r=None):
         """adam: a binding.Adam(6, ...) to update theta6 in the step's own last launch; otherwise the caller applies its
         optimizer to self.gtheta.  z0 [B]: the state the call starts from, a constant of it; want_zT: self.zT <- the state
-        it ends in.  Fills self.y, self.sums, self.status and -- finish -- self.loss3, self.gtheta."""
-        _, self.zT, _, _, _, _ = binding.clipper_asym_step_esr(
-            x, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy, self.skip, self.k, self.warmup, tol=self.tol,
-            max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws, status=self.status,
-            sums14=self.sums, gtheta6=self.gtheta, loss3=self.loss3, finish=finish, opt=adam)
+        it ends in.  r [B]: one pot resistance per sequence in place of theta6[4], as in AsymMseStep.step_fused.
+        Fills self.y, self.sums, self.status and -- finish -- self.loss3, self.gtheta."""
+        kw = dict(tol=self.tol, max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws,
+                  status=self.status, sums14=self.sums, gtheta6=self.gtheta, loss3=self.loss3, finish=finish, opt=adam)
+        if r is None:
+            self.zT = binding.clipper_asym_step_esr(x, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy, self.skip,
+                                                    self.k, self.warmup, **kw)[1]
+        else:
+            self.zT = binding.clipper_asym_step_esr_rseq(x, r, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy,
+                                                         self.skip, self.k, self.warmup, **kw)[1]
         return self.loss3, self.gtheta
 
 
@@ -377,8 +417,8 @@ class _ClipperAsymEsrFn(torch.autograd.Function):
     _steppers = {}
 
     @staticmethod
-    def stepper(B, T, fs, tp, mode, skip, device):
-        key = (B, T, float(fs), tp, mode, int(skip), device)
+    def stepper(B, T, fs, tp, mode, skip, device, pot=False):
+        key = (B, T, float(fs), tp, mode, int(skip), device, bool(pot))
         st = _ClipperAsymEsrFn._steppers.get(key)
         if st is None:
             if len(_ClipperAsymEsrFn._steppers) > 8:
@@ -387,11 +427,11 @@ class _ClipperAsymEsrFn(torch.autograd.Function):
         return st
 
     @staticmethod
-    def forward(ctx, theta6, x, target, fs, skip, tp, mode, z0, keep):
+    def forward(ctx, theta6, x, target, fs, skip, tp, mode, z0, keep, rseq=None):
         B, T = x.shape
-        st = _ClipperAsymEsrFn.stepper(B, T, fs, tp, mode, skip, x.device)
+        st = _ClipperAsymEsrFn.stepper(B, T, fs, tp, mode, skip, x.device, pot=rseq is not None)
         LAST_TP_STATUS["status"] = st.status
-        st.step_fused(theta6.detach().contiguous(), x, target, z0=z0, want_zT=keep)
+        st.step_fused(theta6.detach().contiguous(), x, target, z0=z0, want_zT=keep, r=rseq)
         ctx.save_for_backward(st.gtheta.clone())
         loss = st.loss3[2].clone()
         if not keep:
@@ -403,22 +443,25 @@ class _ClipperAsymEsrFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gl, *_):
         (g,) = ctx.saved_tensors
-        return gl * g, None, None, None, None, None, None, None, None
+        return gl * g, None, None, None, None, None, None, None, None, None
 
 
-def clipper_asym_mse_esr(theta6, x, target, fs, skip=0, tp=None, mode=None, z0=None, return_state=False):
+def clipper_asym_mse_esr(theta6, x, target, fs, skip=0, tp=None, mode=None, z0=None, return_state=False, r=None):
     """The scripts' training loss (clipper_pot.py:146-156,177: mean((y - t)^2) + sqrt(sum((y - t)^2) / (sum(y^2) + eps) / n)
     on the rows past `skip`) of the two-different-diode clipper's output against target [T,B], differentiable w.r.t.
     theta6 = {Is_up, nVt_up, Is_down, nVt_down, R, C} (float32[6] on the device), as ONE pass over the data
     (wdf_clipper_asym_step_esr): no stash, no torch reductions, no reverse sweep.  mode: binding.ASYM_NEWTON_F32
     (default) or binding.ASYM_NEWTON_F64.  tp: a TpPlan (plan_asym_time_parallel) or None for one chunk.
     z0 [B]: the state the loop starts from, a constant of the call.
+    r: one pot resistance per sequence ([B], or a [B,T] channel constant along T) in place of theta6[4], as in clipper_asym.
     -> loss, or (loss, y [T,B], zT [B]) with return_state: the call's output and final state, detached."""
     mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
     if z0 is not None:
         z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
         if z0.numel() != x.shape[0]:
             raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    if r is not None:
+        return _ClipperAsymEsrFn.apply(theta6, x, target, float(fs), int(skip), tp, mode, z0, bool(return_state), _rseq_of(r, x))
     return _ClipperAsymEsrFn.apply(theta6, x, target, float(fs), int(skip), tp, mode, z0, bool(return_state))
 
 

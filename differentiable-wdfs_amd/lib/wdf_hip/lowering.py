@@ -674,9 +674,14 @@ class Circuit:
     per_sample_R: a ResistiveVoltageSource whose resistance is streamed from the NEXT input
     channel (clipper_pot.py:114-116: channel 0 = Vin, channel 1 = R); diode-clipper
     topology only.
+    per_sequence_R: the same channel layout under an AsymDiodePair root with a Newton solver, for a pot that is constant
+    along every sequence (clipper_pot.py's recordings: dataimport.py:96): top.P1, the clipper's ResistiveVoltageSource.  The
+    two-different-diode kernels evaluate the port once per sequence (csrc/wdf_asym.h asym_load_seq); a channel that moves
+    inside a sequence raises.  The source's own R receives no gradient: the pot is data.
     """
 
-    def __init__(self, top, root, probe, per_sample_R=None, force_generic=False, time_parallel="auto", warm_start=True):
+    def __init__(self, top, root, probe, per_sample_R=None, force_generic=False, time_parallel="auto", warm_start=True,
+                 per_sequence_R=None):
         self.top, self.root, self.probe = top, root, probe
         self.time_parallel = time_parallel          # "auto" | None | engine.TpPlan
         self.warm_start = bool(warm_start)          # generic trees with a diode root: SsWarmStart when a batch is re-visited
@@ -699,7 +704,19 @@ class Circuit:
             raise ValueError("the circuit has no voltage source")
         if self.root_kind == "AsymDiodePair" and not (self._is_clipper() and per_sample_R is None and not self.force_generic):
             raise binding.WdfHipError("an AsymDiodePair root runs on the diode-clipper tree only: top = Parallel(ResistiveVoltageSource, "
-                                      "Capacitor), probe = the capacitor, no per_sample_R, not force_generic (csrc/wdf_asym.h)")
+                                      "Capacitor), probe = the capacitor, no per_sample_R (a pot that is constant along every "
+                                      "sequence goes in as per_sequence_R), not force_generic (csrc/wdf_asym.h)")
+        self.per_sequence_R = per_sequence_R
+        if per_sequence_R is not None:
+            if self.root_kind != "AsymDiodePair":
+                raise binding.WdfHipError("per_sequence_R belongs to an AsymDiodePair root (one resistance per sequence: "
+                                          "csrc/wdf_asym.h); every other root streams the pot per sample: per_sample_R")
+            if per_sequence_R is not self.top.P1:
+                raise binding.WdfHipError("per_sequence_R must be top.P1, the ResistiveVoltageSource of the clipper tree: the "
+                                          f"kernels have one pot, the source's (got a {_kind(per_sequence_R)})")
+            if self.root.mode == binding.ASYM_OMEGA_F32:
+                raise binding.WdfHipError("per_sequence_R needs a Newton solver: the closed form (omega_f32, a model approximation "
+                                          "kept for comparison) has no per-sequence pot")
         # Outside the clipper topology a per-sample impedance or a DenseRootModel root runs on the streamed-coefficient kernels
         # (csrc/wdf_ss_dyn.h) -- and so does, since round 6, ANY tree of five to eight capacitors (the static-coefficient kernels
         # of csrc/wdf_statespace.h are compiled for at most four: a larger tree hands the streamed kernels one static row)
@@ -1016,7 +1033,7 @@ class Circuit:
         x = x.float()
         if x.dim() == 2:
             x = x.unsqueeze(-1)
-        nchan = self.ni + (1 if self.per_sample_R is not None else 0)
+        nchan = self.ni + (1 if self.per_sample_R is not None or self.per_sequence_R is not None else 0)
         if x.dim() != 3 or x.shape[2] != nchan:
             raise binding.WdfHipError(f"x must be [B,T,{nchan}] (or [B,T] for one channel), got {tuple(x.shape)}")
         dev = x.device
@@ -1228,88 +1245,81 @@ class Circuit:
         cache[key] = (plan, 0)
         return plan
 
-    def _run_clipper_asym(self, x, z0, return_state):
-        """The clipper tree under an AsymDiodePair root: one launch of the two-different-diode loop (engine.clipper_asym) in the
-        root's solver mode, gradients to the four diode Variables, R and C."""
+    def _asym_inputs(self, x, anchor):
+        """What the three AsymDiodePair paths share: theta6, the [B,T] input, the [B] pot vector (None without per_sequence_R) and
+        the plan.  With a pot the input is [B,T,2] (clipper_pot.py:68-70: channel 1 is the pot), theta6[4] is a placeholder the
+        kernels ignore (vs.R gets no gradient) and the plan comes from the LARGEST pot: it forgets slowest."""
         from . import engine
         dp, vs, cap = self.root, self.top.P1, self.top.P2
-        dev = x.device
-        Rv = vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R))
+        pot = self.per_sequence_R is not None
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        if x.dim() != 3 or x.shape[2] != (2 if pot else 1):
+            raise binding.WdfHipError(("x must be [B,T,2] (Vin, R)" if pot else "x must be [B,T,1] (or [B,T] for one channel)")
+                                      + f", got {tuple(x.shape)}")
+        Rv = torch.tensor(1.0) if pot else (vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R)))
         parts = [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, Rv, cap.C]
-        theta6 = self._theta(parts, dev)
-        xv, _ = engine.split_channels(x, False, anchor=getattr(self, "_anchor", None))
+        theta6 = self._theta(parts, x.device)
+        xv, r = engine.split_channels(x, pot, anchor=anchor)
+        rseq = binding.r_per_sequence(r) if pot else None
         tp = self.time_parallel
         if tp == "auto":
-            tp = engine.plan_asym_time_parallel(xv.shape[0], xv.shape[1], float(parts[4]), float(parts[5]), float(cap.FS))
+            R_plan = engine.resistance_max(r) if pot else float(parts[4])
+            tp = engine.plan_asym_time_parallel(xv.shape[0], xv.shape[1], R_plan, float(parts[5]), float(cap.FS))
         elif not isinstance(tp, engine.TpPlan):
             tp = None
+        return theta6, xv, rseq, tp
+
+    def _run_clipper_asym(self, x, z0, return_state):
+        """The clipper tree under an AsymDiodePair root: one launch of the two-different-diode loop (engine.clipper_asym) in the
+        root's solver mode, gradients to the four diode Variables, R and C (with per_sequence_R: to the diodes and C)."""
+        from . import engine
+        theta6, xv, rseq, tp = self._asym_inputs(x, getattr(self, "_anchor", None))
         z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor)
-        y, zT = engine.clipper_asym(theta6, xv, float(cap.FS), tp=tp, mode=dp.mode, z0=z0t, return_state=True)
+        y, zT = engine.clipper_asym(theta6, xv, float(self.top.P2.FS), tp=tp, mode=self.root.mode, z0=z0t, return_state=True, r=rseq)
         y = y.as_subclass(tf.Tensor)
         return (y, zT.reshape(1, -1)) if return_state else y
 
     def _mse_clipper_asym(self, x, target, z0, stateful):
         """mse() on the clipper tree under an AsymDiodePair root with a Newton solver: forward, loss and the six gradients in
         one pass over the data (engine.clipper_asym_mse) -- no stash, no torch loss, no reverse sweep.  State in and out as
-        the composed path handles it: z0 is a constant of the call, last_state / last_output are set on stateful calls."""
+        the composed path handles it: z0 is a constant of the call, last_state / last_output are set on stateful calls.
+        With per_sequence_R the same one-pass step with one pot per sequence (wdf_clipper_asym_step_mse_rseq)."""
         from . import engine
         anchor = x if isinstance(x, torch.Tensor) else None
         x = torch.as_tensor(x).as_subclass(torch.Tensor)
         x = (x if x.is_cuda else x.cuda()).float()
-        if x.dim() == 2:
-            x = x.unsqueeze(-1)
-        if x.dim() != 3 or x.shape[2] != 1:
-            raise binding.WdfHipError(f"x must be [B,T,1] (or [B,T] for one channel), got {tuple(x.shape)}")
-        dp, vs, cap = self.root, self.top.P1, self.top.P2
-        Rv = vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R))
-        parts = [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, Rv, cap.C]
-        theta6 = self._theta(parts, x.device)
-        xv, _ = engine.split_channels(x, False, anchor=anchor)
+        theta6, xv, rseq, tp = self._asym_inputs(x, anchor)
         B, T = xv.shape
+        fs, mode = float(self.top.P2.FS), self.root.mode
         tgt = torch.as_tensor(target).as_subclass(torch.Tensor).to(x.device).float().reshape(T, B).contiguous()
-        tp = self.time_parallel
-        if tp == "auto":
-            tp = engine.plan_asym_time_parallel(B, T, float(parts[4]), float(parts[5]), float(cap.FS))
-        elif not isinstance(tp, engine.TpPlan):
-            tp = None
         z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor)
         if not stateful:
-            return engine.clipper_asym_mse(theta6, xv, tgt, float(cap.FS), tp=tp, mode=dp.mode).as_subclass(tf.Tensor)
-        loss, y, zT = engine.clipper_asym_mse(theta6, xv, tgt, float(cap.FS), tp=tp, mode=dp.mode, z0=z0t, return_state=True)
+            return engine.clipper_asym_mse(theta6, xv, tgt, fs, tp=tp, mode=mode, r=rseq).as_subclass(tf.Tensor)
+        loss, y, zT = engine.clipper_asym_mse(theta6, xv, tgt, fs, tp=tp, mode=mode, z0=z0t, return_state=True, r=rseq)
         self.last_state, self.last_output = zT.reshape(1, -1), y.as_subclass(tf.Tensor)
         return loss.as_subclass(tf.Tensor)
 
     def _mse_esr_clipper_asym(self, x, target, skip, z0, stateful):
         """mse_esr() on the clipper tree under an AsymDiodePair root with a Newton solver: forward, the loss sums S and E past
         `skip` and the six gradients in one pass over the data (engine.clipper_asym_mse_esr) -- no stash, no torch
-        reductions, no reverse sweep.  State in and out as _mse_clipper_asym handles it."""
+        reductions, no reverse sweep.  State in and out as _mse_clipper_asym handles it; per_sequence_R likewise
+        (wdf_clipper_asym_step_esr_rseq)."""
         from . import engine
         anchor = x if isinstance(x, torch.Tensor) else None
         x = torch.as_tensor(x).as_subclass(torch.Tensor)
         x = (x if x.is_cuda else x.cuda()).float()
-        if x.dim() == 2:
-            x = x.unsqueeze(-1)
-        if x.dim() != 3 or x.shape[2] != 1:
-            raise binding.WdfHipError(f"x must be [B,T,1] (or [B,T] for one channel), got {tuple(x.shape)}")
-        dp, vs, cap = self.root, self.top.P1, self.top.P2
-        Rv = vs.R if isinstance(vs.R, torch.Tensor) else torch.tensor(float(vs.R))
-        parts = [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, Rv, cap.C]
-        theta6 = self._theta(parts, x.device)
-        xv, _ = engine.split_channels(x, False, anchor=anchor)
+        theta6, xv, rseq, tp = self._asym_inputs(x, anchor)
         B, T = xv.shape
+        fs, mode = float(self.top.P2.FS), self.root.mode
         tgt = torch.as_tensor(target).as_subclass(torch.Tensor).to(x.device).float().reshape(T, B).contiguous()
-        tp = self.time_parallel
-        if tp == "auto":
-            tp = engine.plan_asym_time_parallel(B, T, float(parts[4]), float(parts[5]), float(cap.FS))
-        elif not isinstance(tp, engine.TpPlan):
-            tp = None
         z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor)
         if not stateful:
-            loss = engine.clipper_asym_mse_esr(theta6, xv, tgt, float(cap.FS), skip=skip, tp=tp, mode=dp.mode)
-            self.last_output = engine._ClipperAsymEsrFn.stepper(B, T, float(cap.FS), tp, dp.mode, skip, xv.device).y.as_subclass(tf.Tensor)
+            loss = engine.clipper_asym_mse_esr(theta6, xv, tgt, fs, skip=skip, tp=tp, mode=mode, r=rseq)
+            self.last_output = engine._ClipperAsymEsrFn.stepper(B, T, fs, tp, mode, skip, xv.device,
+                                                                pot=rseq is not None).y.as_subclass(tf.Tensor)
             return loss.as_subclass(tf.Tensor)
-        loss, y, zT = engine.clipper_asym_mse_esr(theta6, xv, tgt, float(cap.FS), skip=skip, tp=tp, mode=dp.mode, z0=z0t,
-                                                  return_state=True)
+        loss, y, zT = engine.clipper_asym_mse_esr(theta6, xv, tgt, fs, skip=skip, tp=tp, mode=mode, z0=z0t, return_state=True, r=rseq)
         self.last_state, self.last_output = zT.reshape(1, -1), y.as_subclass(tf.Tensor)
         return loss.as_subclass(tf.Tensor)
 

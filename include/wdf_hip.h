@@ -636,6 +636,38 @@ int wdf_clipper_asym_step_esr(const float* x, float* theta6, float fs, int mode,
                               float beta2, float eps, const float* lo, const float* hi, void* stream);
 int wdf_asym_esr_finish(const float* sums14, double n_global, double eps_energy, float* gtheta6, float* loss3, void* stream);
 
+/* One pot resistance per SEQUENCE (clipper_pot.py's dataset: the pot is constant along a recording, dataimport.py:96): the
+ * twins of the five entry points above, each its static twin's argument list with rseq behind x.  The contract:
+ *   rseq     device float[B]; rseq[b] > 0 is the source resistance of sequence b, constant over its T steps.  The port constants
+ *            are evaluated once per sequence ahead of the time loop; nothing about the pot is evaluated per step.
+ *   theta6   theta6[4] is IGNORED and NEVER WRITTEN, by the kernels and by the in-kernel Adam update alike (its lane leaves
+ *            before it touches value or moments: theta6[4], m[4], v[4] are bit-for-bit what they were).
+ *   gradient component 4 (gtheta6[4], out7[5], sums14[6] and sums14[12]) is exactly 0: the pot is data, not a parameter.
+ *            Component 5 is dL/dC with the chain rule Rp, p -> C applied per sequence under its own pot, ahead of any sum
+ *            over sequences; components 0..3 are the static twins'.
+ * Both NEWTON modes; WDF_ASYM_OMEGA_F32 (a model approximation kept for comparison) is rejected with WDF_EINVAL, and so is
+ * rseq == NULL.  Everything else -- arguments, their checks, chunks, verification, status words, the gated repair launch, z0 / zT
+ * -- is the static twin's, and so is the workspace: the static twins' *_ws_bytes functions size it.  With all rseq[b] equal to
+ * theta6[4] the results are the static twins' to rounding.  Additions to ABI 6: no existing signature changed. */
+int wdf_clipper_asym_fwd_rseq(const float* x, const float* rseq, const float* theta6, float fs, int mode, double tol, int max_iter,
+                              float* y, float* zstash, const float* z0, float* zT, long long* iters, int64_t B, int64_t T, void* stream);
+int wdf_clipper_asym_fwd_tp_rseq(const float* x, const float* rseq, const float* theta6, float fs, int mode, double tol, int max_iter,
+                                 float* y, float* zstash, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                                 float verify_tol, void* ws, void* status, void* stream);
+int wdf_clipper_asym_bwd_tp_rseq(const float* x, const float* rseq, const float* theta6, float fs, int mode, const float* zstash,
+                                 const float* zT, const float* gy, const float* gzT, void* ws, float* gtheta6, float* gz0, int64_t B,
+                                 int64_t T, int n_chunks, void* stream);
+int wdf_clipper_asym_step_mse_rseq(const float* x, const float* rseq, float* theta6, float fs, int mode, double tol, int max_iter,
+                                   const float* target, float gscale, float* y, const float* z0, float* zT, int64_t B, int64_t T,
+                                   int n_chunks, int warmup, float verify_tol, void* ws, void* status, float* out7, float* m, float* v,
+                                   int32_t* step, const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi,
+                                   void* stream);
+int wdf_clipper_asym_step_esr_rseq(const float* x, const float* rseq, float* theta6, float fs, int mode, double tol, int max_iter,
+                                   const float* target, double n_global, double eps_energy, int64_t skip, float* y, const float* z0,
+                                   float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float verify_tol, void* ws, void* status,
+                                   float* sums14, float* gtheta6, float* loss3, float* m, float* v, int32_t* step, const float* lr,
+                                   float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream);
+
 /* Element-wise diode-pair root and Wright omega on device arrays (n elements): the
  * building blocks above, exposed for parity tests against diode_pretraining.py:39-60 /
  * toms917.cpp.  R_port is the port resistance seen by the root (P1.R).
