@@ -24,6 +24,13 @@
 //
 // Launches per step: ss_nl_step_kernel, ss_nl_step_finish_kernel (+ the probe, wdf_ss_step.h, which also carries the
 // optimizers' queued updates): three.
+//
+// LOSS = 1: the scripts' training loss (clipper_pot.py:141-177) on the rows t >= skip,  mse + esr = S / n + sqrt(S / (E + eps) / n)
+// with S = sum e^2, E = sum y^2, n = B (T - skip).  dLoss/dy = ga e + gb y, and ga, gb depend on the GLOBAL S and E, so the pass
+// carries two families of sums -- P with weight e (the MSE step's, unscaled) and Q with weight y -- and the launch's last wave
+// forms ga P + gb Q per coefficient before the chain rule (wdf_clipper_fused.h and wdf_asym_step.h do the same for the clippers).
+// A row before skip has weight 0 in every sum (t is the same for a whole wave: a scalar select, no branch); state, tangents,
+// Psi, y, snapshots and the warm-up prediction do not know about the loss.
 #pragma once
 #include "wdf_ss_step.h"
 
@@ -41,13 +48,16 @@ struct NlStepCtl {                 // 128 bytes, device resident
 };
 static_assert(sizeof(NlStepCtl) == 128, "NlStepCtl is 128 bytes");
 
-template <int NS, int NI>
+template <int NS, int NI, int LOSS = 0>
 struct NlDims {
     using C = SSCoef<NS, NI>;
     static constexpr int nT = C::oCy + 2;                        // tangents: A, Bx, E, ca, da entries, then L and V
     static constexpr int nG = C::kN + 2;                         // gradient entries: every coefficient, then L and V
-    static constexpr int nRec = 2 * NS + NS * NS + nT * NS + NS; // zwarm, zend, Psi_end, S0_end, H
-    static constexpr int oZw = 0, oZe = NS, oPsi = 2 * NS, oS = oPsi + NS * NS, oH = oS + nT * NS;
+    static constexpr int nRec = 2 * NS + NS * NS + nT * NS + NS + (LOSS ? NS : 0);   // zwarm, zend, Psi_end, S0_end, H (, HQ)
+    static constexpr int oZw = 0, oZe = NS, oPsi = 2 * NS, oS = oPsi + NS * NS, oH = oS + nT * NS, oHQ = oH + NS;
+    static constexpr int nQ = LOSS ? nG : 1, nHQ = LOSS ? NS : 1;           // the Q family's accumulators (placeholders without it)
+    static constexpr int nAcc = LOSS ? 2 * nG + 2 : nG + 1;                 // a chunk's / group's sums: {GP[nG], S} (, GQ[nG], E)
+    static constexpr int oQ = nG + 1;                                       // where GQ begins in them
     static constexpr int nSnap = NS + nT * NS + NS * NS;         // z, S (S0 until the finishing kernel adds Psi S_start), Psi
     static constexpr int sZ = 0, sS = NS, sPsi = NS + nT * NS;
     __host__ __device__ static constexpr int gidx(int c) { return c < C::oCy ? c : C::kN + (c - C::oCy); }
@@ -65,8 +75,8 @@ struct NlStepArgs {
     float* coef_prev;          // [kN + 2]: the coefficients, L, V of the previous call (what the snapshots were taken with)
     float* rec;                // [K][nRec][B]
     float* snap;               // [2][K][nSnap][B]
-    double* gpart;             // [K][groups][nG + 1]: the chunks' own sums
-    double* part;              // [groups][nG + 1]
+    double* gpart;             // [K][groups][nAcc]: the chunks' own sums
+    double* part;              // [groups][nAcc + 2]
     unsigned* ticket;
     const double* jac;         // [kN + 1][n_tree] (row kN: the port resistance)
     float* out;                // [1 + n_tree + 2]
@@ -75,6 +85,26 @@ struct NlStepArgs {
     int K, groups, n_tree, n_up, n_down;
     float gscale;
 };
+// what LOSS = 1 takes besides (a struct of its own: the MSE kernels' argument segment stays what it was)
+struct NlStepArgsEsr : NlStepArgs {
+    int64_t skip;              // rows t < skip count for nothing
+    double eps;                // added to E
+    float* loss3;              // <- {mse, esr, mse + esr}
+};
+template <int LOSS> struct NlArgs { using type = NlStepArgs; };
+template <> struct NlArgs<1> { using type = NlStepArgsEsr; };
+// the scale of the P family: the MSE step's gscale; 1 with LOSS = 1 (the scale is not known before S and E are global)
+template <int LOSS, class A> __device__ __forceinline__ float nl_gs(const A& a)
+{
+    if constexpr (LOSS != 0) return 1.0f;
+    else return a.gscale;
+}
+// the weight of row t: 0 before skip (LOSS = 1; the same for a whole wave)
+template <int LOSS, class A> __device__ __forceinline__ float nl_on(const A& a, int64_t t)
+{
+    if constexpr (LOSS != 0) return t < a.skip ? 0.0f : 1.0f;
+    else return 1.0f;
+}
 
 template <int NS, int NI, typename V, bool PSI>
 struct NlU {
@@ -131,10 +161,12 @@ __device__ __forceinline__ void nl_z_step(const SSCoef<NS, NI>& c, const SSDiode
 }
 
 // one step with tangents -> y.  gs = gscale (0 on a padding lane), lv = 1 (0 on a padding lane).
+// LOSS = 1: gs = lv = 1 on a live lane of a row past skip, else 0; G, H, sse take the weight e unscaled, GQ, HQ, see the weight y.
 // FAST (with SYM): the kernel has checked that omega_1's argument never leaves the series-only region (diode_pair, wdf_omega.h).
-template <int NS, int NI, bool SYM, typename V, bool PSI, int FAST = 0>
+template <int NS, int NI, bool SYM, typename V, bool PSI, int FAST = 0, int LOSS = 0>
 __device__ __forceinline__ V nl_step(const SSCoef<NS, NI>& c, const SSDiode& dp, const V (&x)[NI], V tgt, float gs, float lv,
-                                     NlU<NS, NI, V, PSI>& u, V (&G)[NlDims<NS, NI>::nG], V (&H)[NS], V& sse)
+                                     NlU<NS, NI, V, PSI>& u, V (&G)[NlDims<NS, NI>::nG], V (&H)[NS], V& sse,
+                                     V (&GQ)[NlDims<NS, NI, LOSS>::nQ], V (&HQ)[NlDims<NS, NI, LOSS>::nHQ], V& see)
 {
     using C = SSCoef<NS, NI>;
     using D = NlDims<NS, NI>;
@@ -180,20 +212,35 @@ __device__ __forceinline__ V nl_step(const SSCoef<NS, NI>& c, const SSDiode& dp,
     // M = A + E (Da ca)^T: the step's Jacobian; gw = g (cy + fy Da ca): dLoss/dz through y
     V M[NS][NS], gw[NS];
     const V gf = g * c.v[C::oFy];
+    // the Q family: the same construction with y in place of g
+    V gq = zero, gfq = zero, gwq[NS];
+    if constexpr (LOSS != 0) {
+        gq = yv * gs;
+        gfq = gq * c.v[C::oFy];
+        see = vfma(gq, yv, see);
+    }
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
         const V dq = Da * c.v[C::oCa + q];
         gw[q] = vfma(gf, dq, g * c.v[C::oCy + q]);
+        if constexpr (LOSS != 0) gwq[q] = vfma(gfq, dq, gq * c.v[C::oCy + q]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) M[s][q] = vfma(dq, c.v[C::oE + s], vsplat<V>(c.v[C::oA + s * NS + q]));
     }
     // every tangent: G += gw.S + gf beta;  S' = M S + E beta + direct
-    auto advance = [&](V (&S)[NS], V& Gc, V beta, bool has_beta, int di, V dv) {
+    auto advance = [&](V (&S)[NS], V& Gc, V& Qc, V beta, bool has_beta, int di, V dv) {
         V acc = Gc;
 #pragma unroll
         for (int s = 0; s < NS; ++s) acc = vfma(gw[s], S[s], acc);
         if (has_beta) acc = vfma(gf, beta, acc);
         Gc = acc;
+        if constexpr (LOSS != 0) {
+            V aq = Qc;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) aq = vfma(gwq[s], S[s], aq);
+            if (has_beta) aq = vfma(gfq, beta, aq);
+            Qc = aq;
+        }
         V sn[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -206,25 +253,26 @@ __device__ __forceinline__ V nl_step(const SSCoef<NS, NI>& c, const SSDiode& dp,
 #pragma unroll
         for (int s = 0; s < NS; ++s) S[s] = sn[s];
     };
+    auto Q = [&](int i) -> V& { return GQ[LOSS ? i : 0]; };      // (the Q accumulator beside G[i]; a placeholder without the family)
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
-        for (int j = 0; j < NS; ++j) advance(u.S[C::oA + i * NS + j], G[C::oA + i * NS + j], zero, false, i, u.z[j]);
+        for (int j = 0; j < NS; ++j) advance(u.S[C::oA + i * NS + j], G[C::oA + i * NS + j], Q(C::oA + i * NS + j), zero, false, i, u.z[j]);
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
-        for (int j = 0; j < NI; ++j) advance(u.S[C::oB + i * NI + j], G[C::oB + i * NI + j], zero, false, i, x[j]);
+        for (int j = 0; j < NI; ++j) advance(u.S[C::oB + i * NI + j], G[C::oB + i * NI + j], Q(C::oB + i * NI + j), zero, false, i, x[j]);
 #pragma unroll
-    for (int i = 0; i < NS; ++i) advance(u.S[C::oE + i], G[C::oE + i], zero, false, i, b);
+    for (int i = 0; i < NS; ++i) advance(u.S[C::oE + i], G[C::oE + i], Q(C::oE + i), zero, false, i, b);
 #pragma unroll
-    for (int s = 0; s < NS; ++s) advance(u.S[C::oCa + s], G[C::oCa + s], Da * u.z[s], true, -1, zero);
+    for (int s = 0; s < NS; ++s) advance(u.S[C::oCa + s], G[C::oCa + s], Q(C::oCa + s), Da * u.z[s], true, -1, zero);
 #pragma unroll
-    for (int i = 0; i < NI; ++i) advance(u.S[C::oDa + i], G[C::oDa + i], Da * x[i], true, -1, zero);
-    advance(u.S[C::oCy + 0], G[C::kN + 0], DL, true, -1, zero);
-    advance(u.S[C::oCy + 1], G[C::kN + 1], DV, true, -1, zero);
+    for (int i = 0; i < NI; ++i) advance(u.S[C::oDa + i], G[C::oDa + i], Q(C::oDa + i), Da * x[i], true, -1, zero);
+    advance(u.S[C::oCy + 0], G[C::kN + 0], Q(C::kN + 0), DL, true, -1, zero);
+    advance(u.S[C::oCy + 1], G[C::kN + 1], Q(C::kN + 1), DV, true, -1, zero);
     if constexpr (PSI) {
 #pragma unroll
-        for (int j = 0; j < NS; ++j) advance(u.P[j], H[j], zero, false, -1, zero);
+        for (int j = 0; j < NS; ++j) advance(u.P[j], H[j], HQ[LOSS ? j : 0], zero, false, -1, zero);
     }
     // the coefficients y sees directly
 #pragma unroll
@@ -232,6 +280,13 @@ __device__ __forceinline__ V nl_step(const SSCoef<NS, NI>& c, const SSDiode& dp,
 #pragma unroll
     for (int i = 0; i < NI; ++i) G[C::oDy + i] = vfma(g, x[i], G[C::oDy + i]);
     G[C::oFy] = vfma(g, b, G[C::oFy]);
+    if constexpr (LOSS != 0) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) GQ[C::oCy + s] = vfma(gq, u.z[s], GQ[C::oCy + s]);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) GQ[C::oDy + i] = vfma(gq, x[i], GQ[C::oDy + i]);
+        GQ[C::oFy] = vfma(gq, b, GQ[C::oFy]);
+    }
     // the state
     V zn[NS];
 #pragma unroll
@@ -251,11 +306,11 @@ __device__ __forceinline__ V nl_step(const SSCoef<NS, NI>& c, const SSDiode& dp,
 
 // ---- the chunks ------------------------------------------------------------------------------------------------------
 // 256-thread workgroups (four chunks of four neighbouring groups): single-wave workgroups land unevenly on the SIMDs.
-template <int NS, int NI, bool SYM, typename V, int FAST>
-__device__ __forceinline__ void nl_chunk(const NlStepArgs& a, const SSCoef<NS, NI>& c, const SSDiode& dp)
+template <int NS, int NI, bool SYM, typename V, int FAST, int LOSS = 0>
+__device__ __forceinline__ void nl_chunk(const typename NlArgs<LOSS>::type& a, const SSCoef<NS, NI>& c, const SSDiode& dp)
 {
     using C = SSCoef<NS, NI>;
-    using D = NlDims<NS, NI>;
+    using D = NlDims<NS, NI, LOSS>;
     constexpr int WD = LinWidth<V>::w;
     const V zero = vsplat<V>(0.0f);
     const int lane = threadIdx.x & 63;
@@ -287,15 +342,20 @@ __device__ __forceinline__ void nl_chunk(const NlStepArgs& a, const SSCoef<NS, N
         }
     }
     u.start();
-    const float gs = live ? a.gscale : 0.0f, lv = live ? 1.0f : 0.0f;
+    const float gs = live ? nl_gs<LOSS>(a) : 0.0f, lv = live ? 1.0f : 0.0f;
     V G[D::nG], H[NS], sse = zero;
-    double acc[D::nG + 1];
+    V GQ[D::nQ], HQ[D::nHQ], see = zero;                          // (LOSS = 1: the Q family)
+    double acc[D::nAcc];
 #pragma unroll
     for (int i = 0; i < D::nG; ++i) G[i] = zero;
 #pragma unroll
     for (int s = 0; s < NS; ++s) H[s] = zero;
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i) acc[i] = 0.0;
+    for (int i = 0; i < D::nQ; ++i) GQ[i] = zero;
+#pragma unroll
+    for (int s = 0; s < D::nHQ; ++s) HQ[s] = zero;
+#pragma unroll
+    for (int i = 0; i < D::nAcc; ++i) acc[i] = 0.0;
     float* __restrict__ rk = a.rec + ((size_t)k * D::nRec) * B + b;
     V xn[kLinBlk][NI], tn[kLinBlk];
     auto load_blk = [&](int64_t ts) {
@@ -343,14 +403,16 @@ __device__ __forceinline__ void nl_chunk(const NlStepArgs& a, const SSCoef<NS, N
             // next step's diode pair (a padding lane repeats the last sequence: its stores write the same values again)
 #pragma unroll
             for (int i = 0; i < kLinBlk; ++i) {
-                const V yv = nl_step<NS, NI, SYM, V, true, FAST>(c, dp, xc[i], tc[i], gs, lv, u, G, H, sse);
+                const float on = nl_on<LOSS>(a, ts + i);
+                const V yv = nl_step<NS, NI, SYM, V, true, FAST, LOSS>(c, dp, xc[i], tc[i], LOSS ? gs * on : gs, LOSS ? lv * on : lv, u, G, H, sse, GQ, HQ, see);
                 lin_st_nt<V>(a.y + (ts + i) * B + b, yv);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < kLinBlk; ++i) {
                 if (i >= n) break;
-                const V yv = nl_step<NS, NI, SYM, V, true, FAST>(c, dp, xc[i], tc[i], gs, lv, u, G, H, sse);
+                const float on = nl_on<LOSS>(a, ts + i);
+                const V yv = nl_step<NS, NI, SYM, V, true, FAST, LOSS>(c, dp, xc[i], tc[i], LOSS ? gs * on : gs, LOSS ? lv * on : lv, u, G, H, sse, GQ, HQ, see);
                 if (live) lin_st_nt<V>(a.y + (ts + i) * B + b, yv);
             }
         }
@@ -360,11 +422,22 @@ __device__ __forceinline__ void nl_chunk(const NlStepArgs& a, const SSCoef<NS, N
             for (int i = 0; i < D::nG; ++i) { acc[i] += lin_hsum(G[i]); G[i] = zero; }
             acc[D::nG] += lin_hsum(sse);
             sse = zero;
+            if constexpr (LOSS != 0) {
+#pragma unroll
+                for (int i = 0; i < D::nG; ++i) { acc[D::oQ + i] += lin_hsum(GQ[i]); GQ[i] = zero; }
+                acc[D::oQ + D::nG] += lin_hsum(see);
+                see = zero;
+            }
         }
     }
 #pragma unroll
     for (int i = 0; i < D::nG; ++i) acc[i] += lin_hsum(G[i]);
     acc[D::nG] += lin_hsum(sse);
+    if constexpr (LOSS != 0) {
+#pragma unroll
+        for (int i = 0; i < D::nG; ++i) acc[D::oQ + i] += lin_hsum(GQ[i]);
+        acc[D::oQ + D::nG] += lin_hsum(see);
+    }
     if (live) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) lin_st<V>(rk + (size_t)(D::oZe + s) * B, u.z[s]);
@@ -378,10 +451,14 @@ __device__ __forceinline__ void nl_chunk(const NlStepArgs& a, const SSCoef<NS, N
             for (int s = 0; s < NS; ++s) lin_st<V>(rk + (size_t)(D::oS + cc * NS + s) * B, u.S[cc][s]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) lin_st<V>(rk + (size_t)(D::oH + s) * B, H[s]);
-    }
-    double* gp = a.gpart + ((size_t)k * a.groups + grp) * (D::nG + 1);
+        if constexpr (LOSS != 0) {
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i) {
+            for (int s = 0; s < NS; ++s) lin_st<V>(rk + (size_t)(D::oHQ + s) * B, HQ[s]);
+        }
+    }
+    double* gp = a.gpart + ((size_t)k * a.groups + grp) * D::nAcc;
+#pragma unroll
+    for (int i = 0; i < D::nAcc; ++i) {
         const double s = wave_sum_dpp(acc[i]);
         if (lane == 0) gp[i] = s;
     }
@@ -390,8 +467,8 @@ __device__ __forceinline__ void nl_chunk(const NlStepArgs& a, const SSCoef<NS, N
 #ifndef WDF_NL_WAVES
 #define WDF_NL_WAVES 1
 #endif
-template <int NS, int NI, bool SYM, typename V>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WDF_NL_WAVES, WDF_NL_WAVES))) void ss_nl_step_kernel(const NlStepArgs a)
+template <int NS, int NI, bool SYM, typename V, int LOSS = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WDF_NL_WAVES, WDF_NL_WAVES))) void ss_nl_step_kernel(const typename NlArgs<LOSS>::type a)
 {
     SSCoef<NS, NI> c;
     c.load(a.coef);
@@ -402,15 +479,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WDF_NL_WAVE
         // (u1 <= L - log N: a fact about the circuit, the same for every lane)
         const float l0 = dp.L - dp.d.l_dn;
         if (l0 <= -7.5f && l0 >= -80.0f) {                     // the LEAN root tier (round 6, wdf_omega.h): every practical diode
-            nl_chunk<NS, NI, SYM, V, kRootLean>(a, c, dp);
+            nl_chunk<NS, NI, SYM, V, kRootLean, LOSS>(a, c, dp);
             return;
         }
         if (l0 <= kSeriesOnlyBelow) {
-            nl_chunk<NS, NI, SYM, V, kRootFast>(a, c, dp);
+            nl_chunk<NS, NI, SYM, V, kRootFast, LOSS>(a, c, dp);
             return;
         }
     }
-    nl_chunk<NS, NI, SYM, V, kRootGeneral>(a, c, dp);
+    nl_chunk<NS, NI, SYM, V, kRootGeneral, LOSS>(a, c, dp);
 }
 
 // ---- the finish: verify the boundaries, walk the tangents, re-run what missed, reduce, chain rule, steer -----------------
@@ -419,14 +496,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WDF_NL_WAVE
 // sequences.  A tile of chunk records goes through LDS (one round trip to memory per tile instead of one per chunk, and the
 // next tile's loads are in flight while this one is walked); every thread walks the whole tile -- a few dozen FMAs -- and
 // keeps the start of its own chunk.  Wave 0 finishes: the repair of a group that missed, the sums, the ticket.
-template <int NS, int WD> struct NlTile { static constexpr int n = (NS == 1 ? 8 : 4) / WD; };   // (at most 512 threads: 256 VGPRs for the repair path; the records fit 64 KB of LDS)
+// (at most 512 threads: 256 VGPRs for the repair path; the records fit 64 KB of LDS.  LOSS = 1 doubles the sums every thread
+//  holds: at most 256 threads, so that the registers of a whole SIMD are one wave's)
+template <int NS, int WD, int LOSS = 0> struct NlTile { static constexpr int n = (NS == 1 && LOSS == 0 ? 8 : 4) / WD; };
+// LOSS = 1 runs two sequences per lane on the smallest tree only: with a second state or source the doubled accumulators of
+// a pair of sequences do not fit the 512 registers of a wave
+template <int NS, int NI, int LOSS> struct NlPairs { static constexpr bool ok = LOSS == 0 || NS * NI == 1; };
+// ... and is not built for two states WITH two sources: its chunk and finish kernels would not fit the registers without scratch
+template <int NS, int NI, int LOSS> struct NlBuilt { static constexpr bool ok = LOSS == 0 || NS * NI < 4; };
 
-template <int NS, int NI, bool SYM, int WD>
-__global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_finish_kernel(const NlStepArgs a)
+template <int NS, int NI, bool SYM, int WD, int LOSS = 0>
+__global__ __launch_bounds__((64 * WD * NlTile<NS, WD, LOSS>::n)) void ss_nl_step_finish_kernel(const typename NlArgs<LOSS>::type a)
 {
-    constexpr int kNlTile = NlTile<NS, WD>::n, kWaves = WD * kNlTile;
+    constexpr int kNlTile = NlTile<NS, WD, LOSS>::n, kWaves = WD * kNlTile;
     using C = SSCoef<NS, NI>;
-    using D = NlDims<NS, NI>;
+    using D = NlDims<NS, NI, LOSS>;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = wv % kNlTile, hq = wv / kNlTile;
     const int64_t grp = blockIdx.x, B = a.B;
     const int K = a.K;
@@ -443,17 +527,20 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
         for (int i = 0; i < C::kN; ++i) pre.coef[i] = a.coef[i];
         pre.Is = *a.pIs; pre.V = *a.pV; pre.Rp = *a.pRp;
     }
-    double gpre[D::nG + 1];                                       // the chunks' own sums of this group (lane k: chunk k)
+    constexpr bool kPre = LOSS == 0 || NS == 1;                   // (two states and both families: no registers for the early fetch)
+    double gpre[kPre ? D::nAcc : 1];                              // the chunks' own sums of this group (lane k: chunk k)
+    if constexpr (kPre) {
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i)
-        gpre[i] = (wv == 0 && lane < a.K) ? a.gpart[((size_t)lane * a.groups + grp) * (D::nG + 1) + i] : 0.0;
+        for (int i = 0; i < D::nAcc; ++i)
+            gpre[i] = (wv == 0 && lane < a.K) ? a.gpart[((size_t)lane * a.groups + grp) * D::nAcc + i] : 0.0;
+    }
     __shared__ float recs[WD][kNlTile][D::nRec][64];
-    __shared__ double red[kWaves][D::nG + 1];
+    __shared__ double red[kWaves][D::nAcc];
     __shared__ int rbad[kWaves];
     __shared__ float rmiss[kWaves];
-    double tot[D::nG + 1];
+    double tot[D::nAcc];
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i) tot[i] = 0.0;
+    for (int i = 0; i < D::nAcc; ++i) tot[i] = 0.0;
     float miss = 0.0f;
     int nbad = 0;
     {
@@ -549,6 +636,12 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
 #pragma unroll
                     for (int s = 0; s < NS; ++s) d = fmaf(recs[hq][q][D::oH + s][lane], Ss[cc][s], d);
                     tot[D::gidx(cc)] += live ? (double)d : 0.0;
+                    if constexpr (LOSS != 0) {                    // ... and to the Q family: HQ . S_start
+                        float dq = 0.0f;
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) dq = fmaf(recs[hq][q][D::oHQ + s][lane], Ss[cc][s], dq);
+                        tot[D::oQ + D::gidx(cc)] += live ? (double)dq : 0.0;
+                    }
                 }
                 if (fix) {                                        // S0 + Psi S_start, in place
                     float* sp = a.snap + (((size_t)par * K + (k + 1)) * D::nSnap) * B + b;
@@ -571,7 +664,7 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
         const int wb = wave_sum_dpp(nbad);
         const float wm = wave_max_dpp(miss);
 #pragma unroll
-        for (int i = 0; i <= D::nG; ++i) {
+        for (int i = 0; i < D::nAcc; ++i) {
             const double s = wave_sum_dpp(tot[i]);
             if (lane == 0) red[wv][i] = s;
         }
@@ -584,7 +677,7 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
 #pragma unroll
     for (int j = 0; j < kWaves; ++j) { nbad_all += rbad[j]; miss_all = fmaxf(miss_all, rmiss[j]); }
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i) {
+    for (int i = 0; i < D::nAcc; ++i) {
         double s = 0.0;
 #pragma unroll
         for (int j = 0; j < kWaves; ++j) s += red[j][i];
@@ -595,9 +688,11 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
     if (wbad == 0) {
         // the chunks' own sums of this group (lanes over chunks), then one value per accumulator in every lane
 #pragma unroll
-        for (int i = 0; i <= D::nG; ++i) {
-            double s = gpre[i];
-            for (int k = lane + 64; k < K; k += 64) s += a.gpart[((size_t)k * a.groups + grp) * (D::nG + 1) + i];
+        for (int i = 0; i < D::nAcc; ++i) {
+            double s;
+            if constexpr (kPre) s = gpre[i];
+            else s = lane < K ? a.gpart[((size_t)lane * a.groups + grp) * D::nAcc + i] : 0.0;
+            for (int k = lane + 64; k < K; k += 64) s += a.gpart[((size_t)k * a.groups + grp) * D::nAcc + i];
             tot[i] += wave_sum_dpp(s);
         }
     } else {
@@ -607,20 +702,27 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
         SSDiode dp = {};
         nl_load_diode(a, dp);
 #pragma unroll
-        for (int i = 0; i <= D::nG; ++i) tot[i] = 0.0;
+        for (int i = 0; i < D::nAcc; ++i) tot[i] = 0.0;
         for (int h = 0; h < WD; ++h) {                            // (one wave: a miss is rare, and the registers of the walk
                                                                   //  above would not survive a second copy of this loop's)
             const int64_t b_raw = (grp * 64 + lane) * WD + h;
             const bool live = b_raw < B;
             const int64_t b = live ? b_raw : B - 1;
-            const float gs = live ? a.gscale : 0.0f, lv = live ? 1.0f : 0.0f;
+            const float gs = live ? (LOSS != 0 ? 1.0f : a.gscale) : 0.0f, lv = live ? 1.0f : 0.0f;   // (nl_gs, spelled out: see below)
             NlU<NS, NI, float, false> u;
 #pragma unroll
             for (int s = 0; s < NS; ++s) u.z[s] = 0.0f;
             u.start();
             float G[D::nG], Hd[NS] = {}, sse = 0.0f;
+            float GQ[D::nQ], HQd[D::nHQ] = {}, see = 0.0f;
 #pragma unroll
             for (int i = 0; i < D::nG; ++i) G[i] = 0.0f;
+            // (LOSS = 0 never reads its placeholder.  Zeroing it, or reading gscale through nl_gs, leaves the MSE kernels'
+            //  instructions what they were but not their register allocation; written this way they are the same bytes)
+            if constexpr (LOSS != 0) {
+#pragma unroll
+                for (int i = 0; i < D::nQ; ++i) GQ[i] = 0.0f;
+            }
             int since = 0;
             for (int64_t ts = 0; ts < a.T; ts += kLinBlk) {
                 const int n = a.T - ts < kLinBlk ? (int)(a.T - ts) : kLinBlk;
@@ -641,7 +743,8 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
 #pragma unroll
                 for (int i = 0; i < kLinBlk; ++i) {
                     if (i >= n) break;
-                    const float yv = nl_step<NS, NI, SYM, float, false>(c, dp, xs[i], tg[i], gs, lv, u, G, Hd, sse);
+                    const float on = nl_on<LOSS>(a, ts + i);
+                    const float yv = nl_step<NS, NI, SYM, float, false, 0, LOSS>(c, dp, xs[i], tg[i], LOSS ? gs * on : gs, LOSS ? lv * on : lv, u, G, Hd, sse, GQ, HQd, see);
                     if (live) a.y[(ts + i) * B + b] = yv;
                 }
                 if (++since == 4) {
@@ -650,23 +753,34 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
                     for (int i = 0; i < D::nG; ++i) { tot[i] += (double)G[i]; G[i] = 0.0f; }
                     tot[D::nG] += (double)sse;
                     sse = 0.0f;
+                    if constexpr (LOSS != 0) {
+#pragma unroll
+                        for (int i = 0; i < D::nG; ++i) { tot[D::oQ + i] += (double)GQ[i]; GQ[i] = 0.0f; }
+                        tot[D::oQ + D::nG] += (double)see;
+                        see = 0.0f;
+                    }
                 }
             }
 #pragma unroll
             for (int i = 0; i < D::nG; ++i) tot[i] += (double)G[i];
             tot[D::nG] += (double)sse;
+            if constexpr (LOSS != 0) {
+#pragma unroll
+                for (int i = 0; i < D::nG; ++i) tot[D::oQ + i] += (double)GQ[i];
+                tot[D::oQ + D::nG] += (double)see;
+            }
         }
 #pragma unroll
-        for (int i = 0; i <= D::nG; ++i) tot[i] = wave_sum_dpp(tot[i]);
+        for (int i = 0; i < D::nAcc; ++i) tot[i] = wave_sum_dpp(tot[i]);
     }
     // ---- this group's partial {sums.., bad boundaries, largest miss}; the last wave adds them up in a fixed order
-    constexpr int kPart = D::nG + 3;
+    constexpr int kPart = D::nAcc + 2;
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i <= D::nG; ++i)
+        for (int i = 0; i < D::nAcc; ++i)
             __hip_atomic_store(a.part + (size_t)grp * kPart + i, tot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.part + (size_t)grp * kPart + D::nG + 1, (double)wbad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.part + (size_t)grp * kPart + D::nG + 2, (double)wmiss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.part + (size_t)grp * kPart + D::nAcc, (double)wbad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.part + (size_t)grp * kPart + D::nAcc + 1, (double)wmiss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     unsigned old = 0;
@@ -674,24 +788,35 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
     old = __builtin_amdgcn_readfirstlane(old);
     if (old != (unsigned)(a.groups - 1)) return;
     if (lane == 0) *a.ticket = 0u;
-    double sum[D::nG + 1], nbd = 0.0, ggd = 0.0;
+    double sum[D::nAcc], nbd = 0.0, ggd = 0.0;
     float mm = 0.0f;
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i) sum[i] = 0.0;
+    for (int i = 0; i < D::nAcc; ++i) sum[i] = 0.0;
     for (int64_t w = lane; w < a.groups; w += 64) {
         double v[kPart];
 #pragma unroll
         for (int i = 0; i < kPart; ++i) v[i] = __hip_atomic_load(a.part + (size_t)w * kPart + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-        for (int i = 0; i <= D::nG; ++i) sum[i] += v[i];
-        nbd += v[D::nG + 1];
-        ggd += v[D::nG + 1] > 0.0 ? 1.0 : 0.0;
-        mm = fmaxf(mm, (float)v[D::nG + 2]);
+        for (int i = 0; i < D::nAcc; ++i) sum[i] += v[i];
+        nbd += v[D::nAcc];
+        ggd += v[D::nAcc] > 0.0 ? 1.0 : 0.0;
+        mm = fmaxf(mm, (float)v[D::nAcc + 1]);
     }
 #pragma unroll
-    for (int i = 0; i <= D::nG; ++i) sum[i] = wave_sum_dpp(sum[i]);
+    for (int i = 0; i < D::nAcc; ++i) sum[i] = wave_sum_dpp(sum[i]);
     const int nb = (int)wave_sum_dpp(nbd), gg = (int)wave_sum_dpp(ggd);
     mm = wave_max_dpp(mm);
+    // LOSS = 1: the loss and its coefficients from the global sums (esr_coef_kernel's formulas, wdf_elementwise.h), then
+    // ga P + gb Q per coefficient -- from here on sum[0 .. nG) is dLoss/d coefficient as in the MSE step
+    double mse = 0.0, esr = 0.0;
+    if constexpr (LOSS != 0) {
+        const double Ssum = sum[D::nG], En = sum[D::oQ + D::nG] + a.eps, n = (double)a.B * (double)(a.T - a.skip);
+        mse = Ssum / n;
+        esr = sqrt(Ssum / En / n);
+        const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * En * n) : 0.0), gb = -esr / En;
+#pragma unroll
+        for (int i = 0; i < D::nG; ++i) sum[i] = ga * sum[i] + gb * sum[D::oQ + i];
+    }
     // the root's own values (ss_grad_reduce_kernel's formulas): L = log(Rp Is / V)
     const double Is = pre.Is, Vv = pre.V, Rp = pre.Rp;
     const double sL = sum[C::kN], sV = sum[C::kN + 1];
@@ -704,7 +829,11 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD>::n)) void ss_nl_step_fini
     }
     if (lane == 0) {
         a.out[0] = (float)sum[D::nG];
-        if (a.loss) *a.loss = (float)(0.5 * (double)a.gscale * sum[D::nG]);
+        if constexpr (LOSS != 0) {
+            a.loss3[0] = (float)mse; a.loss3[1] = (float)esr; a.loss3[2] = (float)(mse + esr);
+        } else {
+            if (a.loss) *a.loss = (float)(0.5 * (double)a.gscale * sum[D::nG]);
+        }
         a.out[1 + a.n_tree] = (float)(sL / Is);
         a.out[2 + a.n_tree] = (float)(sV - sL / Vv);
         // what the snapshots of this call were taken with

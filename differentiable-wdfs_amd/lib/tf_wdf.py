@@ -18,7 +18,10 @@ New surface (not in the reference):
   Circuit(top, root, probe) / run(...) / Circuit.mse(x, target)
       the fast tier: lowers the WHOLE per-sample loop the scripts own (lpf.py:39-46,
       clipper_pot.py:113-124) to one HIP kernel launch, and its tape.gradient to one reverse
-      sweep.
+      sweep.  After Circuit.to_device() a small tree under a DiodePair root (one or two capacitors and sources: the HPF
+      diode clipper) evaluates Circuit.mse as a one-pass training step (csrc/wdf_ss_nl_step.h: forward, loss and every
+      gradient in one sweep, three launches per step); the same pass for the MSE + ESR loss exists
+      (Circuit._mse_esr_nl_step) and is not yet what Circuit.mse_esr takes.
 
 How the elements execute.  Every method below is plain wave arithmetic; the values flowing
 through are either

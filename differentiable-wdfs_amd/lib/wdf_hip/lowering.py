@@ -289,6 +289,7 @@ _NL_OCC = int(os.environ.get("WDF_NL_OCC", "1"))
 _NL_WMIN = int(os.environ.get("WDF_NL_WMIN", "16"))      # the shortest warm-up the device's controller may settle on
 _ROWS = 1024                                             # result rows per slab (see _LinResident.entry)
 NL_TOL = 1.0e-6                                          # boundary tolerance of the diode-root one-pass step (plan_ss_time_parallel's)
+ESR_EPS = float(np.finfo(float).eps)                     # what the scripts' esr_loss adds to the energy (clipper_pot.py:146-156)
 
 
 class _LinResident:
@@ -383,8 +384,12 @@ class _LinResident:
             self._hc_key, self._hc_val, self.plans = hv, (vals[:-1], float(vals[-1])), {}
         return self._hc_val
 
-    def entry(self, x, target):
-        ent = self.cache.get((x, target))
+    def entry(self, x, target, loss="mse", skip=0):
+        """The buffers of one training set: per (x, target) pair and -- for the diode-root step's MSE + ESR loss -- per
+        (loss, skip), so that an MSE and an ESR loop over the same data each keep their own workspace (snapshots, warm-up
+        control, chunk count)."""
+        extra = None if loss == "mse" else (loss, int(skip))
+        ent = self.cache.get((x, target), extra)
         if ent is None:
             circ, dev = self.circ, self.pb.block.device
             xd = x.as_subclass(torch.Tensor).to(dev).float()
@@ -396,6 +401,8 @@ class _LinResident:
             x_tm = xd.permute(1, 2, 0).contiguous()               # [T][ni][B]: once per training set
             tgt = target.as_subclass(torch.Tensor).to(dev).float().reshape(T, B).contiguous()
             per_wave = 128 if B % 2 == 0 else 64                  # (two sequences per lane when the rows pair up)
+            if loss != "mse" and circ.ns * circ.ni > 1:
+                per_wave = 64                                     # (the MSE + ESR step pairs them up on the smallest tree only)
             L_ = binding.lib()
             y = torch.empty((T, B), dtype=torch.float32, device=dev)
             if circ.root_kind == "DiodePair":
@@ -412,10 +419,12 @@ class _LinResident:
             # slab of _ROWS; a full slab is replaced by a fresh one and lives on for as long as anything still refers to
             # it): the loss history a script keeps (lpf.py:99 `losses.append(loss)`) and gradients read after the loop stay
             # what they were -- no copy per call, one allocation per _ROWS calls
+            # (a row of the MSE + ESR step: {S, gradients}, then {mse, esr, mse + esr})
             ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": y, "ws": ws,
-                                       "ring": torch.zeros((_ROWS, 2 + self.pb.n), dtype=torch.float32, device=dev), "turn": 0,
-                                       "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0},
-                                 nbytes=_nbytes(x_tm, tgt, y, ws))
+                                       "ring": torch.zeros((_ROWS, (2 if loss == "mse" else 4) + self.pb.n), dtype=torch.float32, device=dev),
+                                       "turn": 0, "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0,
+                                       "loss": loss, "skip": int(skip)},
+                                 extra, nbytes=_nbytes(x_tm, tgt, y, ws))
         return ent
 
     def _plan_nl(self, B, T, k, dev, cold_floor=0):
@@ -498,6 +507,19 @@ class _LinResident:
         row = ent["ring"][ent["turn"]]
         ent["turn"] += 1
         out, loss = row[:1 + n], row[1 + n]
+        if circ.root_kind == "DiodePair" and ent.get("loss", "mse") != "mse":
+            # MSE + ESR past skip (wdf_ss_nl_step_esr): out = {S, d(mse + esr)/d component value}, loss = mse + esr; the three
+            # terms stay in ent["loss3"] (a view of this call's row)
+            loss3 = row[1 + n:4 + n]
+            rc = binding.lib().wdf_ss_nl_step_esr(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.pb.block),
+                                                  binding._ptr(self.jac), self.n_tree, circ.ns, circ.ni, int(circ.root.N_up),
+                                                  int(circ.root.N_down), binding._ptr(ent["t"]), int(ent["skip"]), ESR_EPS,
+                                                  binding._ptr(ent["y"]), binding._ptr(ent["ws"]), binding._ptr(out),
+                                                  binding._ptr(loss3), B, T, ent["k"], binding._stream())
+            binding._check(rc, "wdf_ss_nl_step_esr")
+            self._watch(ent)
+            ent["loss3"] = loss3
+            return out, loss3[2]
         if circ.root_kind == "DiodePair":
             rc = binding.lib().wdf_ss_nl_step_mse(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.pb.block),
                                                   binding._ptr(self.jac), self.n_tree, circ.ns, circ.ni, int(circ.root.N_up),
@@ -883,12 +905,46 @@ class Circuit:
         if (getattr(self, "_pblock", None) is not None and isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)
                 and not self.force_generic):
             return self._loss_resident(x, target, "mse+esr", skip)
+        # (a resident small tree under a DiodePair root has a one-pass step for this loss too -- _nl_step_tree /
+        #  _mse_esr_nl_step, wdf_ss_nl_step_esr -- which this method does not take until tools/ss_nl_esr_step_bench.py has
+        #  shown it faster than the composed path below at both of its shapes)
         y = self(x)
         o = y[int(skip):]
         t = tf.convert(target, device=o.device).reshape(y.shape)[int(skip):]
         S, E = tf.reduce_sum(tf.square(o - t)), tf.reduce_sum(tf.square(o)) + float(np.finfo(float).eps)
         n = float(o.numel())
         return S / n + tf.sqrt(S / E / n)
+
+    def _mse_esr_nl_step(self, lin, x, target, skip):
+        """mse_esr(x, target, skip) of the resident tree `lin` as ONE pass (wdf_ss_nl_step_esr) through the MSE step's autograd
+        function: the loss carries the gradient the pass produced (`_wdf_fused`), the queued optimizer updates ride in its probe
+        launch, `last_output` is the step's y."""
+        with torch._C.DisableTorchFunctionSubclass():
+            lin.check()
+            ent = lin.entry(x, target, "mse+esr", int(skip))
+            live = [(i, v) for i, v in sorted(lin.pb.members.items()) if v.requires_grad]
+        loss, out = _LinResidentMseFn.apply(lin, ent, 1.0, [i for i, _ in live], None, False, *[v for _, v in live])
+        loss = loss.as_subclass(tf.Tensor)
+        loss._wdf_fused = (out, {id(v): i for i, v in live})
+        self.last_output = ent["y"]
+        return loss
+
+    def _nl_step_tree(self, x, target, skip=0, z0=None, carry_state=False):
+        """The resident tree whose one-pass MSE + ESR step (wdf_ss_nl_step_esr) can serve mse_esr(x, target, skip), or None: the
+        conditions under which mse() takes the diode-root step -- to_device() made a resident tree, DiodePair root, one or
+        two capacitors and sources, not force_generic, tensors in, zero initial state -- and 0 <= skip < T.  Two capacitors
+        WITH two sources keep the composed path: the MSE + ESR kernels are not built for that tree (WDF_EUNSUPPORTED; both
+        families of accumulators do not fit a wave's registers there)."""
+        tree = getattr(self, "_tree", None)
+        if tree is None or self.root_kind != "DiodePair" or not (1 <= self.ns <= 2 and 1 <= self.ni <= 2) or self.force_generic:
+            return None
+        if self.ns * self.ni == 4:
+            return None
+        if not (isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)) or z0 is not None or carry_state:
+            return None
+        if x.dim() < 2 or not 0 <= int(skip) < int(x.shape[1]):
+            return None
+        return tree
 
     # -- topology tests
     def mse(self, x, target, z0=None, carry_state=False):

@@ -354,6 +354,9 @@ int wdf_ss_lin_step_mse(const float* x, const float* coef, const double* jac, in
  *   wdf_ss_nl_step_read   the 32-word control block {call, parity, have_snap, w_cur, w_snap, w_min, w_max, cool, tol,
  *                         grow_at, shrink_at, cool_miss, n_bad, max_miss, gated_groups, total_gated, ..., w_used at [19]}
  *                         (synchronises).  wdf_ss_nl_step_set: field 2..11 of it (tests, tuning).                  */
+/* (the size is the MSE + ESR step's, the larger of the two, so that one planned workspace serves both entry points: an
+ *  MSE-only caller pays n_chunks x ns x B floats of records and a second set of per-chunk sums it does not use.  0 on bad
+ *  arguments, with wdf_last_error set.)                                                                                */
 size_t wdf_ss_nl_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
 int wdf_ss_nl_step_chunk_len(int64_t T, int n_chunks);
 int wdf_ss_nl_step_plan(void* ws, int ns, int ni, int64_t B, int64_t T, int n_chunks, int cold_warmup, int warm_warmup,
@@ -363,6 +366,19 @@ int wdf_ss_nl_step_read(const void* ws, int32_t* ctl_out, void* stream);
 int wdf_ss_nl_step_mse(const float* x, const float* coef, const float* params, const double* jac, int n_tree, int ns,
                        int ni, int n_up, int n_down, const float* target, float gscale, float* y, void* ws, float* out,
                        float* loss_out, int64_t B, int64_t T, int n_chunks, void* stream);
+/* The same pass with the scripts' training loss (clipper_pot.py:141-177) on the rows t >= skip:
+ *   mse + esr = S / n + sqrt(S / (E + eps) / n),  S = sum (y - target)^2,  E = sum y^2,  n = B (T - skip).
+ * dLoss/dy = ga (y - target) + gb y with ga, gb functions of the GLOBAL S and E: the pass carries the sums of both weights
+ * and the launch's last wave combines them.  Arguments as wdf_ss_nl_step_mse with skip (0 <= skip < T), eps and loss3_out
+ * in place of gscale / loss_out.  out: float [1 + n_tree + 2] = {S, d(mse + esr)/d{component values, Is, nVt}};
+ * loss3_out: float [3] = {mse, esr, mse + esr}.  Plan, set, read and chunk_len are the MSE step's, and so is the
+ * workspace layout (wdf_ss_nl_step_esr_ws_bytes == wdf_ss_nl_step_ws_bytes: a planned workspace serves either entry
+ * point; the snapshots in it belong to the calls made on it, so give each training loop its own).  Built for
+ * ns * ni <= 2: two states WITH two sources answer WDF_EUNSUPPORTED (and a size of 0).                                  */
+size_t wdf_ss_nl_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+int wdf_ss_nl_step_esr(const float* x, const float* coef, const float* params, const double* jac, int n_tree, int ns,
+                       int ni, int n_up, int n_down, const float* target, int64_t skip, double eps, float* y, void* ws,
+                       float* out, float* loss3_out, int64_t B, int64_t T, int n_chunks, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The RESIDENT training step of the MLP-root pot clipper (csrc/wdf_mlp_step.h): what one epoch of
