@@ -206,7 +206,9 @@ void launch_fused(const float* x, const float* r, const float* theta, float fs, 
     // WDF_FUSED_FINISH=inkernel restores the round-5 form (the tile's last chunk wave does the tail, an idle repair launch follows).
     static const bool finish_inkernel = []() { const char* e = getenv("WDF_FUSED_FINISH"); return e && strcmp(e, "inkernel") == 0; }();
     const int later = (g.K > 1 && !finish_inkernel) ? 1 : 0;
-    const int fin_waves = (int)std::min<int64_t>(wdf::kFinMaxWaves, (g.K + wdf::kFinSeg - 1) / wdf::kFinSeg);
+    // waves per tile of the finish launch: the chunks spread over as many of the kFinMaxWaves as leaves each at least kFinMinSeg
+    // records (32 chunks: 8 waves of 4; 128: 8 waves of 16 in two register batches)
+    const int fin_waves = (int)std::min<int64_t>(wdf::kFinMaxWaves, (g.K + wdf::kFinMinSeg - 1) / wdf::kFinMinSeg);
     dispatch([&](auto PAIRS, auto LOSS) {                      // LOSS 1: MSE, 2: MSE + ESR
         using V = std::conditional_t<PAIRS(), wdf::v2f, float>;
         constexpr int N = PAIRS() ? 2 : 1;                     // sequences per lane

@@ -1267,14 +1267,15 @@ __device__ __forceinline__ void tp_finish_deferred(const TpFinishCtx& fc, const 
 
 // A tile's partial sums {S_L, S_V, S_P, SSE} (per lane, dead lanes zero) -> the tile's slot of ws; the LAST tile
 // to arrive (tickets[0], left clean) does the fixed-order reduction over the tiles, the chain rule to
-// {Is, nVt, R, C} and, if asked, the Adam update of the four components.
+// {Is, nVt, R, C} and, if asked, the Adam update of the four components.  REDUCED: the sums are the tile's totals already.
+template <bool REDUCED = false>
 __device__ __forceinline__ void tile_partial_and_finish(double dL, double dV, double dP, double dS, double* ws, unsigned* tickets,
                                                         const float* theta, float fs, int dyn_r, float* gtheta, int accumulate,
                                                         float* __restrict__ sse_out, const AdamTail& adam, double (*sh)[4],
                                                         const TpFinishCtx& fc = TpFinishCtx{nullptr, nullptr, 0, nullptr, 0.0f, 0, 0, 0, false})
 {
     const unsigned ntiles = gridDim.x;
-    dL = wave_sum_dpp(dL); dV = wave_sum_dpp(dV); dP = wave_sum_dpp(dP); dS = wave_sum_dpp(dS);
+    if constexpr (!REDUCED) { dL = wave_sum_dpp(dL); dV = wave_sum_dpp(dV); dP = wave_sum_dpp(dP); dS = wave_sum_dpp(dS); }
     unsigned done = 0;
     if (threadIdx.x == 0) {
         double* o = ws + (int64_t)blockIdx.x * 4;      // slot 3: sum of squared errors (MSE mode)

@@ -174,6 +174,21 @@ __device__ __forceinline__ v4u load_published_quad(__amdgpu_buffer_rsrc_t rs, ui
 {
     return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 16);
 }
+// N adjacent published floats of a [B] row (load_published_n's loads through the row's descriptor: `row` wave-uniform, boff the
+// lane's byte offset, 8-byte aligned for N = 2)
+template <int N>
+__device__ __forceinline__ void load_published_row(const float* row, uint32_t boff, float (&v)[N])
+{
+    const __amdgpu_buffer_rsrc_t rs = row_rsrc(row);
+    if constexpr (N == 2) {
+        const v2u u = __builtin_amdgcn_raw_buffer_load_b64(rs, boff, 0, 16);
+        v[0] = __uint_as_float(u[0]);
+        v[1] = __uint_as_float(u[1]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, boff + 4u * i, 0, 16));
+    }
+}
 
 template <typename V, int NR>
 __device__ __forceinline__ void load_rows(const float* row0, uint32_t boff, uint32_t rowb, V (&v)[NR])
@@ -811,13 +826,15 @@ struct FusedOut {
 
 // MSE + ESR: the tile's eight sums -> its slot of ws (8 doubles per tile); the LAST tile reduces over the tiles in a fixed
 // order (lane i takes tiles i, i + 64, ...; then the wave's shuffle tree), applies the chain rule to P and Q and finishes.
+// REDUCED: v already holds the tile's totals (the finish launch: summed over its waves through LDS).
+template <bool REDUCED = false>
 __device__ __forceinline__ void esr_tile_partial_and_finish(const double (&v)[8], double* ws, unsigned* gticket, const float* theta,
                                                             float fs, int dyn_r, const FusedOut& out)
 {
     const unsigned ntiles = gridDim.x;
     double w[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = wave_sum_dpp(v[i]);
+    for (int i = 0; i < 8; ++i) w[i] = REDUCED ? v[i] : wave_sum_dpp(v[i]);
     unsigned done = 0;
     if (threadIdx.x == 0) {
         double* o = ws + (int64_t)blockIdx.x * 8;
@@ -1186,7 +1203,8 @@ __global__ __launch_bounds__(64) void clipper_fused_repair_kernel(
 // ticket, and as the last tile reduce, apply the chain rule, steer the warm start and run Adam: ~12 us of dependent device-scope
 // round trips at 32 chunks, 30+ at 128 -- and what the idle repair launch behind every step cost on top (4.7 us), as ONE launch
 // of 64 NW-thread workgroups, one per tile, behind the kernel boundary:
-//   * wave w of a tile owns the chunks [k0, k1) (at most kFinSeg = 8 at a time in registers): their records, their boundaries
+//   * wave w of a tile owns the chunks [k0, k1) (the host starts a wave for every kFinMinSeg = 4 chunks, up to 8 waves; at most
+//     kFinSeg = 8 records at a time in registers): their records, their boundaries
 //     and the chunk waves' own sums are requested TOGETHER -- one round trip;
 //   * every wave verifies its own boundaries; the tile's verdict goes through LDS.  A tile with a missed boundary is re-run by
 //     its wave 0 exactly as clipper_fused_repair_kernel does it (sequentially, from the exact state: outputs, snapshots,
@@ -1205,7 +1223,8 @@ __global__ __launch_bounds__(64) void clipper_fused_repair_kernel(
 #else
 #define WDF_FIN_STAMP(i) do {} while (0)
 #endif
-constexpr int kFinSeg = 8;          // chunk records a finishing wave holds in registers at a time
+constexpr int kFinSeg = 8;          // chunk records a finishing wave holds in registers at a time (loaded in halves of 4)
+constexpr int kFinMinSeg = 4;       // the host starts another wave per tile for every 4 chunks, up to kFinMaxWaves
 constexpr int kFinMaxWaves = 8;     // waves per tile (512 threads: the repair path needs up to 161 VGPRs)
 
 template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS>
@@ -1223,7 +1242,9 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     __shared__ double s_sum[kFinMaxWaves][8];
     __shared__ float s_miss[kFinMaxWaves];
     __shared__ int s_bad[kFinMaxWaves];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, NW = blockDim.x >> 6;
+    // (w through v_readfirstlane: the chunk range below is then the wave's, in SGPRs, and the row descriptors built from it need no
+    //  waterfall loop -- left in a VGPR every descriptor load of this kernel was wrapped in one: 109 loops in the headline instantiation)
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63, NW = blockDim.x >> 6;
     const int64_t seg = (K + NW - 1) / NW;
     const int64_t k0 = (int64_t)w * seg < K ? (int64_t)w * seg : K, k1 = k0 + seg < K ? k0 + seg : K;
     const int64_t raw = ((int64_t)blockIdx.x * 64 + lane) * NSEQ;
@@ -1234,14 +1255,18 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     WDF_FIN_STAMP(0);
 
     v4u g[kFinSeg][NQ];
-    auto load_batch = [&](int64_t kb) {                     // records of chunks kb .. kb + 7 (clamped to the wave's last)
+    auto load_half = [&](int64_t kb, auto J0) {             // records of chunks kb + J0 .. kb + J0 + 3 (clamped to the wave's last)
 #pragma unroll
-        for (int j = 0; j < kFinSeg; ++j) {
+        for (int j = decltype(J0)::value; j < decltype(J0)::value + kFinSeg / 2; ++j) {
             const int64_t k = (kb + j < k1) ? kb + j : (k1 > k0 ? k1 - 1 : 0);
             const __amdgpu_buffer_rsrc_t rs = row_rsrc(rec_chunk(rec, k));
 #pragma unroll
             for (int q = 0; q < NQ; ++q) g[j][q] = load_published_quad(rs, rl * 16u, (uint32_t)q * lanes * 16u);
         }
+    };
+    auto load_batch = [&](int64_t kb) {                     // a batch of up to 8 records; the second half only where the wave has chunks there
+        load_half(kb, std::integral_constant<int, 0>{});
+        if (kb + kFinSeg / 2 < k1) load_half(kb, std::integral_constant<int, kFinSeg / 2>{});
     };
     const __amdgpu_buffer_rsrc_t rw = row_rsrc(reinterpret_cast<float*>(wpart + (int64_t)blockIdx.x * K * NSEQ * NP));
     v4u wq[NWQ];
@@ -1255,32 +1280,71 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     load_part(k0 + lane);
     float miss = 0.0f;
     int nbad = 0;
-    for (int64_t kb = k0; kb < k1; kb += kFinSeg) {
-        float zw[kFinSeg][NSEQ], ze[kFinSeg][NSEQ];
+    // (the boundary rows as the records: one descriptor per chunk row from the wave's SGPRs, the lane's 32-bit byte offset -- B < 2^24)
+    auto check_half = [&](int64_t kb, auto J0) {
+        constexpr int H = kFinSeg / 2;
+        float zw[H][NSEQ], ze[H][NSEQ];
 #pragma unroll
-        for (int j = 0; j < kFinSeg; ++j) {
-            int64_t k = (kb + j < k1) ? kb + j : k1 - 1;
+        for (int j = 0; j < H; ++j) {
+            int64_t k = (kb + decltype(J0)::value + j < k1) ? kb + decltype(J0)::value + j : k1 - 1;
             k = k < 1 ? 1 : k;                                  // (chunk 0 has no boundary before it; K >= 2 here)
-            load_published_n<NSEQ>(zwarm + k * B + b_first, zw[j]);
-            load_published_n<NSEQ>(zend + (k - 1) * B + b_first, ze[j]);
+            load_published_row<NSEQ>(zwarm + k * B, (uint32_t)b_first * 4u, zw[j]);
+            load_published_row<NSEQ>(zend + (k - 1) * B, (uint32_t)b_first * 4u, ze[j]);
         }
 #pragma unroll
-        for (int j = 0; j < kFinSeg; ++j)
+        for (int j = 0; j < H; ++j)
 #pragma unroll
             for (int h = 0; h < NSEQ; ++h) {
                 const float m = fabsf(zw[j][h] - ze[j][h]);
-                if (kb + j < k1 && kb + j >= 1) {
+                if (kb + decltype(J0)::value + j < k1 && kb + decltype(J0)::value + j >= 1) {
                     miss = fmaxf(miss, m);
                     nbad += !(m <= tol) ? 1 : 0;                // NaN counts as bad
                 }
             }
+    };
+    for (int64_t kb = k0; kb < k1; kb += kFinSeg) {
+        check_half(kb, std::integral_constant<int, 0>{});
+        if (kb + kFinSeg / 2 < k1) check_half(kb, std::integral_constant<int, kFinSeg / 2>{});
     }
     {
         const float wmax = wave_max_dpp(miss);
         const int wbad = wave_sum_dpp(nbad);
         if (lane == 0) { s_miss[w] = wmax; s_bad[w] = wbad; }
     }
+    // ---- phase A: this wave's chunks as one affine map of the tangent, per sequence.  It does not wait for the tile's verdict:
+    // the maps and the verdict cross the waves behind ONE barrier, and a tile with a missed boundary composes again after the repair
+    auto compose = [&]() {
+        double P[NSEQ], qL[NSEQ], qV[NSEQ], qP[NSEQ];
+#pragma unroll
+        for (int h = 0; h < NSEQ; ++h) { P[h] = 1.0; qL[h] = qV[h] = qP[h] = 0.0; }
+        for (int64_t kb = k0; kb < k1; kb += kFinSeg) {
+            if (kb > k0) load_batch(kb);
+#pragma unroll
+            for (int j = 0; j < kFinSeg; ++j) {
+                if (kb + j >= k1) break;                        // wave-uniform
+                float v[NQ * 4];
+#pragma unroll
+                for (int i = 0; i < NQ * 4; ++i) v[i] = __uint_as_float(g[j][i / 4][i % 4]);
+#pragma unroll
+                for (int h = 0; h < NSEQ; ++h) {
+                    const float* rr = v + h * NREC;
+                    const double A = rr[0];
+                    P[h] *= A;
+                    qL[h] = A * qL[h] + (double)rr[1];
+                    qV[h] = A * qV[h] + (double)rr[2];
+                    qP[h] = A * qP[h] + (double)rr[3];
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < NSEQ; ++h) {
+            s_pq[w][h][lane][0] = (float)P[h]; s_pq[w][h][lane][1] = (float)qL[h];
+            s_pq[w][h][lane][2] = (float)qV[h]; s_pq[w][h][lane][3] = (float)qP[h];
+        }
+    };
     WDF_FIN_STAMP(1);
+    compose();
+    WDF_FIN_STAMP(2);
     __syncthreads();
     int tile_bad_pairs = 0;
     float tile_miss = 0.0f;
@@ -1338,39 +1402,9 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
         __syncthreads();
         load_batch(k0);                                        // (agent-scope loads: past this CU's L1)
         load_part(k0 + lane);
+        compose();
+        __syncthreads();
     }
-    // ---- phase A: this wave's chunks as one affine map of the tangent, per sequence
-    {
-        double P[NSEQ], qL[NSEQ], qV[NSEQ], qP[NSEQ];
-#pragma unroll
-        for (int h = 0; h < NSEQ; ++h) { P[h] = 1.0; qL[h] = qV[h] = qP[h] = 0.0; }
-        for (int64_t kb = k0; kb < k1; kb += kFinSeg) {
-            if (kb > k0) load_batch(kb);
-#pragma unroll
-            for (int j = 0; j < kFinSeg; ++j) {
-                if (kb + j >= k1) break;                        // wave-uniform
-                float v[NQ * 4];
-#pragma unroll
-                for (int i = 0; i < NQ * 4; ++i) v[i] = __uint_as_float(g[j][i / 4][i % 4]);
-#pragma unroll
-                for (int h = 0; h < NSEQ; ++h) {
-                    const float* rr = v + h * NREC;
-                    const double A = rr[0];
-                    P[h] *= A;
-                    qL[h] = A * qL[h] + (double)rr[1];
-                    qV[h] = A * qV[h] + (double)rr[2];
-                    qP[h] = A * qP[h] + (double)rr[3];
-                }
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < NSEQ; ++h) {
-            s_pq[w][h][lane][0] = (float)P[h]; s_pq[w][h][lane][1] = (float)qL[h];
-            s_pq[w][h][lane][2] = (float)qV[h]; s_pq[w][h][lane][3] = (float)qP[h];
-        }
-    }
-    WDF_FIN_STAMP(2);
-    __syncthreads();
     // ---- phase B: the tangent entering this wave's first chunk, then the walk with the sums
     double sL[NSEQ], sV[NSEQ], sP[NSEQ];                   // (the tangent entering the tile is 0: z0 does not depend on theta)
 #pragma unroll
@@ -1438,17 +1472,16 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     WDF_FIN_STAMP(3);
     __syncthreads();
     if (w != 0) return;
+    // the waves' sums in wave order, by every lane (LDS broadcast reads): the tile's totals, which cross the wave no second time
     double tot[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (lane == 0) {
-        for (int ww = 0; ww < NW; ++ww)
+    for (int ww = 0; ww < NW; ++ww)
 #pragma unroll
-            for (int i = 0; i < (LOSS == 2 ? 8 : 4); ++i) tot[i] += s_sum[ww][i];
-    }
+        for (int i = 0; i < (LOSS == 2 ? 8 : 4); ++i) tot[i] += s_sum[ww][i];
     out.fc = TpFinishCtx{status, ctl, J, tickets, tol, K, L, W, skew != 0};
     WDF_FIN_STAMP(4);
-    if constexpr (LOSS == 2) esr_tile_partial_and_finish(tot, ws, gticket, theta, fs, DYN_R ? 1 : 0, out);
-    else tile_partial_and_finish(tot[0], tot[1], tot[2], tot[3], ws, gticket, theta, fs, DYN_R ? 1 : 0, out.gtheta, out.accumulate, out.sse_out,
-                                 out.adam, sh, out.fc);
+    if constexpr (LOSS == 2) esr_tile_partial_and_finish<true>(tot, ws, gticket, theta, fs, DYN_R ? 1 : 0, out);
+    else tile_partial_and_finish<true>(tot[0], tot[1], tot[2], tot[3], ws, gticket, theta, fs, DYN_R ? 1 : 0, out.gtheta, out.accumulate,
+                                       out.sse_out, out.adam, sh, out.fc);
 }
 
 }  // namespace wdf
