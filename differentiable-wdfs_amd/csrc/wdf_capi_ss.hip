@@ -12,7 +12,13 @@ namespace {
 using SsStates = Values<int, 0, 1, 2, 3, 4>;
 using SsStates1 = Values<int, 1, 2, 3, 4>;        // the chunked kernels: at least one state to carry across a boundary
 using SsInputs = Values<int, 1, 2>;
-using SsRoots = Values<int, wdf::kRootNone, wdf::kRootDiode>;
+using SsRoots = Values<int, wdf::kRootNone, wdf::kRootDiode, wdf::kRootAsym>;
+using SsNlRoots = Values<int, wdf::kRootDiode, wdf::kRootAsym>;      // the speculating forward: roots that are not folded into the matrices
+// Two different diodes: up to three states.  The chunked reverse sweep's five root sums per run (1 + ns runs) do not fit a wave's
+// registers at ns = 4 (kernel-resource-usage: 49 VGPR spills at ni = 1, 280 bytes of scratch at ni = 2), so that size is not built
+// for this root in any of the four kernels: WDF_EUNSUPPORTED.
+constexpr int kAsymMaxStates = 3;
+template <class NS, class ROOT> constexpr bool ss_built(NS, ROOT) { return !(ROOT() == wdf::kRootAsym && NS() > kAsymMaxStates); }
 constexpr int kUnit = 8;                          // chunk lengths and warm-ups of the time-parallel kernels: multiples of 8 steps
 
 int ss_check(const float* x, const float* coef, const float* rootp, int ns, int ni, int root, int n_up, int n_down,
@@ -20,8 +26,12 @@ int ss_check(const float* x, const float* coef, const float* rootp, int ns, int 
 {
     if (!x || !coef) return fail(WDF_EINVAL, "null x/coef");
     if (ns < 0 || ns > 4 || ni < 1 || ni > 2) return fail(WDF_EUNSUPPORTED, "state-space kernels cover ns in [0,4], ni in [1,2] (got ns=%d ni=%d)", ns, ni);
-    if (root != wdf::kRootNone && root != wdf::kRootDiode) return fail(WDF_EINVAL, "unknown root kind %d", root);
+    if (root != wdf::kRootNone && root != wdf::kRootDiode && root != wdf::kRootAsym) return fail(WDF_EINVAL, "unknown root kind %d", root);
     if (root == wdf::kRootDiode && !rootp) return fail(WDF_EINVAL, "diode root needs rootp = {Is, nVt, R_port}");
+    if (root == wdf::kRootAsym && ns > kAsymMaxStates)
+        return fail(WDF_EUNSUPPORTED, "the two-different-diode root runs on trees of at most %d states (got ns=%d): its chunked reverse sweep "
+                    "does not fit a wave's registers beyond", kAsymMaxStates, ns);
+    if (root == wdf::kRootAsym && !rootp) return fail(WDF_EINVAL, "two-different-diode root needs rootp = {Is_up, nVt_up, Is_down, nVt_down, R_port}");
     if (root == wdf::kRootDiode && (n_up < 1 || n_down < 1 || n_up > 16 || n_down > 16)) return fail(WDF_EINVAL, "n_up/n_down must be in [1,16]");
     if (B <= 0 || T <= 0) return fail(WDF_EINVAL, "B and T must be positive");
     if (flags != 0) return fail(WDF_EINVAL, "state-space kernels take flags = 0");
@@ -35,15 +45,24 @@ bool launch_ss_fwd(int ns, int ni, int root, bool v4, const float* x, const floa
                    float* zstash, const float* z0, float* zT, int64_t B, int64_t T, const unsigned* gate, hipStream_t s)
 {
     return dispatch([&](auto NS, auto NI, auto ROOT, auto V4) {
-        hipLaunchKernelGGL((wdf::ss_fwd_kernel<NS(), NI(), ROOT(), false, V4()>), dim3(waves64(B)), dim3(64), 0, s, x, coef, rootp, n_up,
-                           n_down, y, zstash, z0, zT, B, T, gate);
+        if constexpr (!ss_built(NS, ROOT)) return false;
+        else {
+            hipLaunchKernelGGL((wdf::ss_fwd_kernel<NS(), NI(), ROOT(), false, V4()>), dim3(waves64(B)), dim3(64), 0, s, x, coef, rootp, n_up,
+                               n_down, y, zstash, z0, zT, B, T, gate);
+            return true;
+        }
     }, SsStates{ns}, SsInputs{ni}, SsRoots{root}, Bools{v4});
 }
 
 void launch_ss_grad_reduce(const double* part, int ns, int ni, int root, const float* rootp, float* gcoef, float* groot, int64_t B, hipStream_t s)
 {
     const int ncoef = wdf_ss_ncoef(ns, ni);
-    hipLaunchKernelGGL(wdf::ss_grad_reduce_kernel, dim3(1), dim3(64), 0, s, part, (int)waves64(B), ncoef + 2, ncoef,
+    if (root == wdf::kRootAsym) {
+        hipLaunchKernelGGL(wdf::ss_grad_reduce_kernel<true>, dim3(1), dim3(64), 0, s, part, (int)waves64(B),
+                           ncoef + wdf::kSsRootAcc<wdf::kRootAsym>, ncoef, rootp, gcoef, groot);
+        return;
+    }
+    hipLaunchKernelGGL(wdf::ss_grad_reduce_kernel<false>, dim3(1), dim3(64), 0, s, part, (int)waves64(B), ncoef + 2, ncoef,
                        root == wdf::kRootDiode ? rootp : nullptr, gcoef, root == wdf::kRootDiode ? groot : nullptr);
 }
 
@@ -68,7 +87,8 @@ int wdf_ss_ncoef(int ns, int ni) { return ns * ns + ns * ni + ns + ns + ni + ns 
 
 size_t wdf_ss_bwd_ws_bytes(int ns, int ni, int64_t B)
 {
-    return B > 0 ? waves64(B) * (size_t)(wdf_ss_ncoef(ns, ni) + 2) * sizeof(double) : 0;
+    // (no root argument: rows of kN + 5 doubles, the two-different-diode root's, hold every root's)
+    return B > 0 ? waves64(B) * (size_t)(wdf_ss_ncoef(ns, ni) + wdf::kSsRootAccMax) * sizeof(double) : 0;
 }
 
 int wdf_ss_fwd(const float* x, const float* coef, const float* rootp, int ns, int ni, int root, int n_up, int n_down,
@@ -122,11 +142,15 @@ int wdf_ss_bwd(const float* x, const float* coef, const float* rootp, int ns, in
     if (rc) return rc;
     if (!gy || !ws || !gcoef) return fail(WDF_EINVAL, "null gy/ws/gcoef");
     if (ns > 0 && !zstash) return fail(WDF_EINVAL, "null zstash");
-    if (root == wdf::kRootDiode && !groot) return fail(WDF_EINVAL, "null groot");
+    if (root != wdf::kRootNone && !groot) return fail(WDF_EINVAL, "null groot");
     hipStream_t s = (hipStream_t)stream;
     const bool ok = dispatch([&](auto NS, auto NI, auto ROOT, auto V4) {
-        hipLaunchKernelGGL((wdf::ss_bwd_kernel<NS(), NI(), ROOT(), false, V4()>), dim3(waves64(B)), dim3(64), 0, s, x, coef, rootp, n_up,
-                           n_down, zstash, gy, (double*)ws, gz0, B, T);
+        if constexpr (!ss_built(NS, ROOT)) return false;
+        else {
+            hipLaunchKernelGGL((wdf::ss_bwd_kernel<NS(), NI(), ROOT(), false, V4()>), dim3(waves64(B)), dim3(64), 0, s, x, coef, rootp, n_up,
+                               n_down, zstash, gy, (double*)ws, gz0, B, T);
+            return true;
+        }
     }, SsStates{ns}, SsInputs{ni}, SsRoots{root}, Bools{ss_v4(x, T, ni)});
     if (!ok) return no_kernel("wdf_ss_bwd");
     rc = check_launch("wdf_ss_bwd");
@@ -157,7 +181,17 @@ int wdf_ss_fwd_tp(const float* x, const float* coef, const float* rootp, int ns,
                   float* zstash, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol,
                   const float* zinit, void* ws, void* status, void* stream)
 {
-    int rc = ss_check(x, coef, rootp, ns, ni, wdf::kRootDiode, n_up, n_down, B, T, 0);
+    return wdf_ss_fwd_tp_root(x, coef, rootp, ns, ni, WDF_ROOT_DIODE_PAIR, n_up, n_down, y, zstash, z0, zT, B, T, n_chunks, warmup, tol,
+                              zinit, ws, status, stream);
+}
+
+int wdf_ss_fwd_tp_root(const float* x, const float* coef, const float* rootp, int ns, int ni, int root_kind, int n_up, int n_down,
+                       float* y, float* zstash, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol,
+                       const float* zinit, void* ws, void* status, void* stream)
+{
+    if (root_kind != wdf::kRootDiode && root_kind != wdf::kRootAsym)
+        return fail(WDF_EINVAL, "wdf_ss_fwd_tp_root: root kind %d has nothing to speculate about (a linear tree takes wdf_ss_fwd_lin_tp)", root_kind);
+    int rc = ss_check(x, coef, rootp, ns, ni, root_kind, n_up, n_down, B, T, 0);
     if (rc) return rc;
     if (!y || !ws || !status) return fail(WDF_EINVAL, "null y/ws/status");
     if (ns < 1) return fail(WDF_EINVAL, "a tree without states has nothing to speculate about: use wdf_ss_fwd");
@@ -174,20 +208,25 @@ int wdf_ss_fwd_tp(const float* x, const float* coef, const float* rootp, int ns,
     bool ok;
     {
         EventBracket bracket(s);
-        ok = dispatch([&](auto NS, auto NI, auto SYM, auto V4) {
-            hipLaunchKernelGGL((wdf::ss_fwd_tp_kernel<NS(), NI(), SYM(), V4()>), grid, dim3(64), 0, s, x, coef, rootp, n_up, n_down, y, zstash,
-                               z0, zT, zwarm, zend, (wdf::SsTpStatus*)status, B, T, g.L, W, zinit);
-        }, SsStates1{ns}, SsInputs{ni}, Bools{n_up == n_down}, Bools{v4});
+        // two different diodes have no symmetric case: they take the SYM = false instantiation
+        ok = dispatch([&](auto NS, auto NI, auto ROOT, auto SYM, auto V4) {
+            if constexpr ((ROOT() == wdf::kRootAsym && SYM()) || !ss_built(NS, ROOT)) return false;
+            else {
+                hipLaunchKernelGGL((wdf::ss_fwd_tp_kernel<NS(), NI(), ROOT(), SYM(), V4()>), grid, dim3(64), 0, s, x, coef, rootp, n_up,
+                                   n_down, y, zstash, z0, zT, zwarm, zend, (wdf::SsTpStatus*)status, B, T, g.L, W, zinit);
+                return true;
+            }
+        }, SsStates1{ns}, SsInputs{ni}, SsNlRoots{root_kind}, Bools{root_kind == wdf::kRootDiode && n_up == n_down}, Bools{v4});
     }
     if (ok && g.K > 1) {
         hipLaunchKernelGGL(wdf::ss_tp_verify_kernel, dim3(grid.x), dim3(64), 0, s, (const float*)zwarm, (const float*)zend, ns, B,
                            (int64_t)g.K, tol, w.gate, (wdf::SsTpStatus*)status);
-        ok = launch_ss_fwd(ns, ni, wdf::kRootDiode, v4, x, coef, rootp, n_up, n_down, y, zstash, z0, zT, B, T, w.gate, s);
+        ok = launch_ss_fwd(ns, ni, root_kind, v4, x, coef, rootp, n_up, n_down, y, zstash, z0, zT, B, T, w.gate, s);
     }
     return ok ? check_launch("wdf_ss_fwd_tp") : no_kernel("wdf_ss_fwd_tp");
 }
 
-static int ss_tp_rec(int ns, int ni) { const int nacc = wdf_ss_ncoef(ns, ni) + 2; return ns * ns + ns + nacc * (ns + 1); }
+static int ss_tp_rec(int ns, int ni) { const int nacc = wdf_ss_ncoef(ns, ni) + wdf::kSsRootAccMax; return ns * ns + ns + nacc * (ns + 1); }
 
 size_t wdf_ss_bwd_tp_ws_bytes(int ns, int ni, int64_t B, int n_chunks)
 {
@@ -203,7 +242,7 @@ int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns,
     if (rc) return rc;
     if (!gy || !ws || !gcoef || !zstash) return fail(WDF_EINVAL, "null gy/ws/gcoef/zstash");
     if (ns < 1) return fail(WDF_EINVAL, "a tree without states has no adjoint to scan: use wdf_ss_bwd");
-    if (root == wdf::kRootDiode && !groot) return fail(WDF_EINVAL, "null groot");
+    if (root != wdf::kRootNone && !groot) return fail(WDF_EINVAL, "null groot");
     const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
     if ((rc = check_tiles(g, n_chunks, T, kUnit, "wdf_ss_tp_chunks"))) return rc;
     double* part = (double*)ws;
@@ -211,16 +250,17 @@ int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns,
     const dim3 grid(waves64(B), (unsigned)g.K);
     hipStream_t s = (hipStream_t)stream;
     // a linear tree has no diode pair to be symmetric: it takes the SYM = true instantiation
-    const bool sym = root == wdf::kRootNone || n_up == n_down;
+    // (two different diodes have no symmetric case: SYM = false)
+    const bool sym = root == wdf::kRootNone || (root == wdf::kRootDiode && n_up == n_down);
     const bool ok = dispatch([&](auto NS, auto NI, auto ROOT, auto SYM, auto V4) {
-        if constexpr (ROOT() == wdf::kRootNone && !SYM()) return false;
+        if constexpr ((ROOT() == wdf::kRootNone && !SYM()) || (ROOT() == wdf::kRootAsym && SYM()) || !ss_built(NS, ROOT)) return false;
         else {
             {
                 EventBracket bracket(s);
                 hipLaunchKernelGGL((wdf::ss_bwd_tp_kernel<NS(), NI(), ROOT(), SYM(), V4()>), grid, dim3(64), 0, s, x, coef, rootp, n_up, n_down,
                                    zstash, gy, rec, B, T, g.L);
             }
-            hipLaunchKernelGGL((wdf::ss_bwd_tp_combine_kernel<NS(), NI()>), dim3(grid.x), dim3(64), 0, s, (const float*)rec, part, gz0, B,
+            hipLaunchKernelGGL((wdf::ss_bwd_tp_combine_kernel<NS(), NI(), wdf::kSsRootAcc<ROOT()>>), dim3(grid.x), dim3(64), 0, s, (const float*)rec, part, gz0, B,
                                (int64_t)g.K);
             return true;
         }

@@ -20,17 +20,26 @@
 // Layouts: x [B][T][NI] (the reference's input[:, i, c]), y [T][B], state stash [T][NS][B],
 // z0 / zT [NS][B].  coef (device, fp32):
 //     A[NS][NS] | Bx[NS][NI] | E[NS] | ca[NS] | da[NI] | cy[NS] | dy[NI] | fy
-// rootp (device, fp32) for the diode pair: {Is, nVt, R_port}.
+// rootp (device, fp32) for the diode pair: {Is, nVt, R_port}; for the pair of two DIFFERENT diodes (root kind ASYM: the exact
+// Shockley pair of wdf_asym.h, solved by Newton in fp32 at every step): {Is_up, nVt_up, Is_down, nVt_down, R_port}.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "wdf_asym.h"
 #include "wdf_omega.h"
 
 namespace wdf {
 
-enum { kRootNone = 0, kRootDiode = 2 };
+enum { kRootNone = 0, kRootDiode = 2, kRootAsym = 4 };
+
+// sums a reverse sweep keeps for the root's own parameters: {D_L, D_V} for the symmetric pair (and, unused, for a linear tree),
+// dL/d{Is_up, nVt_up, Is_down, nVt_down, R_port} for two different diodes
+template <int ROOT> constexpr int kSsRootAcc = (ROOT == kRootAsym) ? 5 : 2;
+constexpr int kSsRootAccMax = 5;                       // what the hosts' workspaces are sized for, whatever the root
 
 template <int NS, int NI>
 struct SSCoef {
@@ -55,6 +64,25 @@ struct SSDiode {
         d = make_diode_static(V, n_up, n_down);
     }
 };
+
+// Two different diodes: wdf_asym.h's constants with Rp = the port resistance the tree shows the root (p belongs to the clipper
+// tree and is not used).  The solve is asym_newton32_solve with engine.clipper_asym's defaults as compile-time constants: the
+// tolerance at its fp32 floor (tol = 0 -> 4 FLT_EPSILON) and at most 50 iterations.  Its stop rule is a wavefront ballot, so
+// every lane of a wave has to reach it together: the ss_* kernels clamp dead lanes to B - 1 and return per WAVE only.
+struct SSAsym {
+    AsymConsts c;
+    __device__ __forceinline__ void load(const float* __restrict__ rp, int, int)
+    {
+        c.Is1 = rp[0]; c.V1 = rp[1]; c.Is2 = rp[2]; c.V2 = rp[3]; c.Rp = rp[4];
+        c.p = 0.0f;
+        c.l1 = logf(c.Rp * c.Is1 / c.V1);
+        c.l2 = logf(c.Rp * c.Is2 / c.V2);
+    }
+};
+constexpr double kSsAsymTol = 0.0;
+constexpr int kSsAsymMaxIter = 50;
+
+template <int ROOT> using SSRoot = std::conditional_t<ROOT == kRootAsym, SSAsym, SSDiode>;
 
 // loads kBlkSS steps x NI channels of lane b's row into v[step][chan]
 constexpr int kBlkSS = 8;
@@ -85,7 +113,7 @@ __device__ __forceinline__ void ss_load_block(const float* __restrict__ x, int64
 }
 
 template <int NS, int NI, int ROOT, bool SYM>
-__device__ __forceinline__ float ss_fwd_step(const SSCoef<NS, NI>& c, const SSDiode& dp, const float (&x)[NI],
+__device__ __forceinline__ float ss_fwd_step(const SSCoef<NS, NI>& c, const SSRoot<ROOT>& dp, const float (&x)[NI],
                                              float (&z)[NS > 0 ? NS : 1])
 {
     using C = SSCoef<NS, NI>;
@@ -97,6 +125,15 @@ __device__ __forceinline__ float ss_fwd_step(const SSCoef<NS, NI>& c, const SSDi
 #pragma unroll
         for (int i = 0; i < NI; ++i) a = fmaf(c.v[C::oDa + i], x[i], a);
         b = diode_pair<SYM>(a, dp.L, dp.d).b;
+    }
+    if constexpr (ROOT == kRootAsym) {
+        float a = 0.0f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) a = fmaf(c.v[C::oCa + s], z[s], a);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) a = fmaf(c.v[C::oDa + i], x[i], a);
+        int iters = 0;
+        b = asym_newton32_root(dp.c, a, kSsAsymTol, kSsAsymMaxIter, iters);
     }
     float y = c.v[C::oFy] * b;
 #pragma unroll
@@ -131,8 +168,8 @@ __global__ __launch_bounds__(64) void ss_fwd_kernel(const float* __restrict__ x,
     const int64_t b = b_raw < B ? b_raw : B - 1;     // dead lanes shadow the last sequence
     SSCoef<NS, NI> c;
     c.load(coef);
-    SSDiode dp = {};
-    if constexpr (ROOT == kRootDiode) dp.load(rootp, n_up, n_down);
+    SSRoot<ROOT> dp = {};
+    if constexpr (ROOT != kRootNone) dp.load(rootp, n_up, n_down);
     float z[NSa];
 #pragma unroll
     for (int s = 0; s < NS; ++s) z[s] = z0 ? z0[s * B + b] : 0.0f;
@@ -359,15 +396,29 @@ __global__ __launch_bounds__(64) void ss_lin_chunk_kernel(const float* __restric
 //   dA[s][s'] += lam[s] z[s'] ; dBx[s][i] += lam[s] x[i] ; dE[s] += lam[s] b
 //   dca[s] += ga z[s] ; dda[i] += ga x[i] ; dcy[s] += g z[s] ; ddy[i] += g x[i] ; dfy += g b
 //   diode: dL += gb D_L ; dV += gb D_V   (D's partials as in wdf_clipper.h)
-// Accumulators per lane: SSCoef::kN coefficient gradients + 2 root sums, fp32 inside a
-// block of 8 steps, fp64 across blocks.
+//   two different diodes: a is formed from the stash and the root solved again by the forward's own function (the same b, bit
+//   for bit); asym_newton_partials gives Da and cf = db/d{Is_up, nVt_up, Is_down, nVt_down, R_port} there: droot[i] += gb cf[i]
+// Accumulators per lane: SSCoef::kN coefficient gradients + kSsRootAcc root sums (2, or 5 for two different diodes), fp32
+// inside a block of 8 steps, fp64 across blocks.
 template <int NS, int NI, int ROOT, bool SYM>
-__device__ __forceinline__ void ss_bwd_step(const SSCoef<NS, NI>& c, const SSDiode& dp, const float (&x)[NI],
+__device__ __forceinline__ void ss_bwd_step(const SSCoef<NS, NI>& c, const SSRoot<ROOT>& dp, const float (&x)[NI],
                                             const float (&z)[NS > 0 ? NS : 1], float g,
-                                            float (&lam)[NS > 0 ? NS : 1], float (&acc)[SSCoef<NS, NI>::kN + 2])
+                                            float (&lam)[NS > 0 ? NS : 1], float (&acc)[SSCoef<NS, NI>::kN + kSsRootAcc<ROOT>])
 {
     using C = SSCoef<NS, NI>;
     float b = 0.0f, Da = 0.0f, DL = 0.0f, DV = 0.0f;
+    [[maybe_unused]] float cf[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (ROOT == kRootAsym) {
+        float a = 0.0f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) a = fmaf(c.v[C::oCa + s], z[s], a);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) a = fmaf(c.v[C::oDa + i], x[i], a);
+        int iters = 0;
+        float v, e1, e2;
+        b = asym_newton32_solve(dp.c, a, kSsAsymTol, kSsAsymMaxIter, iters, v, e1, e2);
+        asym_newton_partials(dp.c, v, e1, e2, Da, cf);
+    }
     if constexpr (ROOT == kRootDiode) {
         float a = 0.0f;
 #pragma unroll
@@ -405,8 +456,13 @@ __device__ __forceinline__ void ss_bwd_step(const SSCoef<NS, NI>& c, const SSDio
         acc[C::oDy + i] = fmaf(g, x[i], acc[C::oDy + i]);
     }
     acc[C::oFy] = fmaf(g, b, acc[C::oFy]);
-    acc[C::kN + 0] = fmaf(gb, DL, acc[C::kN + 0]);
-    acc[C::kN + 1] = fmaf(gb, DV, acc[C::kN + 1]);
+    if constexpr (ROOT == kRootAsym) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) acc[C::kN + i] = fmaf(gb, cf[i], acc[C::kN + i]);
+    } else {
+        acc[C::kN + 0] = fmaf(gb, DL, acc[C::kN + 0]);
+        acc[C::kN + 1] = fmaf(gb, DV, acc[C::kN + 1]);
+    }
     // adjoint of the state
     float ln[NS > 0 ? NS : 1];
 #pragma unroll
@@ -420,7 +476,7 @@ __device__ __forceinline__ void ss_bwd_step(const SSCoef<NS, NI>& c, const SSDio
     for (int s = 0; s < NS; ++s) lam[s] = ln[s];
 }
 
-// ws: double[gridDim.x][kN + 2] per-wave partial sums
+// ws: double[gridDim.x][kN + kSsRootAcc<ROOT>] per-wave partial sums
 template <int NS, int NI, int ROOT, bool SYM, bool VEC4>
 __global__ __launch_bounds__(64) void ss_bwd_kernel(const float* __restrict__ x, const float* __restrict__ coef,
                                                     const float* __restrict__ rootp, int n_up, int n_down,
@@ -430,14 +486,14 @@ __global__ __launch_bounds__(64) void ss_bwd_kernel(const float* __restrict__ x,
 {
     using C = SSCoef<NS, NI>;
     constexpr int NSa = NS > 0 ? NS : 1;
-    constexpr int NACC = C::kN + 2;
+    constexpr int NACC = C::kN + kSsRootAcc<ROOT>;
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool live = b_raw < B;
     const int64_t b = live ? b_raw : B - 1;
     C c;
     c.load(coef);
-    SSDiode dp = {};
-    if constexpr (ROOT == kRootDiode) dp.load(rootp, n_up, n_down);
+    SSRoot<ROOT> dp = {};
+    if constexpr (ROOT != kRootNone) dp.load(rootp, n_up, n_down);
 
     double tot[NACC];
 #pragma unroll
@@ -493,7 +549,9 @@ __global__ __launch_bounds__(64) void ss_bwd_kernel(const float* __restrict__ x,
 }
 
 // Fixed-order sum of the per-wave partials; writes gcoef[kN] and, for the diode root,
-// groot[3] = dL/d{Is, nVt, R_port}  (L = log(R_port Is / nVt)).
+// groot[3] = dL/d{Is, nVt, R_port}  (L = log(R_port Is / nVt)).  ASYM: the five root sums ARE dL/d{Is_up, nVt_up, Is_down,
+// nVt_down, R_port} (asym_newton_partials differentiates with respect to the values themselves): groot[5] <- the sums.
+template <bool ASYM>
 static __global__ __launch_bounds__(64) void ss_grad_reduce_kernel(const double* __restrict__ ws, int nparts, int nacc,
                                                             int ncoef, const float* __restrict__ rootp,
                                                             float* __restrict__ gcoef, float* __restrict__ groot)
@@ -513,12 +571,16 @@ static __global__ __launch_bounds__(64) void ss_grad_reduce_kernel(const double*
         for (; p < nparts; ++p) s += ws[(int64_t)p * nacc + i];
     }
     if (i < ncoef) gcoef[i] = (float)s;
-    const double sL = __shfl(s, ncoef, 64), sV = __shfl(s, ncoef + 1, 64);
-    if (i == 0 && groot && rootp) {
-        const double Is = rootp[0], V = rootp[1], Rp = rootp[2];
-        groot[0] = (float)(sL / Is);
-        groot[1] = (float)(sV - sL / V);
-        groot[2] = (float)(sL / Rp);
+    if constexpr (ASYM) {
+        if (i >= ncoef && i < nacc && groot) groot[i - ncoef] = (float)s;
+    } else {
+        const double sL = __shfl(s, ncoef, 64), sV = __shfl(s, ncoef + 1, 64);
+        if (i == 0 && groot && rootp) {
+            const double Is = rootp[0], V = rootp[1], Rp = rootp[2];
+            groot[0] = (float)(sL / Is);
+            groot[1] = (float)(sV - sL / V);
+            groot[2] = (float)(sL / Rp);
+        }
     }
 }
 
@@ -535,7 +597,7 @@ static __global__ __launch_bounds__(64) void ss_grad_reduce_kernel(const double*
 // radius of the step's Jacobian at both ends of the diode's slope, lowering.plan_ss_time_parallel).
 struct SsTpStatus { int n_bad; float max_miss; int gated_waves; int pad; };
 
-template <int NS, int NI, bool SYM, bool VEC4>
+template <int NS, int NI, int ROOT, bool SYM, bool VEC4>
 __global__ __launch_bounds__(64) void ss_fwd_tp_kernel(const float* __restrict__ x, const float* __restrict__ coef,
                                                        const float* __restrict__ rootp, int n_up, int n_down,
                                                        float* __restrict__ y, float* __restrict__ zstash,
@@ -552,9 +614,10 @@ __global__ __launch_bounds__(64) void ss_fwd_tp_kernel(const float* __restrict__
     const int64_t b = b_raw < B ? b_raw : B - 1;
     const int64_t k = blockIdx.y, t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
     const int64_t tw = (t0 > W) ? t0 - W : 0;
+    static_assert(ROOT != kRootNone, "a linear tree takes the exact scan (ss_lin_*)");
     SSCoef<NS, NI> c;
     c.load(coef);
-    SSDiode dp = {};
+    SSRoot<ROOT> dp = {};
     dp.load(rootp, n_up, n_down);
     float z[NS];
 #pragma unroll
@@ -573,7 +636,7 @@ __global__ __launch_bounds__(64) void ss_fwd_tp_kernel(const float* __restrict__
         if (t + kBlkSS < tfull) ss_load_block<NI, VEC4>(x, b, T, t + kBlkSS, xn);
         if (t < t0) {                                           // warm-up block: nothing stored
 #pragma unroll
-            for (int q = 0; q < kBlkSS; ++q) (void)ss_fwd_step<NS, NI, kRootDiode, SYM>(c, dp, xc[q], z);
+            for (int q = 0; q < kBlkSS; ++q) (void)ss_fwd_step<NS, NI, ROOT, SYM>(c, dp, xc[q], z);
             continue;
         }
         if (t == t0) {
@@ -586,7 +649,7 @@ __global__ __launch_bounds__(64) void ss_fwd_tp_kernel(const float* __restrict__
 #pragma unroll
                 for (int s = 0; s < NS; ++s) zstash[((t + q) * NS + s) * B + b] = z[s];
             }
-            y[(t + q) * B + b] = ss_fwd_step<NS, NI, kRootDiode, SYM>(c, dp, xc[q], z);
+            y[(t + q) * B + b] = ss_fwd_step<NS, NI, ROOT, SYM>(c, dp, xc[q], z);
         }
     }
     if (tfull <= t0) {                                          // (a chunk shorter than a block: only the last one can be)
@@ -601,7 +664,7 @@ __global__ __launch_bounds__(64) void ss_fwd_tp_kernel(const float* __restrict__
 #pragma unroll
             for (int s = 0; s < NS; ++s) zstash[(t * NS + s) * B + b] = z[s];
         }
-        y[t * B + b] = ss_fwd_step<NS, NI, kRootDiode, SYM>(c, dp, xt, z);
+        y[t * B + b] = ss_fwd_step<NS, NI, ROOT, SYM>(c, dp, xt, z);
     }
 #pragma unroll
     for (int s = 0; s < NS; ++s) zend[(k * NS + s) * B + b] = z[s];
@@ -647,12 +710,13 @@ static __global__ __launch_bounds__(64) void ss_tp_verify_kernel(const float* __
 // omega, its partials -- is evaluated once per step) and leaves the record {Phi, beta, P, q}; ss_bwd_tp_combine_kernel walks
 // a sequence's chunks from the last to the first (LAM_{k-1} = Phi_k LAM_k + beta_k), adds up P LAM + q in double and leaves
 // the per-wave partial sums ss_grad_reduce_kernel expects.  Only the summation order differs from ss_bwd_kernel.
-template <int NS, int NI> struct SsTpRec { static constexpr int NACC = SSCoef<NS, NI>::kN + 2, N = NS * NS + NS + NACC * (NS + 1); };
+template <int NS, int NI, int NR = 2> struct SsTpRec { static constexpr int NACC = SSCoef<NS, NI>::kN + NR, N = NS * NS + NS + NACC * (NS + 1); };
 
-// the linear part of ss_bwd_step for one adjoint vector (g = 0 for the homogeneous runs)
-template <int NS, int NI>
+// the linear part of ss_bwd_step for one adjoint vector (g = 0 for the homogeneous runs); rd: the root's NR partials ({D_L, D_V}
+// or asym_newton_partials' five)
+template <int NS, int NI, int NR>
 __device__ __forceinline__ void ss_bwd_linear(const SSCoef<NS, NI>& c, const float (&x)[NI], const float (&z)[NS], float b, float Da,
-                                              float DL, float DV, float g, float (&lam)[NS], float (&acc)[SSCoef<NS, NI>::kN + 2])
+                                              const float (&rd)[NR], float g, float (&lam)[NS], float (&acc)[SSCoef<NS, NI>::kN + NR])
 {
     using C = SSCoef<NS, NI>;
     float gb = c.v[C::oFy] * g;
@@ -675,8 +739,8 @@ __device__ __forceinline__ void ss_bwd_linear(const SSCoef<NS, NI>& c, const flo
         acc[C::oDy + i] = fmaf(g, x[i], acc[C::oDy + i]);
     }
     acc[C::oFy] = fmaf(g, b, acc[C::oFy]);
-    acc[C::kN + 0] = fmaf(gb, DL, acc[C::kN + 0]);
-    acc[C::kN + 1] = fmaf(gb, DV, acc[C::kN + 1]);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) acc[C::kN + i] = fmaf(gb, rd[i], acc[C::kN + i]);
     float ln[NS];
 #pragma unroll
     for (int s2 = 0; s2 < NS; ++s2) {
@@ -697,14 +761,14 @@ __global__ __launch_bounds__(64) void ss_bwd_tp_kernel(const float* __restrict__
                                                        float* __restrict__ rec, int64_t B, int64_t T, int64_t L)
 {
     using C = SSCoef<NS, NI>;
-    constexpr int NACC = C::kN + 2;
+    constexpr int NR = kSsRootAcc<ROOT>, NACC = C::kN + NR;
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t b = b_raw < B ? b_raw : B - 1;
     const int64_t k = blockIdx.y, t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
     C c;
     c.load(coef);
-    SSDiode dp = {};
-    if constexpr (ROOT == kRootDiode) dp.load(rootp, n_up, n_down);
+    SSRoot<ROOT> dp = {};
+    if constexpr (ROOT != kRootNone) dp.load(rootp, n_up, n_down);
     // run 0: the actual adjoint (beta, q); runs 1..NS: homogeneous, LAM = e_{r-1} (Phi's column, P's row)
     float lam[NS + 1][NS], acc[NS + 1][NACC];
 #pragma unroll
@@ -716,7 +780,21 @@ __global__ __launch_bounds__(64) void ss_bwd_tp_kernel(const float* __restrict__
     }
     const float* __restrict__ xp = x + b * T * NI;
     auto one_step = [&](const float (&xt)[NI], const float (&zt)[NS], float g) {
-        float bb = 0.0f, Da = 0.0f, DL = 0.0f, DV = 0.0f;
+        float bb = 0.0f, Da = 0.0f;
+        float rd[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) rd[i] = 0.0f;
+        if constexpr (ROOT == kRootAsym) {
+            float a = 0.0f;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) a = fmaf(c.v[C::oCa + s], zt[s], a);
+#pragma unroll
+            for (int i = 0; i < NI; ++i) a = fmaf(c.v[C::oDa + i], xt[i], a);
+            int iters = 0;
+            float v, e1, e2;
+            bb = asym_newton32_solve(dp.c, a, kSsAsymTol, kSsAsymMaxIter, iters, v, e1, e2);
+            asym_newton_partials(dp.c, v, e1, e2, Da, rd);
+        }
         if constexpr (ROOT == kRootDiode) {
             float a = 0.0f;
 #pragma unroll
@@ -728,11 +806,11 @@ __global__ __launch_bounds__(64) void ss_bwd_tp_kernel(const float* __restrict__
             const float w0p = o.w0 * fast_rcp(1.0f + o.w0), w1p = o.w1 * fast_rcp(1.0f + o.w1);
             const float l2 = o.lam * o.lam, sp = w0p + w1p;
             Da = fmaf(-2.0f * l2, sp, 1.0f);
-            DL = -dp.d.two_v * o.lam * (o.m0 * w0p - o.m1 * w1p);
-            DV = fmaf(2.0f * l2 * a, sp * fast_rcp(dp.V), -2.0f * o.lam * (o.m0 * o.w0 - o.m1 * o.w1));
+            rd[0] = -dp.d.two_v * o.lam * (o.m0 * w0p - o.m1 * w1p);
+            rd[1] = fmaf(2.0f * l2 * a, sp * fast_rcp(dp.V), -2.0f * o.lam * (o.m0 * o.w0 - o.m1 * o.w1));
         }
 #pragma unroll
-        for (int r = 0; r <= NS; ++r) ss_bwd_linear<NS, NI>(c, xt, zt, bb, Da, DL, DV, r == 0 ? g : 0.0f, lam[r], acc[r]);
+        for (int r = 0; r <= NS; ++r) ss_bwd_linear<NS, NI, NR>(c, xt, zt, bb, Da, rd, r == 0 ? g : 0.0f, lam[r], acc[r]);
     };
     const int64_t tfull = t1 - (t1 - t0) % kBlkSS;              // t0 and L are multiples of 8: only the last chunk has a tail
     for (int64_t t = t1 - 1; t >= tfull; --t) {                 // tail first (highest t)
@@ -778,7 +856,7 @@ __global__ __launch_bounds__(64) void ss_bwd_tp_kernel(const float* __restrict__
 #pragma unroll
         for (int q = kBlkSS - 1; q >= 0; --q) one_step(xc[q], zc[q], gc[q]);
     }
-    float* __restrict__ o = rec + (size_t)k * SsTpRec<NS, NI>::N * B + b;
+    float* __restrict__ o = rec + (size_t)k * SsTpRec<NS, NI, NR>::N * B + b;
     int e = 0;
 #pragma unroll
     for (int s = 0; s < NS; ++s)
@@ -795,11 +873,11 @@ __global__ __launch_bounds__(64) void ss_bwd_tp_kernel(const float* __restrict__
 }
 
 // ws: double[gridDim.x][NACC] per-wave partial sums, as ss_bwd_kernel leaves them
-template <int NS, int NI>
+template <int NS, int NI, int NR>
 __global__ __launch_bounds__(64) void ss_bwd_tp_combine_kernel(const float* __restrict__ rec, double* __restrict__ ws,
                                                                float* __restrict__ gz0, int64_t B, int64_t K)
 {
-    constexpr int NACC = SSCoef<NS, NI>::kN + 2, NREC = SsTpRec<NS, NI>::N;
+    constexpr int NACC = SSCoef<NS, NI>::kN + NR, NREC = SsTpRec<NS, NI, NR>::N;
     const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool live = b_raw < B;
     const int64_t b = live ? b_raw : B - 1;

@@ -13,7 +13,8 @@ New surface (not in the reference):
       protocol Toms917DiodePair.h:21-59) with trainable Is and nVt;
   AsymDiodePair(next, Is_up, Is_down, Vt=25.85e-3, nDiodes_up=1, nDiodes_down=1, trainable=False, solver="newton_f32")
       two DIFFERENT antiparallel diodes, the exact Shockley pair solved by Newton (csrc/wdf_asym.h); a root for
-      Circuit on the diode-clipper tree, trainable Is and nVt per diode; with a Newton solver Circuit.mse and
+      Circuit on the diode-clipper tree -- with any_tree=True on any tree of at most three capacitors and two sources, through
+      the generic state-space kernels -- trainable Is and nVt per diode; on the clipper tree with a Newton solver Circuit.mse and
       Circuit.mse_esr are one-pass training steps (forward, loss and six gradients in one sweep: csrc/wdf_asym_step.h);
   Circuit(top, root, probe) / run(...) / Circuit.mse(x, target)
       the fast tier: lowers the WHOLE per-sample loop the scripts own (lpf.py:39-46,
@@ -275,13 +276,23 @@ class AsymDiodePair(_Element):
     as Circuit(..., per_sequence_R=vs) with vs the tree's ResistiveVoltageSource and a Newton solver: circ(x), mse and mse_esr
     then run the same kernels with one resistance per sequence (the wdf_clipper_asym_*_rseq entry points); the trainable values
     are Is_up, nVt_up, Is_down, nVt_down and C -- vs.R receives no gradient: the pot is data.  A channel that moves inside a
-    sequence raises; per_sample_R stays unsupported under this root.'''
+    sequence raises; per_sample_R stays unsupported under this root.
+
+    any_tree=True (default False: every refusal above stays) lets the root terminate ANY tree of at most three capacitors and
+    two sources, probed anywhere -- HPFDiodeClipper.h:28-32's Parallel(R, Series(Vs, C)) with a silicon diode against a
+    germanium one, say -- and the clipper tree under Circuit(..., force_generic=True): those run on the generic state-space
+    kernels (csrc/wdf_statespace.h, root kind WDF_ROOT_ASYM_PAIR: sequential and time-parallel forward, sequential and
+    chunked reverse sweep) with the pair solved by Newton in fp32 at every step; gradients reach the four diode Variables and,
+    through the port resistance and the step's matrices, every component; Circuit.mse / mse_esr compose the loss from the
+    forward.  The clipper tree probed at its capacitor keeps its own kernels and one-pass steps.  On the generic kernels the
+    root takes solver="newton_f32" only and no per_sample_R / per_sequence_R; to_device() stays unsupported.'''
 
     SOLVERS = {"omega_f32": 0, "newton_f64": 1, "newton_f32": 2}          # wdf_hip.binding.ASYM_*
 
     def __init__(self, next, Is_up, Is_down, Vt=25.85e-3, nDiodes_up=1.0, nDiodes_down=1.0, trainable=False,  # noqa: A002
-                 solver="newton_f32"):
+                 solver="newton_f32", any_tree=False):
         super().__init__()
+        self.any_tree = bool(any_tree)
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {sorted(self.SOLVERS)}, got {solver!r}")
         self.next = next
@@ -301,7 +312,7 @@ class AsymDiodePair(_Element):
     def reflected(self):
         raise _lowering.binding.WdfHipError(
             "AsymDiodePair has no element-wise reflected(): run it as the root of tf_wdf.Circuit on the diode-clipper tree "
-            "(Parallel(ResistiveVoltageSource, Capacitor), probe = the capacitor)")
+            "(Parallel(ResistiveVoltageSource, Capacitor), probe = the capacitor), or with any_tree=True on any small tree")
 
 
 # ---- fast tier ------------------------------------------------------------------------------

@@ -273,6 +273,8 @@ def lib():
     L.wdf_ss_fwd_tp_ws_bytes.argtypes = [ci, i64, ci]
     L.wdf_ss_fwd_tp.restype = ci
     L.wdf_ss_fwd_tp.argtypes = [fp, fp, fp, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, fp, vp, vp, vp]
+    L.wdf_ss_fwd_tp_root.restype = ci
+    L.wdf_ss_fwd_tp_root.argtypes = [fp, fp, fp, ci, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, fp, vp, vp, vp]
     L.wdf_ss_tp_starts.restype = ci
     L.wdf_ss_tp_starts.argtypes = [i64, ci, ci, C.POINTER(C.c_int64)]
     L.wdf_ss_bwd_tp_ws_bytes.restype = C.c_size_t
@@ -335,7 +337,7 @@ EXPORTED_SYMBOLS = (
     "wdf_ss_nl_step_ws_bytes", "wdf_ss_nl_step_chunk_len", "wdf_ss_nl_step_plan", "wdf_ss_nl_step_set", "wdf_ss_nl_step_read",
     "wdf_ss_nl_step_mse", "wdf_ss_nl_step_esr_ws_bytes", "wdf_ss_nl_step_esr",
     "wdf_ss_ncoef", "wdf_ss_fwd", "wdf_ss_bwd", "wdf_ss_bwd_ws_bytes", "wdf_ss_fwd_lin_tp_ws_bytes", "wdf_ss_fwd_lin_tp",
-    "wdf_ss_tp_chunks", "wdf_ss_tp_starts", "wdf_ss_fwd_tp_ws_bytes", "wdf_ss_fwd_tp", "wdf_ss_bwd_tp_ws_bytes", "wdf_ss_bwd_tp",
+    "wdf_ss_tp_chunks", "wdf_ss_tp_starts", "wdf_ss_fwd_tp_ws_bytes", "wdf_ss_fwd_tp", "wdf_ss_fwd_tp_root", "wdf_ss_bwd_tp_ws_bytes", "wdf_ss_bwd_tp",
     "wdf_omega_f32", "wdf_omega_f64", "wdf_diode_pair_f32", "wdf_adam_step", "wdf_adam_step_multi",
     "wdf_event_create", "wdf_event_record", "wdf_event_elapsed_ms", "wdf_event_destroy", "wdf_event_bracket_next",
     "wdf_clock_stamp",
@@ -1317,6 +1319,13 @@ def asym_root(a, theta6, fs, mode, tol=1e-12, max_iter=50):
 
 
 ROOT_NONE, ROOT_DIODE_PAIR, ROOT_MLP = 0, 2, 3
+ROOT_ASYM_PAIR = 4        # two different diodes, exact, fp32 Newton: ss_fwd / ss_bwd / ss_fwd_tp / ss_bwd_tp; rootp [5], groot [5]
+
+
+def _ss_groot(root_kind, device):
+    """The reverse sweeps' root-gradient buffer: [3] for the diode pair, [5] for two different diodes, None for a linear tree."""
+    n = {ROOT_DIODE_PAIR: 3, ROOT_ASYM_PAIR: 5}.get(root_kind)
+    return None if n is None else torch.empty((n,), dtype=torch.float32, device=device)
 
 
 def ss_fwd(x, coef, ns, ni, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, want_stash=True, z0=None,
@@ -1360,7 +1369,7 @@ def ss_fwd_lin_tp(x, coef, ns, ni, n_chunks, want_stash=True, z0=None, want_zT=F
 
 
 def ss_bwd(x, coef, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, want_gz0=False):
-    """Returns (gcoef [ncoef], groot [3] | None, gz0 [ns,B] | None)."""
+    """Returns (gcoef [ncoef], groot [3] ([5] under ROOT_ASYM_PAIR) | None, gz0 [ns,B] | None)."""
     require_gpu()
     x = _f32_dev(x, "x")
     coef = _f32_dev(coef, "coef")
@@ -1373,7 +1382,7 @@ def ss_bwd(x, coef, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, n_up=1,
     ncoef = lib().wdf_ss_ncoef(ns, ni)
     ws = torch.empty((lib().wdf_ss_bwd_ws_bytes(ns, ni, B),), dtype=torch.uint8, device=x.device)
     gcoef = torch.empty((ncoef,), dtype=torch.float32, device=x.device)
-    groot = torch.empty((3,), dtype=torch.float32, device=x.device) if root_kind == ROOT_DIODE_PAIR else None
+    groot = _ss_groot(root_kind, x.device)
     gz0 = torch.empty((ns, B), dtype=torch.float32, device=x.device) if (want_gz0 and ns > 0) else None
     rc = lib().wdf_ss_bwd(_ptr(x), _ptr(coef), _ptr(rootp), ns, ni, root_kind, int(n_up), int(n_down),
                           _ptr(zstash), _ptr(gy), _ptr(ws), _ptr(gcoef), _ptr(groot), _ptr(gz0), B, T, 0, _stream())
@@ -1390,8 +1399,9 @@ def ss_tp_starts(T, n_chunks, warmup):
 
 
 def ss_fwd_tp(x, coef, ns, ni, rootp, n_chunks, warmup, tol=1e-6, n_up=1, n_down=1, want_stash=True, z0=None, want_zT=False,
-              zinit=None):
-    """Time-parallel forward of a tree with a diode-pair root (include/wdf_hip.h, wdf_ss_fwd_tp): chunks warmed up from
+              zinit=None, root_kind=ROOT_DIODE_PAIR):
+    """Time-parallel forward of a tree with a diode-pair root, or with root_kind=ROOT_ASYM_PAIR (rootp [5]) a pair of two
+    different diodes (include/wdf_hip.h, wdf_ss_fwd_tp_root): chunks warmed up from
     z = 0 (or from zinit [chunks, ns, B]: states for the samples ss_tp_starts names), boundaries verified on the device,
     missed waves re-run sequentially behind a gate.
     -> y [T,B], zstash [T,ns,B] | None, zT [ns,B] | None, status (device int32[4]: read with ss_tp_status)."""
@@ -1409,9 +1419,10 @@ def ss_fwd_tp(x, coef, ns, ni, rootp, n_chunks, warmup, tol=1e-6, n_up=1, n_down
     status = torch.empty((4,), dtype=torch.int32, device=x.device)
     if zinit is not None and tuple(zinit.shape) != (K, ns, B):
         raise WdfHipError(f"zinit: expected [chunks, ns, B] = [{K},{ns},{B}]")
-    rc = lib().wdf_ss_fwd_tp(_ptr(x), _ptr(coef), _ptr(rootp), ns, ni, int(n_up), int(n_down), _ptr(y), _ptr(zs), _ptr(z0),
-                             _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(zinit), _ptr(ws), _ptr(status), _stream())
-    _check(rc, "wdf_ss_fwd_tp")
+    rc = lib().wdf_ss_fwd_tp_root(_ptr(x), _ptr(coef), _ptr(rootp), ns, ni, int(root_kind), int(n_up), int(n_down), _ptr(y),
+                                  _ptr(zs), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(zinit), _ptr(ws),
+                                  _ptr(status), _stream())
+    _check(rc, "wdf_ss_fwd_tp_root")
     return y, zs, zT, status
 
 
@@ -1625,7 +1636,7 @@ def ss_bwd_tp(x, coef, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, rootp=
     ncoef = lib().wdf_ss_ncoef(ns, ni)
     ws = torch.empty((lib().wdf_ss_bwd_tp_ws_bytes(ns, ni, B, K),), dtype=torch.uint8, device=x.device)
     gcoef = torch.empty((ncoef,), dtype=torch.float32, device=x.device)
-    groot = torch.empty((3,), dtype=torch.float32, device=x.device) if root_kind == ROOT_DIODE_PAIR else None
+    groot = _ss_groot(root_kind, x.device)
     gz0 = torch.empty((ns, B), dtype=torch.float32, device=x.device) if want_gz0 else None
     rc = lib().wdf_ss_bwd_tp(_ptr(x), _ptr(coef), _ptr(rootp), ns, ni, root_kind, int(n_up), int(n_down), _ptr(zstash),
                              _ptr(gy), _ptr(ws), _ptr(gcoef), _ptr(groot), _ptr(gz0), B, T, K, _stream())

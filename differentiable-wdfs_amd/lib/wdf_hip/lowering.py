@@ -44,7 +44,7 @@ def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
     waves = max(1, -(-B // 64))
     k_bwd = min(T // 64, (2 * N_SIMD) // waves)           # (measured at 8192 x 4096: 16 chunks 0.179 ms, 32: 0.182, 64: 0.221)
     k_fwd, W = 1, 0
-    if root_kind == binding.ROOT_DIODE_PAIR:
+    if root_kind in (binding.ROOT_DIODE_PAIR, binding.ROOT_ASYM_PAIR):      # (two different diodes: Da = 2/F - 1, F >= 1 -- the same bound)
         c = coef64.detach().double().cpu().numpy()
         A = c[:ns * ns].reshape(ns, ns)
         oE = ns * ns + ns * ni
@@ -160,11 +160,11 @@ class _StateSpaceFn(torch.autograd.Function):
         k_lin = min(T // 64, (2 * 1024) // max(1, -(-B // 64))) if (root_kind == binding.ROOT_NONE and ns > 0) else 0
         if k_lin >= 2:      # linear tree, few sequences: the exact chunked scan (csrc/wdf_statespace.h) fills the chip
             y, zs, zT = binding.ss_fwd_lin_tp(x, c, ns, ni, k_lin, want_stash=need, z0=z0d, want_zT=want_zT)
-        elif tp is not None and tp.k_fwd >= 2 and root_kind == binding.ROOT_DIODE_PAIR:
+        elif tp is not None and tp.k_fwd >= 2 and root_kind in (binding.ROOT_DIODE_PAIR, binding.ROOT_ASYM_PAIR):
             # nonlinear root: chunks warmed up from z = 0, verified on the device, missed waves re-run sequentially
             k, W, zinit = (tp.k_fwd, tp.warmup, None) if (warm is None or not need or z0d is not None) else warm.start()
             y, zs, zT, st = binding.ss_fwd_tp(x, c, ns, ni, rp, k, W, tp.tol, n_up, n_down, want_stash=need,
-                                              z0=z0d, want_zT=want_zT, zinit=zinit)
+                                              z0=z0d, want_zT=want_zT, zinit=zinit, root_kind=root_kind)
             LAST_SS_TP_STATUS["status"] = st
             LAST_SS_TP_STATUS["warmup_used"], LAST_SS_TP_STATUS["chunks_used"] = W, k
             if warm is not None and need and z0d is None:
@@ -688,8 +688,16 @@ def diode_pair_reflected(dp):
 # ------------------------------------------------------------------------------ Circuit
 class Circuit:
     """The fast tier.  top: element connected to the root (e.g. the Inverter of lpf.py:28 or
-    P1 of clipper_pot.py:99); root: IdealVoltageSource, DiodePair or layers.DenseRootModel;
+    P1 of clipper_pot.py:99); root: IdealVoltageSource, DiodePair, AsymDiodePair or layers.DenseRootModel;
     probe: element whose voltage() is the output (C1 in lpf.py:44, C in clipper_pot.py:123).
+
+    An AsymDiodePair root (two different diodes, the exact Shockley pair) runs on the diode-clipper tree probed at the
+    capacitor, on kernels of its own (csrc/wdf_asym.h).  Built with any_tree=True it also terminates any tree of at most three
+    capacitors and two sources, any probe, and the clipper tree under force_generic: the state-space kernels of
+    csrc/wdf_statespace.h (sequential and time-parallel forward, both reverse sweeps) solve the pair by Newton in fp32 at
+    every step, gradients flow to the four diode Variables and, through the port resistance and the step's matrices, to the
+    components; mse / mse_esr compose the loss from the forward there.  Off the clipper's own kernels the root takes
+    solver="newton_f32" only, no per_sample_R / per_sequence_R and no to_device().
 
     Input channels: channel k of x feeds the k-th voltage source found walking the tree in
     post-order (ResistiveVoltageSource leaves), then the ideal-source root if there is one.
@@ -724,10 +732,33 @@ class Circuit:
                              "tf_wdf.py:51-52,80-81)")
         if self.ni < 1:
             raise ValueError("the circuit has no voltage source")
-        if self.root_kind == "AsymDiodePair" and not (self._is_clipper() and per_sample_R is None and not self.force_generic):
+        asym = self.root_kind == "AsymDiodePair"
+        own = self._is_clipper() and not self.force_generic       # the two-different-diode clipper's own kernels (csrc/wdf_asym.h)
+        if asym and not getattr(root, "any_tree", False) and not (own and per_sample_R is None):
             raise binding.WdfHipError("an AsymDiodePair root runs on the diode-clipper tree only: top = Parallel(ResistiveVoltageSource, "
                                       "Capacitor), probe = the capacitor, no per_sample_R (a pot that is constant along every "
-                                      "sequence goes in as per_sequence_R), not force_generic (csrc/wdf_asym.h)")
+                                      "sequence goes in as per_sequence_R), not force_generic (csrc/wdf_asym.h); "
+                                      "AsymDiodePair(..., any_tree=True) takes the generic state-space kernels on any small tree")
+        # AsymDiodePair(any_tree=True) off the clipper's own kernels: the generic state-space kernels, root kind ROOT_ASYM_PAIR
+        self._asym_generic = asym and not own
+        if asym and per_sample_R is not None:
+            raise binding.WdfHipError("per_sample_R is not supported under an AsymDiodePair root: the root's kernels take static "
+                                      "coefficients (a pot that is constant along every sequence goes in as per_sequence_R on "
+                                      "the diode-clipper tree)")
+        if self._asym_generic:
+            if root.mode != binding.ASYM_NEWTON_F32:
+                raise binding.WdfHipError("an AsymDiodePair root on the generic state-space kernels takes solver='newton_f32' only "
+                                          f"(got {root.solver!r}): the fp64 Newton mode and the omega closed form run on the "
+                                          "diode-clipper tree's own kernels")
+            if per_sequence_R is not None:
+                raise binding.WdfHipError("per_sequence_R under an AsymDiodePair root belongs to the diode-clipper tree's own "
+                                          "kernels (probe = the capacitor, not force_generic): the generic state-space kernels "
+                                          "take static coefficients")
+            if self.ns > 3 or self.ni > 2:
+                raise binding.WdfHipError("an AsymDiodePair root runs on trees of at most three capacitors and two sources "
+                                          f"(this one has {self.ns} and {self.ni}): with four states the chunked reverse sweep's "
+                                          "sums for this root do not fit a wave's registers, so csrc/wdf_statespace.h is not "
+                                          "built for it there")
         self.per_sequence_R = per_sequence_R
         if per_sequence_R is not None:
             if self.root_kind != "AsymDiodePair":
@@ -758,7 +789,8 @@ class Circuit:
         its float64 probe on the host and needs the Variables there.  Returns self."""
         if self.root_kind == "AsymDiodePair":
             raise binding.WdfHipError("Circuit.to_device: there is no resident training step for an AsymDiodePair root; the circuit "
-                                      "trains on the host path (its forward and reverse sweep are single launches either way)")
+                                      "trains on the host path (its forward and reverse sweep are single launches either way; "
+                                      "on a generic tree the step's matrices are probed on the host)")
         binding.require_gpu()
         if any(getattr(self, a, None) is not None for a in ("_lin", "_pblock", "_tree", "_mlp", "_dynres")):
             return self
@@ -877,7 +909,8 @@ class Circuit:
         which is what clipper_pot.py:110-111 does before every forward)."""
         binding.require_gpu()
         stateful = (z0 is not None or carry_state) and self.ns > 0
-        if self.root_kind == "AsymDiodePair" and self.root.mode != binding.ASYM_OMEGA_F32 and 0 <= int(skip) < int(np.shape(x)[1]):
+        if self.root_kind == "AsymDiodePair" and not self._asym_generic and self.root.mode != binding.ASYM_OMEGA_F32 \
+                and 0 <= int(skip) < int(np.shape(x)[1]):
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
             return self._mse_esr_clipper_asym(x, target, int(skip), z0, stateful)      # the Newton solvers: the one-pass step
@@ -990,7 +1023,7 @@ class Circuit:
             if stateful:
                 self.last_state = ent["zT"].clone()              # (ent["zT"] is one of two ping-pong buffers: [ns,B], kept by value)
             return loss
-        if self.root_kind == "AsymDiodePair" and self.root.mode != binding.ASYM_OMEGA_F32:
+        if self.root_kind == "AsymDiodePair" and not self._asym_generic and self.root.mode != binding.ASYM_OMEGA_F32:
             return self._mse_clipper_asym(x, target, z0, stateful)      # the Newton solvers: the one-pass step
         if stateful:
             y, zT = self(x, z0=z0, return_state=True)
@@ -1098,7 +1131,7 @@ class Circuit:
             return self._run_dyn(x, z0, return_state)
         if self._is_clipper() and self.root_kind == "DiodePair" and not self.force_generic:
             return self._run_clipper(x, z0, return_state)
-        if self.root_kind == "AsymDiodePair":
+        if self.root_kind == "AsymDiodePair" and not self._asym_generic:
             return self._run_clipper_asym(x, z0, return_state)
         if self.root_kind == "DenseRootModel":
             from . import mlp_root
@@ -1126,6 +1159,13 @@ class Circuit:
                                      dp.nVt.as_subclass(torch.Tensor).double().reshape(()),
                                      r_port.double().reshape(())]).to(device=dev, dtype=torch.float32)
                 kind, n_up, n_down = binding.ROOT_DIODE_PAIR, dp.N_up, dp.N_down
+            elif self.root_kind == "AsymDiodePair":
+                # two different diodes on the generic kernels: the four diode Variables and the port resistance the tree shows
+                dp = self.root
+                rootp = torch.stack([v.as_subclass(torch.Tensor).double().reshape(()) for v in
+                                     (dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down)]
+                                    + [r_port.double().reshape(())]).to(device=dev, dtype=torch.float32)
+                kind, n_up, n_down = binding.ROOT_ASYM_PAIR, 1, 1
             else:
                 rootp, kind, n_up, n_down = None, binding.ROOT_NONE, 1, 1
         z0t = None if z0 is None else z0.as_subclass(torch.Tensor).to(dev).float().reshape(self.ns, -1).contiguous()
@@ -1140,7 +1180,8 @@ class Circuit:
         elif not isinstance(tp, SsTpPlan):
             tp = None
         warm = None
-        if tp is not None and tp.k_fwd >= 2 and kind == binding.ROOT_DIODE_PAIR and self._anchor is not None and self.warm_start:
+        if tp is not None and tp.k_fwd >= 2 and kind in (binding.ROOT_DIODE_PAIR, binding.ROOT_ASYM_PAIR) and self._anchor is not None \
+                and self.warm_start:
             # the caller's tensor object and version name the batch: the same one again -> its chunks start warm
             ws = self.__dict__.setdefault("_ss_warm", ObjectMemo(4))
             warm = ws.get(self._anchor, tuple(x.shape))

@@ -442,11 +442,24 @@ int wdf_clipper_mlp_step(const float* x, const float* p, const float* lr, const 
  * coef    device float[wdf_ss_ncoef(ns, ni)]:
  *         A[ns][ns] | Bx[ns][ni] | E[ns] | ca[ns] | da[ni] | cy[ns] | dy[ni] | fy
  * root_kind  WDF_ROOT_NONE (ideal source folded into the matrices; IdealVoltageSource
- *         tf_wdf.py:13-28) or WDF_ROOT_DIODE_PAIR with rootp = device float[3] {Is, nVt, R_port}
+ *         tf_wdf.py:13-28), WDF_ROOT_DIODE_PAIR with rootp = device float[3] {Is, nVt, R_port} (n_up / n_down copies of
+ *         ONE diode, the Wright-omega closed form), or WDF_ROOT_ASYM_PAIR with rootp = device float[5] {Is_up, nVt_up,
+ *         Is_down, nVt_down, R_port}: two DIFFERENT antiparallel diodes, the exact Shockley pair
+ *             i(v) = Is_up (exp(v / nVt_up) - 1) - Is_down (exp(-v / nVt_down) - 1),  a = v + R_port i,  b = 2 v - a
+ *         solved by Newton in fp32 at every step (csrc/wdf_asym.h asym_newton32_solve: stop rule at its fp32 floor,
+ *         4 FLT_EPSILON, at most 50 iterations -- compile-time constants here); n_up and n_down are ignored.
+ *         ns <= 3 under this root: at four states the chunked reverse sweep's five root sums per run do not fit a wave's
+ *         registers (VGPR spills / scratch), so no kernel of the family is built there: WDF_EUNSUPPORTED.
  * x       [B][T][ni] ; y [T][B] ; zstash [T][ns][B] ; z0, zT, gz0 [ns][B]
- * bwd:    gcoef[ncoef] = dL/dcoef, groot[3] = dL/d{Is, nVt, R_port}; ws of wdf_ss_bwd_ws_bytes.
+ * bwd:    gcoef[ncoef] = dL/dcoef, groot[3] = dL/d{Is, nVt, R_port} (WDF_ROOT_ASYM_PAIR: groot[5] = dL/d{Is_up, nVt_up,
+ *         Is_down, nVt_down, R_port}; the root is solved again from the stash, the same b bit for bit, and differentiated
+ *         implicitly there); ws of wdf_ss_bwd_ws_bytes.  A null rootp (fwd, bwd) or groot (bwd) under a root that needs
+ *         it is WDF_EINVAL.
+ * The workspaces of the two reverse sweeps hold per-wave rows of wdf_ss_ncoef + 5 doubles -- the two-different-diode root's
+ * five sums; the *_ws_bytes functions take no root and size for it whatever the root (the other roots use kN + 2 of a row).
  * ---------------------------------------------------------------------------------- */
-enum { WDF_ROOT_NONE = 0, WDF_ROOT_DIODE_PAIR = 2, WDF_ROOT_MLP = 3 /* wdf_ss_dyn_* only */ };
+enum { WDF_ROOT_NONE = 0, WDF_ROOT_DIODE_PAIR = 2, WDF_ROOT_MLP = 3 /* wdf_ss_dyn_* only */,
+       WDF_ROOT_ASYM_PAIR = 4 /* wdf_ss_fwd / _bwd / _fwd_tp_root / _bwd_tp only */ };
 
 int wdf_ss_ncoef(int ns, int ni);
 int wdf_ss_fwd(const float* x, const float* coef, const float* rootp,
@@ -469,7 +482,8 @@ int wdf_ss_bwd(const float* x, const float* coef, const float* rootp,
 
 /* Time-parallel forms of the two calls above (csrc/wdf_statespace.h, second half) for trees with >= 1 state; n_chunks
  * must be a value wdf_ss_tp_chunks returns (chunks of a multiple of 8 steps).
- * wdf_ss_fwd_tp (diode root): chunk k starts `warmup` steps early from z = 0 -- or, with zinit [n_chunks][ns][B], from
+ * wdf_ss_fwd_tp (diode root) / wdf_ss_fwd_tp_root (the same with the root kind as an argument: WDF_ROOT_DIODE_PAIR or
+ *   WDF_ROOT_ASYM_PAIR; wdf_ss_fwd_tp is wdf_ss_fwd_tp_root with WDF_ROOT_DIODE_PAIR): chunk k starts `warmup` steps early from z = 0 -- or, with zinit [n_chunks][ns][B], from
  *   the states the caller supplies for the samples wdf_ss_tp_starts names (a training loop that re-visits its batch hands
  *   in the previous call's stash rows: a fraction of the cold warm-up then closes the gap); chunk boundaries are verified
  *   on the device (|arrival - predecessor's end| <= tol per state) and the sequential kernel, launched behind it, re-runs
@@ -484,6 +498,9 @@ int wdf_ss_tp_starts(int64_t T, int n_chunks, int warmup, int64_t* starts /* [n_
 int wdf_ss_fwd_tp(const float* x, const float* coef, const float* rootp, int ns, int ni, int n_up, int n_down, float* y,
                   float* zstash, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol,
                   const float* zinit, void* ws, void* status, void* stream);
+int wdf_ss_fwd_tp_root(const float* x, const float* coef, const float* rootp, int ns, int ni, int root_kind, int n_up, int n_down,
+                       float* y, float* zstash, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol,
+                       const float* zinit, void* ws, void* status, void* stream);
 size_t wdf_ss_bwd_tp_ws_bytes(int ns, int ni, int64_t B, int n_chunks);
 int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns, int ni, int root, int n_up, int n_down,
                   const float* zstash, const float* gy, void* ws, float* gcoef, float* groot, float* gz0, int64_t B, int64_t T,
