@@ -284,7 +284,9 @@ class AsymDiodePair(_Element):
     kernels (csrc/wdf_statespace.h, root kind WDF_ROOT_ASYM_PAIR: sequential and time-parallel forward, sequential and
     chunked reverse sweep) with the pair solved by Newton in fp32 at every step; gradients reach the four diode Variables and,
     through the port resistance and the step's matrices, every component; Circuit.mse / mse_esr compose the loss from the
-    forward.  The clipper tree probed at its capacitor keeps its own kernels and one-pass steps.  On the generic kernels the
+    forward.  Trees of one or two capacitors also have a one-pass training step there (csrc/wdf_ss_asym_step.h: forward, loss
+    and every gradient in one sweep, Circuit._asym_tree_step; mse / mse_esr take it for a loss once tools/ss_asym_step_bench.py
+    has shown it faster than composing: lowering.ASYM_TREE_STEP_SERVES).  The clipper tree probed at its capacitor keeps its own kernels and one-pass steps.  On the generic kernels the
     root takes solver="newton_f32" only and no per_sample_R / per_sequence_R; to_device() stays unsupported.'''
 
     SOLVERS = {"omega_f32": 0, "newton_f64": 1, "newton_f32": 2}          # wdf_hip.binding.ASYM_*

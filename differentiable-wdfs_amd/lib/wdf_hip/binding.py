@@ -283,6 +283,15 @@ def lib():
     L.wdf_ss_bwd_tp.argtypes = [fp, fp, fp, ci, ci, ci, ci, ci, fp, fp, vp, fp, fp, fp, i64, i64, ci, vp]
     L.wdf_ss_bwd_ws_bytes.restype = C.c_size_t
     L.wdf_ss_bwd_ws_bytes.argtypes = [ci, ci, i64]
+    L.wdf_ss_asym_step_ws_bytes.restype = C.c_size_t
+    L.wdf_ss_asym_step_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
+    L.wdf_ss_asym_step_esr_ws_bytes.restype = C.c_size_t
+    L.wdf_ss_asym_step_esr_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
+    L.wdf_ss_asym_step_mse.restype = ci
+    L.wdf_ss_asym_step_mse.argtypes = [fp, fp, fp, ci, ci, fp, cf, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, fp, vp]
+    L.wdf_ss_asym_step_esr.restype = ci
+    L.wdf_ss_asym_step_esr.argtypes = [fp, fp, fp, ci, ci, fp, C.c_double, C.c_double, i64, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp,
+                                       fp, fp, fp, vp]
     L.wdf_omega_f32.restype = ci
     L.wdf_omega_f32.argtypes = [fp, fp, vp, i64, vp]
     L.wdf_omega_f64.restype = ci
@@ -338,6 +347,7 @@ EXPORTED_SYMBOLS = (
     "wdf_ss_nl_step_mse", "wdf_ss_nl_step_esr_ws_bytes", "wdf_ss_nl_step_esr",
     "wdf_ss_ncoef", "wdf_ss_fwd", "wdf_ss_bwd", "wdf_ss_bwd_ws_bytes", "wdf_ss_fwd_lin_tp_ws_bytes", "wdf_ss_fwd_lin_tp",
     "wdf_ss_tp_chunks", "wdf_ss_tp_starts", "wdf_ss_fwd_tp_ws_bytes", "wdf_ss_fwd_tp", "wdf_ss_fwd_tp_root", "wdf_ss_bwd_tp_ws_bytes", "wdf_ss_bwd_tp",
+    "wdf_ss_asym_step_ws_bytes", "wdf_ss_asym_step_esr_ws_bytes", "wdf_ss_asym_step_mse", "wdf_ss_asym_step_esr",
     "wdf_omega_f32", "wdf_omega_f64", "wdf_diode_pair_f32", "wdf_adam_step", "wdf_adam_step_multi",
     "wdf_event_create", "wdf_event_record", "wdf_event_elapsed_ms", "wdf_event_destroy", "wdf_event_bracket_next",
     "wdf_clock_stamp",
@@ -1429,6 +1439,96 @@ def ss_fwd_tp(x, coef, ns, ni, rootp, n_chunks, warmup, tol=1e-6, n_up=1, n_down
 def ss_tp_status(status):
     s = status.cpu()
     return {"n_bad": int(s[0]), "max_miss": float(s[1:2].view(torch.float32)[0]), "gated_waves": int(s[2])}
+
+
+def ss_asym_step_built(ns, ni, loss="mse"):
+    """Whether the one-pass step of a tree under ROOT_ASYM_PAIR is built for (ns, ni) and this loss ("mse" | "mse_esr"): the
+    library answers a workspace size of 0 where it is not (no GPU needed)."""
+    f = lib().wdf_ss_asym_step_esr_ws_bytes if loss == "mse_esr" else lib().wdf_ss_asym_step_ws_bytes
+    return f(int(ns), int(ni), 64, 64, 1) > 0
+
+
+def _ss_asym_step_args(who, x, coef, rootp, ns, ni, target, n_chunks, y, z0, want_zT, ws, status):
+    x, coef, rootp, target, z0 = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(rootp, "rootp"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
+    B, T = x.shape[0], x.shape[1]
+    if x.numel() != B * T * ni or coef.numel() != lib().wdf_ss_ncoef(ns, ni):
+        raise WdfHipError(f"{who}: x / coef do not match ns, ni")
+    if rootp is None or rootp.numel() != 5:
+        raise WdfHipError(f"{who}: rootp must hold {{Is_up, nVt_up, Is_down, nVt_down, R_port}}")
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if z0 is not None and tuple(z0.shape) != (ns, B):
+        raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
+    K = lib().wdf_ss_tp_chunks(T, int(n_chunks))
+    if y is None:
+        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
+    elif tuple(_f32_dev(y, "y").shape) != (T, B):
+        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    zT = torch.empty((ns, B), dtype=torch.float32, device=x.device) if want_zT else None
+    need = lib().wdf_ss_asym_step_ws_bytes(ns, ni, B, T, K)
+    if need == 0:
+        raise WdfHipError(f"{who}: no one-pass step is built for ns={ns}, ni={ni} (compose the loss from ss_fwd_tp and ss_bwd_tp)")
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
+    if status is None:
+        status = torch.empty((4,), dtype=torch.int32, device=x.device)
+    return x, coef, rootp, target, z0, B, T, K, y, zT, ws, status
+
+
+def ss_asym_step_mse(x, coef, rootp, ns, ni, target, gscale, n_chunks=1, warmup=0, tol=1e-6, y=None, z0=None, want_zT=False, ws=None,
+                     status=None, out=None):
+    """The MSE training step of a small tree under ROOT_ASYM_PAIR in one pass over the data (wdf_ss_asym_step_mse): forward,
+    loss and d(gscale/2 sum (y - target)^2)/d{coef, rootp}; x [B,T,ni] and target [T,B] read once, y written once, no stash.
+    n_chunks is rounded like ss_fwd_tp's (1: the exact sequential recursion); y, ws, status, out can be preallocated.
+    -> y [T,B], zT [ns,B] | None, out = {sse, gcoef[ncoef], groot[5]}, status (int32[4]; read with ss_tp_status())."""
+    require_gpu()
+    x, coef, rootp, target, z0, B, T, K, y, zT, ws, status = _ss_asym_step_args("ss_asym_step_mse", x, coef, rootp, ns, ni, target,
+                                                                               n_chunks, y, z0, want_zT, ws, status)
+    n = 1 + coef.numel() + 5
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=x.device)
+    elif _f32_dev(out, "out").numel() != n:
+        raise WdfHipError(f"out must hold {{sse, gcoef, groot}} = {n} floats")
+    _check(lib().wdf_ss_asym_step_mse(_ptr(x), _ptr(coef), _ptr(rootp), int(ns), int(ni), _ptr(target), float(gscale), _ptr(y), _ptr(z0),
+                                      _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status), _ptr(out), _stream()),
+           "wdf_ss_asym_step_mse")
+    return y, zT, out, status
+
+
+def ss_asym_step_esr(x, coef, rootp, ns, ni, target, n_global, eps_energy, skip, n_chunks=1, warmup=0, tol=1e-6, y=None, z0=None,
+                     want_zT=False, ws=None, status=None, sums=None, g=None, loss3=None, finish=True):
+    """The MSE + ESR training step of a small tree under ROOT_ASYM_PAIR in one pass over the data (wdf_ss_asym_step_esr):
+    loss = S/n + sqrt(S / (E + eps_energy) / n) on the rows past `skip`, S = sum (y - target)^2, E = sum y^2, n = n_global.
+    finish=True: a single rank -- the kernel forms g = dloss/d{coef, rootp} and loss3 = {mse, esr, mse + esr} itself.
+    finish=False: one shard of several -- only sums = {S, E, gP[ncoef + 5], gQ[ncoef + 5]} of this call comes back.
+    -> y [T,B], zT [ns,B] | None, sums, g, loss3, status (int32[4]; read with ss_tp_status())."""
+    require_gpu()
+    x, coef, rootp, target, z0, B, T, K, y, zT, ws, status = _ss_asym_step_args("ss_asym_step_esr", x, coef, rootp, ns, ni, target,
+                                                                               n_chunks, y, z0, want_zT, ws, status)
+    if lib().wdf_ss_asym_step_esr_ws_bytes(ns, ni, B, T, K) == 0:
+        raise WdfHipError(f"ss_asym_step_esr: no MSE + ESR step is built for ns={ns}, ni={ni}")
+    ng = coef.numel() + 5
+    if sums is None:
+        sums = torch.empty((2 + 2 * ng,), dtype=torch.float32, device=x.device)
+    elif _f32_dev(sums, "sums").numel() != 2 + 2 * ng:
+        raise WdfHipError(f"sums must hold {{S, E, gP, gQ}} = {2 + 2 * ng} floats")
+    if not finish:
+        g = loss3 = None
+    else:
+        if g is None:
+            g = torch.empty((ng,), dtype=torch.float32, device=x.device)
+        elif _f32_dev(g, "g").numel() != ng:
+            raise WdfHipError(f"g must hold {ng} gradients")
+        if loss3 is None:
+            loss3 = torch.empty((3,), dtype=torch.float32, device=x.device)
+        elif _f32_dev(loss3, "loss3").numel() != 3:
+            raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
+    _check(lib().wdf_ss_asym_step_esr(_ptr(x), _ptr(coef), _ptr(rootp), int(ns), int(ni), _ptr(target), float(n_global), float(eps_energy),
+                                      int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status),
+                                      _ptr(sums), _ptr(g), _ptr(loss3), _stream()), "wdf_ss_asym_step_esr")
+    return y, zT, sums, g, loss3, status
 
 
 def _dyn_rows_mode(rows, T, n, B, who):

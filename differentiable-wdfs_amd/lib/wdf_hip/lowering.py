@@ -30,6 +30,10 @@ from .tensor_cache import EntryCache, ObjectMemo, tensor_key  # noqa: F401  (ten
 SsTpPlan = namedtuple("SsTpPlan", ["k_fwd", "warmup", "tol", "k_bwd"])
 LAST_SS_TP_STATUS = {"status": None}
 N_SIMD = 1024            # MI355X: 256 CUs x 4
+# Whether Circuit.mse / mse_esr take the one-pass step of csrc/wdf_ss_asym_step.h on a tree under AsymDiodePair(any_tree=True):
+# decided per loss by tools/ss_asym_step_bench.py (the step's slowest sample against the composed path's fastest, at both of its
+# shapes; profiles/r13_ss_asym_step.jsonl).  Circuit._asym_tree_step is the step either way.
+ASYM_TREE_STEP_SERVES = {"mse": False, "mse_esr": False}
 
 
 def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
@@ -189,6 +193,39 @@ class _StateSpaceFn(torch.autograd.Function):
             gcoef, groot, gz0 = binding.ss_bwd(x, c, ns, ni, zs, gy.contiguous(), root_kind, rp, n_up, n_down,
                                                want_gz0=has_z0)
         return gcoef, groot, None, gz0, None, None, None, None, None, None, None, None
+
+
+class _AsymTreeStepFn(torch.autograd.Function):
+    """loss = the one-pass step of a small tree under ROOT_ASYM_PAIR (csrc/wdf_ss_asym_step.h) over (coef, rootp): forward runs
+    the step and keeps d loss/d coef and d loss/d rootp, backward hands them back scaled by the incoming gradient -- the
+    float64 probe's graph carries them on to R, C and the diode Variables, as it does _StateSpaceFn's.
+    kind: "mse" (mean squared error) | "mse_esr" (the scripts' loss on the rows past skip).  -> loss, y [T,B], zT [ns,B] | None."""
+
+    @staticmethod
+    def forward(ctx, coef, rootp, x, target, ns, ni, kind, skip, z0, want_zT, k, W, tol):
+        c, rp = coef.detach().contiguous(), rootp.detach().contiguous()
+        B, T, nc = x.shape[0], x.shape[1], c.numel()
+        if kind == "mse":
+            n = float(B * T)
+            y, zT, out, st = binding.ss_asym_step_mse(x, c, rp, ns, ni, target, 2.0 / n, k, W, tol, z0=z0, want_zT=want_zT)
+            loss, g = out[0] / n, out[1:]
+        else:
+            n = float(B * (T - skip))
+            y, zT, _, g, loss3, st = binding.ss_asym_step_esr(x, c, rp, ns, ni, target, n, float(np.finfo(float).eps), skip, k, W, tol,
+                                                              z0=z0, want_zT=want_zT)
+            loss = loss3[2].clone()
+        LAST_SS_TP_STATUS["status"] = st
+        LAST_SS_TP_STATUS["warmup_used"], LAST_SS_TP_STATUS["chunks_used"] = W, k
+        ctx.save_for_backward(g[:nc], g[nc:])
+        ctx.mark_non_differentiable(y)
+        if zT is not None:
+            ctx.mark_non_differentiable(zT)
+        return loss, y, zT
+
+    @staticmethod
+    def backward(ctx, gl, _gy, _gzT):
+        gcoef, groot = ctx.saved_tensors
+        return (gcoef * gl, groot * gl) + (None,) * 11
 
 
 # The device tape interpreter keeps a sample's node values in LDS: its time grows with the square of the tape's length, torch's
@@ -696,7 +733,8 @@ class Circuit:
     capacitors and two sources, any probe, and the clipper tree under force_generic: the state-space kernels of
     csrc/wdf_statespace.h (sequential and time-parallel forward, both reverse sweeps) solve the pair by Newton in fp32 at
     every step, gradients flow to the four diode Variables and, through the port resistance and the step's matrices, to the
-    components; mse / mse_esr compose the loss from the forward there.  Off the clipper's own kernels the root takes
+    components; mse / mse_esr compose the loss from the forward there, and trees of one or two capacitors have a one-pass step
+    (csrc/wdf_ss_asym_step.h: _asym_tree_step; ASYM_TREE_STEP_SERVES says for which loss mse / mse_esr take it).  Off the clipper's own kernels the root takes
     solver="newton_f32" only, no per_sample_R / per_sequence_R and no to_device().
 
     Input channels: channel k of x feeds the k-th voltage source found walking the tree in
@@ -914,6 +952,10 @@ class Circuit:
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
             return self._mse_esr_clipper_asym(x, target, int(skip), z0, stateful)      # the Newton solvers: the one-pass step
+        if ASYM_TREE_STEP_SERVES["mse_esr"] and self._asym_step_tree(x, target, "mse_esr", skip):
+            if carry_state and z0 is None:
+                z0 = getattr(self, "last_state", None)
+            return self._asym_tree_step(x, target, "mse_esr", int(skip), z0, stateful)
         if stateful:
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
@@ -961,6 +1003,52 @@ class Circuit:
         loss._wdf_fused = (out, {id(v): i for i, v in live})
         self.last_output = ent["y"]
         return loss
+
+    def _asym_step_tree(self, x, target, kind="mse", skip=0):
+        """Whether the one-pass step of csrc/wdf_ss_asym_step.h can serve mse(x, target) (kind="mse") or mse_esr(x, target, skip)
+        (kind="mse_esr") on this circuit: an AsymDiodePair(any_tree=True) root on the generic state-space kernels, a tree the
+        step is built for under this loss (one or two capacitors, one or two sources), tensors in, 0 <= skip < T."""
+        if not getattr(self, "_asym_generic", False) or kind not in ("mse", "mse_esr"):
+            return False
+        if not (isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)):
+            return False
+        if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[2] != self.ni) or (x.dim() == 2 and self.ni != 1):
+            return False
+        if not 0 <= int(skip) < int(x.shape[1]):
+            return False
+        return bool(binding.ss_asym_step_built(self.ns, self.ni, kind))
+
+    def _asym_tree_step(self, x, target, kind="mse", skip=0, z0=None, stateful=False):
+        """mse(x, target) / mse_esr(x, target, skip) of a tree under AsymDiodePair(any_tree=True) as ONE pass over the data
+        (wdf_ss_asym_step_mse / _esr): forward, loss and the gradient of every coefficient and of the root's five values in one
+        sweep; the probe's float64 graph carries them to the components.  The chunks are plan_ss_time_parallel's (k_fwd,
+        warmup, tol) or those of an explicit SsTpPlan; time_parallel=None is the sequential recursion.  z0 [ns,B] and
+        stateful (z0 / carry_state was asked for): the kernel's own z0 / zT; last_output and last_state as in mse()."""
+        binding.require_gpu()
+        xt = x.as_subclass(torch.Tensor)
+        xt = (xt if xt.is_cuda else xt.cuda()).float()
+        if xt.dim() == 2:
+            xt = xt.unsqueeze(-1)
+        xt = xt.contiguous()
+        dev, B, T = xt.device, int(xt.shape[0]), int(xt.shape[1])
+        tgt = target.as_subclass(torch.Tensor).detach().to(dev).float().reshape(T, B).contiguous()
+        coef64, r_port = self.matrices()
+        coef = coef64.to(device=dev, dtype=torch.float32)
+        dp = self.root
+        rootp = torch.stack([v.as_subclass(torch.Tensor).double().reshape(()) for v in (dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down)]
+                            + [r_port.double().reshape(())]).to(device=dev, dtype=torch.float32)
+        tp = self.time_parallel
+        if tp == "auto":
+            tp = plan_ss_time_parallel(coef64, self.ns, self.ni, binding.ROOT_ASYM_PAIR, B, T)
+        elif not isinstance(tp, SsTpPlan):
+            tp = None
+        k, W, tol = (int(tp.k_fwd), int(tp.warmup), float(tp.tol)) if (tp is not None and tp.k_fwd >= 2) else (1, 0, 1.0e-6)
+        z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(dev).float().reshape(self.ns, B).contiguous()
+        loss, y, zT = _AsymTreeStepFn.apply(coef, rootp, xt, tgt, self.ns, self.ni, kind, int(skip), z0t, bool(stateful), k, W, tol)
+        self.last_output = y
+        if stateful:
+            self.last_state = zT
+        return loss.as_subclass(tf.Tensor)
 
     def _nl_step_tree(self, x, target, skip=0, z0=None, carry_state=False):
         """The resident tree whose one-pass MSE + ESR step (wdf_ss_nl_step_esr) can serve mse_esr(x, target, skip), or None: the
@@ -1025,6 +1113,8 @@ class Circuit:
             return loss
         if self.root_kind == "AsymDiodePair" and not self._asym_generic and self.root.mode != binding.ASYM_OMEGA_F32:
             return self._mse_clipper_asym(x, target, z0, stateful)      # the Newton solvers: the one-pass step
+        if ASYM_TREE_STEP_SERVES["mse"] and self._asym_step_tree(x, target, "mse"):
+            return self._asym_tree_step(x, target, "mse", 0, z0, stateful)     # any small tree under this root: its one-pass step
         if stateful:
             y, zT = self(x, z0=z0, return_state=True)
             self.last_state, self.last_output = zT.detach(), y.detach()

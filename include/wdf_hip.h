@@ -507,6 +507,33 @@ int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns,
                   int n_chunks, void* stream);
 size_t wdf_ss_bwd_ws_bytes(int ns, int ni, int64_t B);
 
+/* One-pass training step of a small tree under WDF_ROOT_ASYM_PAIR (csrc/wdf_ss_asym_step.h): forward, loss and the gradient of
+ * every coefficient and of the root's five values in one sweep -- x and target read once, y written once, no state stash, one
+ * root solve per sample -- by carrying the state's forward-mode tangents.  ns in 1..2, ni in 1..2 for both losses; ns = 3
+ * answers WDF_EUNSUPPORTED and a workspace size of 0 (its kernels do not fit a wave's registers without scratch): compose the
+ * loss from wdf_ss_fwd_tp_root and wdf_ss_bwd_tp there.
+ * x [B][T][ni] as wdf_ss_fwd takes it; target, y [T][B]; coef in the order above; rootp = {Is_up, nVt_up, Is_down, nVt_down,
+ * R_port}; z0, zT [ns][B] (optional; zT must not alias z0).
+ * n_chunks: a value wdf_ss_tp_chunks returns; 1 is the exact sequential recursion.  Chunk k > 0 starts `warmup` steps early
+ * (at most a chunk's length) from z = 0; boundaries are verified on the device at tol per state (status: the four words of
+ * wdf_ss_fwd_tp_root) and a wave that missed is re-run as ONE chunk by a gated launch of the same kernel, whose record replaces
+ * the wave's: results are within tol of n_chunks = 1 or ARE its results, and they repeat bit for bit from call to call.
+ * ws: wdf_ss_asym_step_ws_bytes bytes, 8-byte aligned (sized for the MSE + ESR step: it serves both entry points;
+ * wdf_ss_asym_step_esr_ws_bytes is the same number where the MSE + ESR step is built and 0 where it is not).
+ * mse: out[1 + ncoef + 5] = {sum (y - target)^2, gscale/2 d sum/d coef[ncoef], gscale/2 d sum/d rootp[5]}.
+ * esr: loss = S/n + sqrt(S / (E + eps_energy) / n) on the rows t >= skip (0 <= skip < T), S = sum (y - target)^2, E = sum y^2,
+ *      n = n_global.  sums[2 + 2 (ncoef + 5)] = {S, E, gP[ncoef + 5], gQ[ncoef + 5]} of THIS call, gP = d(S/2)/d{coef, rootp},
+ *      gQ = d(E/2)/d{coef, rootp}: what several ranks all-reduce.  g != NULL: the call finishes as a single rank --
+ *      g[ncoef + 5] = ga gP + gb gQ and (optional) loss3 = {mse, esr, mse + esr}, ga and gb from S, E, n, eps in fp64. */
+size_t wdf_ss_asym_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+size_t wdf_ss_asym_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+int wdf_ss_asym_step_mse(const float* x, const float* coef, const float* rootp, int ns, int ni, const float* target, float gscale,
+                         float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol, void* ws,
+                         void* status, float* out, void* stream);
+int wdf_ss_asym_step_esr(const float* x, const float* coef, const float* rootp, int ns, int ni, const float* target, double n_global,
+                         double eps_energy, int64_t skip, float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks,
+                         int warmup, float tol, void* ws, void* status, float* sums, float* g, float* loss3, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * State-space recursion with PER-SAMPLE coefficient rows, and the MLP root on any small tree (round 5; csrc/wdf_ss_dyn.h).
  * Replaces, for any tree of <= 8 capacitors (round 6; 4 until round 5) and <= 2 sources:
