@@ -70,6 +70,69 @@ int wdf_esr_coef(const double* sums, double n, double eps, float* gcoef, float* 
     return check_launch("wdf_esr_coef");
 }
 
+// ---- the weighted loss family (csrc/wdf_elementwise.h: MSE, ESR, pre-emphasised ESR, mean) ----
+int64_t wdf_loss_terms_ws_bytes(void) { return 2048 * 6 * (int64_t)sizeof(double); }
+
+static int loss_terms_shape_check(int64_t B, int64_t T, int64_t skip)
+{
+    if (B <= 0 || T <= 0 || skip < 0 || skip >= T) return fail(WDF_EINVAL, "need B, T > 0 and 0 <= skip < T");
+    return WDF_OK;
+}
+
+static int loss_terms_coeff_check(double c)
+{
+    if (!(c >= 0.0 && c < 1.0)) return fail(WDF_EINVAL, "the pre-emphasis coefficient must be in [0, 1) (got %g)", c);
+    return WDF_OK;
+}
+
+int wdf_loss_terms_sums(const float* y, const float* target, int64_t B, int64_t T, int64_t skip, double c, void* ws,
+                        double* sums6, void* stream)
+{
+    if (!y || !target || !ws || !sums6) return fail(WDF_EINVAL, "null y/target/ws/sums6");
+    if (int rc = loss_terms_shape_check(B, T, skip)) return rc;
+    if (int rc = loss_terms_coeff_check(c)) return rc;
+    if (!aligned8(ws) || !aligned8(sums6)) return fail(WDF_EINVAL, "ws and sums6 must be 8-byte aligned");
+    const int64_t n0 = skip * B, n1 = T * B;
+    const unsigned nblk = loss_blocks(n1 - n0);
+    const bool vec = B % 4 == 0 && aligned16(y) && aligned16(target);
+    auto kernel = vec ? wdf::loss_terms_sums_kernel<true> : wdf::loss_terms_sums_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, y, target, n0, n1, B, (float)c, (double*)ws);
+    hipLaunchKernelGGL(wdf::loss_terms_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, (int)nblk,
+                       sums6);
+    return check_launch("wdf_loss_terms_sums");
+}
+
+int wdf_loss_terms_coef(const double* sums6, double n, double eps, const double* w4, double c, float* gcoef, float* terms,
+                        void* stream)
+{
+    if (!sums6 || !w4 || !gcoef || !terms) return fail(WDF_EINVAL, "null sums6/w4/gcoef/terms");
+    if (!(n > 0.0)) return fail(WDF_EINVAL, "n must be positive");
+    if (!(eps >= 0.0)) return fail(WDF_EINVAL, "eps must not be negative");
+    if (int rc = loss_terms_coeff_check(c)) return rc;
+    double total = 0.0;
+    for (int k = 0; k < 4; ++k) {
+        if (!(w4[k] >= 0.0)) return fail(WDF_EINVAL, "weight %d is negative (or not a number): {mse, esr, esr_emph, avg} >= 0", k);
+        total += w4[k];
+    }
+    if (!(total > 0.0)) return fail(WDF_EINVAL, "the weights {mse, esr, esr_emph, avg} are all zero");
+    hipLaunchKernelGGL(wdf::loss_terms_coef_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sums6, n, eps,
+                       wdf::LossWeights{w4[0], w4[1], w4[2], w4[3]}, c, gcoef, terms);
+    return check_launch("wdf_loss_terms_coef");
+}
+
+int wdf_loss_terms_grad(const float* y, const float* target, const float* gcoef, double c, int64_t B, int64_t T, int64_t skip,
+                        float* gy, void* stream)
+{
+    if (!y || !target || !gcoef || !gy) return fail(WDF_EINVAL, "null y/target/gcoef/gy");
+    if (int rc = loss_terms_shape_check(B, T, skip)) return rc;
+    if (int rc = loss_terms_coeff_check(c)) return rc;
+    const bool vec = B % 4 == 0 && aligned16(y) && aligned16(target) && aligned16(gy);
+    auto kernel = vec ? wdf::loss_terms_grad_kernel<true> : wdf::loss_terms_grad_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(loss_blocks(T * B)), dim3(256), 0, (hipStream_t)stream, y, target, gcoef, c, skip * B, T * B, B,
+                       gy);
+    return check_launch("wdf_loss_terms_grad");
+}
+
 int wdf_omega_f32(const float* x, float* w, int32_t* iters, int64_t n, void* stream)
 {
     if (!x || !w || n <= 0) return fail(WDF_EINVAL, "wdf_omega_f32: bad arguments");

@@ -119,6 +119,14 @@ def lib():
     L.wdf_esr_coef.argtypes = [vp, C.c_double, C.c_double, fp, fp, vp]
     L.wdf_loss_esr_grad.restype = ci
     L.wdf_loss_esr_grad.argtypes = [fp, fp, fp, i64, i64, i64, fp, vp]
+    L.wdf_loss_terms_ws_bytes.restype = i64
+    L.wdf_loss_terms_ws_bytes.argtypes = []
+    L.wdf_loss_terms_sums.restype = ci
+    L.wdf_loss_terms_sums.argtypes = [fp, fp, i64, i64, i64, C.c_double, vp, vp, vp]
+    L.wdf_loss_terms_coef.restype = ci
+    L.wdf_loss_terms_coef.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_double, fp, fp, vp]
+    L.wdf_loss_terms_grad.restype = ci
+    L.wdf_loss_terms_grad.argtypes = [fp, fp, fp, C.c_double, i64, i64, i64, fp, vp]
     L.wdf_clipper_bwd_esr_tp.restype = ci
     L.wdf_clipper_bwd_esr_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, fp, i64, vp, fp, fp, fp, ci, i64, i64, ci,
                                          ci, vp]
@@ -325,6 +333,7 @@ EXPORTED_SYMBOLS = (
     "wdf_clipper_bwd_tp_ws_bytes", "wdf_clipper_bwd_tp_ws_init", "wdf_clipper_bwd_tp", "wdf_clipper_bwd_mse_tp",
     "wdf_clipper_bwd_mse_tp_adam", "wdf_clipper_step_mse_tp_ws_bytes", "wdf_clipper_step_mse_tp_ws_init",
     "wdf_clipper_step_mse_tp", "wdf_clipper_step_esr_tp", "wdf_esr_finish", "wdf_loss_sums_ws_bytes", "wdf_loss_sums", "wdf_esr_coef", "wdf_loss_esr_grad", "wdf_clipper_bwd_esr_tp",
+    "wdf_loss_terms_ws_bytes", "wdf_loss_terms_sums", "wdf_loss_terms_coef", "wdf_loss_terms_grad",
     "wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp_ws_bytes", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_ws_bytes", "wdf_clipper_asym_bwd",
     "wdf_clipper_asym_bwd_tp_ws_bytes", "wdf_clipper_asym_bwd_tp", "wdf_asym_root",
     "wdf_clipper_asym_step_mse_ws_bytes", "wdf_clipper_asym_step_mse",
@@ -736,6 +745,88 @@ def loss_esr_grad(y, target, gcoef, skip, gy=None):
     if gy is None:
         gy = torch.empty_like(y)
     _check(lib().wdf_loss_esr_grad(_ptr(y), _ptr(target), _ptr(gcoef), B, T, int(skip), _ptr(gy), _stream()), "wdf_loss_esr_grad")
+    return gy
+
+
+def check_loss_weights(weights, coeff):
+    """The four weights {mse, esr, esr_emph, avg} (each >= 0, not all 0) and the pre-emphasis coefficient (0 <= c < 1) as
+    floats; ValueError otherwise -- what wdf_loss_terms_coef rejects, said before anything touches the device."""
+    w = tuple(float(v) for v in weights)
+    c = float(coeff)
+    if len(w) != 4:
+        raise ValueError(f"the loss takes four weights {{mse, esr, esr_emph, avg}}, got {len(w)}")
+    if not all(v >= 0.0 for v in w):
+        raise ValueError(f"the loss weights {{mse, esr, esr_emph, avg}} must not be negative, got {w}")
+    if not sum(w) > 0.0:
+        raise ValueError("the loss weights {mse, esr, esr_emph, avg} are all zero")
+    if not 0.0 <= c < 1.0:
+        raise ValueError(f"the pre-emphasis coefficient must be in [0, 1), got {c}")
+    return w, c
+
+
+def _loss_terms_pair(y, target):
+    """y, target as float32 device tensors of one shape [T,B].  Dense, but not necessarily at a 16-byte address: a view that
+    starts one float into its storage takes the kernels' scalar loads."""
+    y, target = _f32_dev(y, "y"), _f32_dev(target, "target")
+    if y.dim() != 2 or tuple(target.shape) != tuple(y.shape):
+        raise WdfHipError("y and target must have one shape [T,B]")
+    return y, target
+
+
+def loss_terms_sums(y, target, skip, coeff=0.85, sums6=None, ws=None):
+    """sums6 = {S, E, Sp, Ep, So, St} over rows skip.. of [T,B] arrays -> float64[6] on the device (wdf_loss_terms_sums):
+    S = sum (y-t)^2, E = sum y^2, Sp / Ep the same behind the pre-emphasis filter v[k] - coeff v[k-1] along time, So = sum y,
+    St = sum t.  Fixed-order reduction: the same inputs give the same bits."""
+    require_gpu()
+    y, target = _loss_terms_pair(y, target)
+    T, B = y.shape
+    if ws is None:
+        ws = torch.empty((lib().wdf_loss_terms_ws_bytes(),), dtype=torch.uint8, device=y.device)
+    if sums6 is None:
+        sums6 = torch.empty((6,), dtype=torch.float64, device=y.device)
+    elif sums6.dtype != torch.float64 or not sums6.is_cuda or sums6.numel() != 6 or not sums6.is_contiguous():
+        raise WdfHipError("sums6 must be a float64[6] device tensor")
+    _check(lib().wdf_loss_terms_sums(_ptr(y), _ptr(target), B, T, int(skip), float(coeff), _ptr(ws), _ptr(sums6), _stream()),
+           "wdf_loss_terms_sums")
+    return sums6
+
+
+def loss_terms_coef(sums6, n, eps, weights, coeff=0.85, gcoef=None, terms=None):
+    """(gcoef[6] = {ga, gb, al, be, gm, c}, terms[5] = {mse, esr, esr_emph, avg, loss}) from the global sums6 and sample count n;
+    weights = (w_mse, w_esr, w_emph, w_avg); see include/wdf_hip.h (wdf_loss_terms_coef)."""
+    require_gpu()
+    if sums6.dtype != torch.float64 or not sums6.is_cuda or sums6.numel() != 6 or not sums6.is_contiguous():
+        raise WdfHipError("sums6 must be a float64[6] device tensor")
+    if len(weights) != 4:
+        raise WdfHipError("weights = (w_mse, w_esr, w_emph, w_avg)")
+    gcoef, terms = _f32_dev(gcoef, "gcoef"), _f32_dev(terms, "terms")
+    if gcoef is None:
+        gcoef = torch.empty((6,), dtype=torch.float32, device=sums6.device)
+    if terms is None:
+        terms = torch.empty((5,), dtype=torch.float32, device=sums6.device)
+    if gcoef.numel() != 6 or terms.numel() != 5:
+        raise WdfHipError("gcoef holds 6 floats, terms 5")
+    w4 = (C.c_double * 4)(*[float(v) for v in weights])
+    _check(lib().wdf_loss_terms_coef(_ptr(sums6), float(n), float(eps), w4, float(coeff), _ptr(gcoef), _ptr(terms), _stream()),
+           "wdf_loss_terms_coef")
+    return gcoef, terms
+
+
+def loss_terms_grad(y, target, gcoef, skip, coeff=0.85, gy=None):
+    """dL/dy [T,B] of the weighted loss past `skip` from the device coefficients of loss_terms_coef() (wdf_loss_terms_grad);
+    coeff: the same pre-emphasis coefficient (gcoef[5] is its float32 copy).  Rows before skip are exactly 0."""
+    require_gpu()
+    y, target = _loss_terms_pair(y, target)
+    gcoef = _f32_dev(gcoef, "gcoef")
+    T, B = y.shape
+    if gcoef.numel() != 6:
+        raise WdfHipError("gcoef = {ga, gb, al, be, gm, c}")
+    if gy is None:
+        gy = torch.empty((T, B), dtype=torch.float32, device=y.device)
+    elif _f32_dev(gy, "gy").shape != y.shape:
+        raise WdfHipError("gy must have y's shape [T,B]")
+    _check(lib().wdf_loss_terms_grad(_ptr(y), _ptr(target), _ptr(gcoef), float(coeff), B, T, int(skip), _ptr(gy), _stream()),
+           "wdf_loss_terms_grad")
     return gy
 
 

@@ -228,6 +228,40 @@ class _AsymTreeStepFn(torch.autograd.Function):
         return (gcoef * gl, groot * gl) + (None,) * 11
 
 
+class _LossTermsFn(torch.autograd.Function):
+    """loss = w_mse mse + w_esr esr + w_emph esr_emph + w_avg avg of (y, target) [T,B] past `skip` (clipper_pot.py:141-165), the
+    fused device stage of csrc/wdf_elementwise.h: forward launches sums -> (sums_allreduce(sums6), in place) -> coef -> grad and
+    returns (loss, terms[5] = {mse, esr, esr_emph, avg, loss}); backward hands back gy times the incoming scalar, for whichever
+    reverse sweep produced y.  want_grad False (a validation pass) skips the grad launch.
+    launches: how many times each kernel family went out (tests read it: a validation pass leaves "grad" alone)."""
+    launches = {"sums": 0, "coef": 0, "grad": 0}
+
+    @staticmethod
+    def forward(ctx, y, target, skip, weights, coeff, n, sums_allreduce, want_grad):
+        yd = y.detach().contiguous()
+        sums6 = binding.loss_terms_sums(yd, target, skip, coeff)
+        _LossTermsFn.launches["sums"] += 1
+        if sums_allreduce is not None:
+            sums_allreduce(sums6)
+        gcoef, terms = binding.loss_terms_coef(sums6, n, float(np.finfo(float).eps), weights, coeff)
+        _LossTermsFn.launches["coef"] += 1
+        gy = None
+        if want_grad:
+            gy = binding.loss_terms_grad(yd, target, gcoef, skip, coeff)
+            _LossTermsFn.launches["grad"] += 1
+        ctx.save_for_backward(gy)
+        ctx.mark_non_differentiable(terms)
+        return terms[4].clone(), terms
+
+    @staticmethod
+    def backward(ctx, gl, _gterms):
+        gy, = ctx.saved_tensors
+        if gy is None:
+            raise binding.WdfHipError("Circuit.loss: this loss was evaluated without a gradient (torch.no_grad(), or nothing "
+                                      "required one)")
+        return gy * gl, None, None, None, None, None, None, None
+
+
 # The device tape interpreter keeps a sample's node values in LDS: its time grows with the square of the tape's length, torch's
 # (one launch per operation over the whole channel) linearly -- past this many operations torch runs the tape
 # (tools/ss_dyn_rows_crossover.py, profiles/r05_rows_crossover.txt: 32 operations 1.6 vs 2.2 ms per step, 48: 2.5 vs 3.3, 89: 5.5 vs 5.2, 138: 12.9 vs 7.5).
@@ -989,6 +1023,42 @@ class Circuit:
         S, E = tf.reduce_sum(tf.square(o - t)), tf.reduce_sum(tf.square(o)) + float(np.finfo(float).eps)
         n = float(o.numel())
         return S / n + tf.sqrt(S / E / n)
+
+    def loss(self, x, target, skip=0, mse=1.0, esr=1.0, esr_emph=0.0, avg=0.0, coeff=0.85, n_global=None, sums_allreduce=None):
+        """mse * mse_loss + esr * esr_loss + esr_emph * esr_with_emph + avg * avg_loss of clipper_pot.py:141-165 on this circuit's
+        output past `skip` samples (:248: the slice first, the filter second), as one fused device stage behind the forward of
+        whatever circuit this is (csrc/wdf_elementwise.h: wdf_loss_terms_sums / _coef / _grad; all sums in fp64).  With o =
+        y[skip:], t = target[skip:], n = n_global (default: the kept sample count) and eps = np.finfo(float).eps:
+            mse = sum((o-t)^2) / n            esr = sqrt(sum((o-t)^2) / (sum(o^2) + eps) / n)
+            avg = |sum(o) - sum(t)| / n       esr_emph = esr of (f(o), f(t)),  f(v)[0] = v[0], f(v)[k] = v[k] - coeff v[k-1]
+        The scripts call esr_loss(outs, train_Y) on a function declared (target, predicted), so both energies are the OUTPUT's
+        (mse_esr's convention).  Weights >= 0 and not all zero, 0 <= coeff < 1; target: [T,B] like the output.
+        One deviation from the reference: its pre_emphasis_filter works on axis 0 of whatever it is given, which in the script
+        would be the BATCH axis of [B,T',1]; the function is never called there.  Here the filter runs along TIME, which is
+        its evident purpose and what axis 0 is on this engine's [T,B] layout.
+
+        y = self(x): the gradient reaches the Variables through the reverse sweep that forward registers, fed the stage's
+        dL/dy.  Under torch.no_grad(), or when nothing requires a gradient, dL/dy is not formed and the forward keeps no
+        stash (the validation pass of clipper_pot.py:258-266).  sums_allreduce: in-place SUM all-reduce of the six float64
+        sums when the batch is sharded (wdf_hip.dist.allreduce_sum_), with n_global the sample count over all ranks.
+        `circ.last_loss_terms` is {mse, esr, esr_emph, avg} as detached device scalars, `circ.last_output` is y: the scripts'
+        history[...] lines need no second pass.  mse() and mse_esr() are untouched by this stage."""
+        weights, coeff = binding.check_loss_weights((mse, esr, esr_emph, avg), coeff)
+        if n_global is not None and not float(n_global) > 0.0:
+            raise ValueError(f"n_global must be positive, got {n_global}")
+        binding.require_gpu()
+        y = self(x)
+        yt = y.as_subclass(torch.Tensor)
+        T = int(yt.shape[0])
+        if not 0 <= int(skip) < T:
+            raise ValueError(f"skip must be in [0, {T}), got {skip}")
+        tgt = torch.as_tensor(target).as_subclass(torch.Tensor).detach().to(yt.device).float().reshape(yt.shape).contiguous()
+        n = float(n_global) if n_global is not None else float((T - int(skip)) * int(yt.shape[1]))
+        want_grad = torch.is_grad_enabled() and yt.requires_grad
+        loss, terms = _LossTermsFn.apply(yt, tgt, int(skip), weights, coeff, n, sums_allreduce, want_grad)
+        self.last_output = yt.detach()
+        self.last_loss_terms = {"mse": terms[0], "esr": terms[1], "esr_emph": terms[2], "avg": terms[3]}
+        return loss.as_subclass(tf.Tensor)
 
     def _mse_esr_nl_step(self, lin, x, target, skip):
         """mse_esr(x, target, skip) of the resident tree `lin` as ONE pass (wdf_ss_nl_step_esr) through the MSE step's autograd

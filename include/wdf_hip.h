@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -237,6 +237,32 @@ int wdf_esr_coef(const double* sums, double n, double eps, float* gcoef, float* 
  * rows before skip 0, then gcoef[0] (y - target) + gcoef[1] y; gcoef on the device (wdf_esr_coef's output). */
 int wdf_loss_esr_grad(const float* y, const float* target, const float* gcoef, int64_t B, int64_t T, int64_t skip,
                       float* gy, void* stream);
+/* The weighted loss family of clipper_pot.py:141-165 (mse_loss, esr_loss, esr_with_emph, avg_loss) as one stage after any
+ * forward, all sums in fp64 from fp32 y, target [T][B].  With o = y[skip:], t = target[skip:], n the GLOBAL sample count:
+ *   loss = w[0] S/n + w[1] sqrt(S/(E+eps)/n) + w[2] sqrt(Sp/(Ep+eps)/n) + w[3] |So - St|/n ,
+ *   S = sum (o-t)^2, E = sum o^2, So = sum o, St = sum t; Sp, Ep: S and E behind the pre-emphasis filter f(v)[0] = v[0],
+ *   f(v)[k] = v[k] - c v[k-1], 0 <= c < 1, taken along TIME inside the kept rows (slice first, filter second: :248).  The
+ *   energies are the output's, as above.  (The reference's pre_emphasis_filter works on axis 0 of what it is given, which in the
+ *   script would be the batch axis of [B,T',1]; the function is never called there.  Here the filter runs along time.)
+ *   wdf_loss_terms_sums   this rank's sums6 = {S, E, Sp, Ep, So, St} (device double; all-reduce them when the batch is sharded);
+ *                         fixed-order reduction, no atomics: the same inputs give the same bits.  ws: wdf_loss_terms_ws_bytes()
+ *                         bytes, 8-byte aligned.  16-byte loads when B % 4 == 0 and y, target are 16-byte aligned.
+ *   wdf_loss_terms_coef   sums6, n, eps, w4 (HOST pointer to the four weights {mse, esr, esr_emph, avg}: each >= 0, not all 0),
+ *                         c -> gcoef[6] = {ga, gb, al, be, gm, c} and terms[5] = {mse, esr, esr_emph, avg, loss} (device float,
+ *                         formed in fp64).  An ESR that is 0 contributes no gradient; sign(0) = 0.
+ *   wdf_loss_terms_grad   gy [T][B]: rows before skip exactly 0; on kept row k, with e = o - t, ep = f(e), op = f(o), u[T'] := 0,
+ *                         ga e[k] + gb o[k] + al (ep[k] - c ep[k+1]) + be (op[k] - c op[k+1]) + gm.  c: the same value as a
+ *                         double (gcoef[5] holds its fp32 copy): the kernel forms the differences in fp64, so that a filtered
+ *                         residual that cancels keeps its digits.  For any reverse sweep that takes dL/dy.
+ * Every argument is checked before any HIP call (null pointers, B, T <= 0, skip outside [0, T), c outside [0, 1), a negative or
+ * all-zero weight vector, n <= 0). */
+int64_t wdf_loss_terms_ws_bytes(void);
+int wdf_loss_terms_sums(const float* y, const float* target, int64_t B, int64_t T, int64_t skip, double c, void* ws,
+                        double* sums6, void* stream);
+int wdf_loss_terms_coef(const double* sums6, double n, double eps, const double* w4, double c, float* gcoef, float* terms,
+                        void* stream);
+int wdf_loss_terms_grad(const float* y, const float* target, const float* gcoef, double c, int64_t B, int64_t T, int64_t skip,
+                        float* gy, void* stream);
 int wdf_clipper_bwd_esr_tp(const float* x, const float* r, const float* theta, float fs, int n_up, int n_down,
                            const float* zstash, const float* zT, const float* target,
                            const float* gcoef, int64_t skip, void* ws, float* gtheta, float* sse,
