@@ -26,6 +26,11 @@ int dyn_check(const char* who, const float* x, const float* crow, int ns, int ni
         if (!dyn_mlp_ok(hidden, n_tanh_layers))
             return fail(WDF_EUNSUPPORTED, "%s: MLP root on a generic tree: width 4 / 8 / 16 with 3 tanh layers, 4 / 8 with 5 (got %d, %d)",
                         who, hidden, n_tanh_layers);
+    } else if (root == WDF_ROOT_ASYM_PAIR) {
+        if (!rootp) return fail(WDF_EINVAL, "%s: the two-different-diode root needs rootp = {Is_up, nVt_up, Is_down, nVt_down}", who);
+        if (ns > 4)
+            return fail(WDF_EUNSUPPORTED, "%s: the two-different-diode root runs on trees of at most four capacitors (got %d): the "
+                                          "eight-slot kernels' reverse sweep needs scratch under this root and is not built", who, ns);
     } else if (root != WDF_ROOT_NONE) {
         return fail(WDF_EINVAL, "%s: unknown root kind %d", who, root);
     }
@@ -45,8 +50,12 @@ DynKind dyn_kind(int root, int n_up, int n_down, int n_tanh_layers)
 {
     return {root, root != WDF_ROOT_DIODE_PAIR || n_up == n_down, root == WDF_ROOT_MLP && n_tanh_layers != 3 ? 5 : 3};
 }
-constexpr bool dyn_built(int root, bool sym, int nl) { return (root == wdf::kDynRootDiode || sym) && (root == wdf::kDynRootMlp || nl == 3); }
-using DynRoots = Values<int, wdf::kDynRootNone, wdf::kDynRootDiode, wdf::kDynRootMlp>;
+// (two different diodes: four state slots only -- with eight the sequential sweep spills to scratch)
+constexpr bool dyn_built(int root, bool sym, int nl, int ms = 4)
+{
+    return (root == wdf::kDynRootDiode || sym) && (root == wdf::kDynRootMlp || nl == 3) && (root != wdf::kDynRootAsym || ms == 4);
+}
+using DynRoots = Values<int, wdf::kDynRootNone, wdf::kDynRootDiode, wdf::kDynRootMlp, wdf::kDynRootAsym>;
 using DynDepths = Values<int, 3, 5>;
 using DynSlots = Values<int, 4, 8>;          // state slots the kernel is compiled for (4: trees of up to four capacitors; 8: five to eight)
 
@@ -57,7 +66,7 @@ template <class... A> bool launch_dyn_fwd(DynKind k, int ns, int64_t B, int gy, 
 {
     const dim3 grid(dyn_grid_x(k.root == WDF_ROOT_MLP, B), (unsigned)gy);
     return dispatch([&](auto ROOT, auto SYM, auto NL, auto MS) {
-        if constexpr (!dyn_built(ROOT(), SYM(), NL())) return false;
+        if constexpr (!dyn_built(ROOT(), SYM(), NL(), MS())) return false;
         else {
             hipLaunchKernelGGL((wdf::ss_dyn_fwd_kernel<ROOT(), SYM(), 16, NL(), MS()>), grid, dim3(64), 0, s, args...);
             return true;
@@ -72,12 +81,33 @@ template <int MODE, class... A> bool launch_dyn_bwd(DynKind k, int ns, int64_t B
     if (MODE == 2) k = DynKind{k.root, true, 3};
     const dim3 grid(dyn_grid_x(MODE != 2 && k.root == WDF_ROOT_MLP, B), (unsigned)gy);
     return dispatch([&](auto ROOT, auto SYM, auto NL, auto MS) {
-        if constexpr (!dyn_built(ROOT(), SYM(), NL()) || (MODE == 2 && (!SYM() || NL() != 3))) return false;
+        if constexpr (!dyn_built(ROOT(), SYM(), NL(), MS()) || (MODE == 2 && (!SYM() || NL() != 3))) return false;
         else {
             hipLaunchKernelGGL((wdf::ss_dyn_bwd_kernel<ROOT(), SYM(), 16, NL(), MODE, MS()>), grid, dim3(64), 0, s, args...);
             return true;
         }
     }, DynRoots{k.root}, Bools{k.sym}, DynDepths{k.nl}, DynSlots{ns > 4 ? 8 : 4});
+}
+
+// The reverse sweeps' workspaces by root kind: the per-(chunk, wave) root sums -- 2 doubles, 4 under two different diodes -- then
+// (chunked) the chunk maps, the entering adjoints and the root's partials of every step (5 floats, 7 under two different
+// diodes).  One walk for the *_ws_bytes functions (null base: counts only) and the entry points.
+int dyn_root_sums(int root) { return root == WDF_ROOT_ASYM_PAIR ? 4 : 2; }
+int dyn_root_rpart(int root) { return root == WDF_ROOT_ASYM_PAIR ? wdf::kDynRpartOf<wdf::kDynRootAsym> : wdf::kDynRpart; }
+bool dyn_root_known(int root) { return root == WDF_ROOT_NONE || root == WDF_ROOT_DIODE_PAIR || root == WDF_ROOT_MLP || root == WDF_ROOT_ASYM_PAIR; }
+
+struct DynBwdTpWs { double* part; float *rec, *lam_in, *rpart; size_t bytes; };
+DynBwdTpWs dyn_bwd_tp_carve(void* ws, int root, int ns, int64_t B, int64_t T, int K)
+{
+    const size_t nsa = ns > 0 ? ns : 1, waves = waves64(B);
+    Carver c(ws);
+    DynBwdTpWs w;
+    w.part = c.take<double>((size_t)K * waves * dyn_root_sums(root));
+    w.rec = c.take<float>((size_t)K * (nsa + 1) * nsa * (size_t)B);
+    w.lam_in = c.take<float>((size_t)K * nsa * (size_t)B);
+    w.rpart = c.take<float>((size_t)T * dyn_root_rpart(root) * (size_t)B);
+    w.bytes = c.off;
+    return w;
 }
 
 }  // namespace
@@ -149,6 +179,11 @@ int wdf_ss_dyn_fwd_tp(const float* x, const float* rows, int per_sample, int ns,
 
 size_t wdf_ss_dyn_bwd_ws_bytes(int64_t B) { return B > 0 ? waves64(B) * 2 * sizeof(double) : 0; }
 
+size_t wdf_ss_dyn_bwd_root_ws_bytes(int root, int64_t B)
+{
+    return (B > 0 && dyn_root_known(root)) ? waves64(B) * dyn_root_sums(root) * sizeof(double) : 0;
+}
+
 int wdf_ss_dyn_bwd(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
                    int hidden, int n_tanh_layers, int n_up, int n_down, const float* zstash, const float* gy, float* grows,
                    void* ws, float* gb, float* ain, float* lrin, float* gz0, int64_t B, int64_t T, void* stream)
@@ -177,6 +212,13 @@ size_t wdf_ss_dyn_bwd_tp_ws_bytes(int ns, int64_t B, int64_t T, int n_chunks)
            ((size_t)n_chunks * (nsa + 1) * nsa + (size_t)n_chunks * nsa + (size_t)T * wdf::kDynRpart) * (size_t)B * sizeof(float);
 }
 
+// the same by root kind (the old roots: the value above)
+size_t wdf_ss_dyn_bwd_tp_root_ws_bytes(int root, int ns, int64_t B, int64_t T, int n_chunks)
+{
+    if (ns < 0 || B <= 0 || T <= 0 || n_chunks <= 0 || !dyn_root_known(root)) return 0;
+    return dyn_bwd_tp_carve(nullptr, root, ns, B, T, n_chunks).bytes;
+}
+
 int wdf_ss_dyn_bwd_tp(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
                       int hidden, int n_tanh_layers, int n_up, int n_down, const float* zstash, const float* gy, float* grows,
                       void* ws, float* gb, float* ain, float* lrin, float* gz0, int64_t B, int64_t T, int n_chunks, void* stream)
@@ -194,10 +236,9 @@ int wdf_ss_dyn_bwd_tp(const float* x, const float* rows, int per_sample, int ns,
     const int64_t n = wdf::DynLayout(ns, ni).n;
     const int64_t cs = per_sample ? B : 1, ts = per_sample == 1 ? n * B : 0, bs = per_sample ? 1 : 0;   // (2: rows [n][B], the same row at every step)
     const size_t waves = waves64(B);
-    double* part = (double*)ws;
-    float* rec = (float*)(part + (size_t)K * waves * 2);
-    float* lam_in = rec + (size_t)K * (size_t)(ns + 1) * (size_t)ns * (size_t)B;
-    float* rpart = lam_in + (size_t)K * (size_t)ns * (size_t)B;
+    const DynBwdTpWs wsl = dyn_bwd_tp_carve(ws, root, ns, B, T, K);
+    double* part = wsl.part;
+    float *rec = wsl.rec, *lam_in = wsl.lam_in, *rpart = wsl.rpart;
     hipStream_t s = (hipStream_t)stream;
     const int acc = per_sample != 1;       // (grows [K][n][B] then: one partial per chunk, added up by the caller)
     const DynKind kind = dyn_kind(root, n_up, n_down, n_tanh_layers);

@@ -22,6 +22,16 @@
 // with per-sample rows the chain rule to the component values runs per sample too (wdf_ss_dyn_rows_bwd runs the tape
 // backwards over it); diode root: the lane sums of gb D_L, gb D_V (-> dL/dIs, dL/dnVt) and dL/dR_port = gb D_L / R_port in the row;
 // MLP root: gb = dL/db, a and log R_port per sample for the weight-gradient pass, dL/dR_port = gb (-dMLP/dlr) / R_port.
+//
+// Fourth root kind, kDynRootAsym (MS = 4 only): two DIFFERENT diodes, the exact Shockley pair solved by Newton in fp32
+// (wdf_asym.h asym_newton32_solve, the static kernels' kSsAsymTol / kSsAsymMaxIter) with R_port from the row -- a pot that
+// moves under tf_wdf.AsymDiodePair.  rootp = {Is_up, nVt_up, Is_down, nVt_down}; one lane per sequence.  The reverse sweep
+// re-solves the root from the stash (the same a bit for bit, so the same b), differentiates it with asym_newton_partials
+// (partials with respect to the VALUES: dL/dR_port = gb cf[4], no division by R_port) and keeps four lane sums gb cf[0..3]
+// -> ws [chunk][wave][4]; MODE 1 leaves seven floats per step for MODE 2 (kDynRpartOf).
+// The solve's stop rule is a WAVEFRONT BALLOT: every lane of a wave has to reach every solve together.  These kernels clamp
+// dead lanes to B - 1 and leave per WAVE only (the gate), and every solve stands outside the `if (writer)` / `if (live)` /
+// `if (owned)` blocks -- keep it so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,7 +42,7 @@
 
 namespace wdf {
 
-enum { kDynRootNone = 0, kDynRootDiode = 2, kDynRootMlp = 3 };
+enum { kDynRootNone = 0, kDynRootDiode = 2, kDynRootMlp = 3, kDynRootAsym = 4 };
 
 // Who is who in a wave.  Ideal-source / diode roots: one lane per sequence.  MLP root: one 16-lane DPP ROW per sequence
 // (wdf_mlp_row.h: lane j = hidden neuron j, the layer's matrix-vector product as 16 v_fmac_f32_dpp, weights in registers) --
@@ -104,6 +114,23 @@ struct DynRoot {
         }
     }
 };
+//   two different diodes: rootp = {Is_up, nVt_up, Is_down, nVt_down}; port(R_port) sets Rp and the two logarithms the closed
+//   form's start value reads -- once ahead of the time loop when the rows do not change in time, every step otherwise
+template <bool SYM, int H, int NL>
+struct DynRoot<kDynRootAsym, SYM, H, NL> {
+    AsymConsts c;
+    __device__ __forceinline__ void load(const float* __restrict__ rootp, int, int)
+    {
+        c.Is1 = rootp[0]; c.V1 = rootp[1]; c.Is2 = rootp[2]; c.V2 = rootp[3];
+        c.p = 0.0f; c.Rp = 1.0f; c.l1 = 0.0f; c.l2 = 0.0f;
+    }
+    __device__ __forceinline__ void port(float rp)
+    {
+        c.Rp = rp;
+        c.l1 = logf(rp * c.Is1 / c.V1);
+        c.l2 = logf(rp * c.Is2 / c.V2);
+    }
+};
 
 // x [B][T][ni] -> y [T][B]; w_in: flat MLP weights (MLP root) -- H, NL are ignored for the other roots
 template <int ROOT, bool SYM, int H, int NL, int MS = 4>
@@ -146,6 +173,7 @@ __global__ __launch_bounds__(64) void ss_dyn_fwd_kernel(const float* __restrict_
     [[maybe_unused]] float lroot = 0.0f;
     if constexpr (ROOT == kDynRootDiode) lroot = logf(c.rp * root.Is / root.V);
     if constexpr (ROOT == kDynRootMlp) lroot = logf(c.rp);
+    if constexpr (ROOT == kDynRootAsym) root.port(c.rp);
     for (int64_t t = tw; t < t1; ++t) {
         const bool owned = t >= t0;                                // wave-uniform
         if (t == t0 && zwarm != nullptr && writer) {
@@ -157,6 +185,7 @@ __global__ __launch_bounds__(64) void ss_dyn_fwd_kernel(const float* __restrict_
             c = dyn_load_row<MS>(cp + t * ts, cs, L, ns, ni);
             if constexpr (ROOT == kDynRootDiode) lroot = logf(c.rp * root.Is / root.V);
             if constexpr (ROOT == kDynRootMlp) lroot = logf(c.rp);
+            if constexpr (ROOT == kDynRootAsym) root.port(c.rp);
         }
         float xv[kDynMaxI];
 #pragma unroll
@@ -169,6 +198,10 @@ __global__ __launch_bounds__(64) void ss_dyn_fwd_kernel(const float* __restrict_
         float broot = 0.0f;
         if constexpr (ROOT == kDynRootDiode) broot = diode_pair<SYM>(a, lroot, root.d).b;
         if constexpr (ROOT == kDynRootMlp) broot = -row_mlp_fwd<NL>(RW, a, lroot, act);
+        if constexpr (ROOT == kDynRootAsym) {                      // (every lane of the wave: the stop rule is a ballot)
+            int iters = 0;
+            broot = asym_newton32_root(root.c, a, kSsAsymTol, kSsAsymMaxIter, iters);
+        }
         float yv = c.fy * broot;
 #pragma unroll
         for (int s = 0; s < MS; ++s) yv = fmaf(c.cy[s], z[s], yv);
@@ -207,19 +240,21 @@ __global__ __launch_bounds__(64) void ss_dyn_fwd_kernel(const float* __restrict_
     }
 }
 
-// grow [T][kN1][B]; ws: double[gridDim.y gridDim.x][2] = the (chunk, wave)'s {sum gb D_L, sum gb D_V} (diode root);
+// grow [T][kN1][B]; ws: double[gridDim.y gridDim.x][2] = the (chunk, wave)'s {sum gb D_L, sum gb D_V} (diode root;
+// two different diodes: [4] = sum gb d b / d{Is_up, nVt_up, Is_down, nVt_down});
 // gbroot / ain / lrin [T][B] (MLP root): dL/db, a, log R_port of every step for mlp_wgrad_list_kernel.
 //
 // Time chunks (round 5, wdf_ss_dyn_bwd_tp) -- EXACT: the adjoint recurrence is linear in the adjoint entering a chunk from the
 // future, so the sweep runs in three launches over grid (waves, K):
 //   MODE 1  evaluates the root's partials of every step ONCE (the expensive part: omega / the network and its input gradient),
-//           leaves them in rpart [T][5][B] = {Da, b, d b/d R_port, D_L, D_V} (and a, log R_port for the network's weight
-//           gradient), and carries the chunk's adjoint map: lam leaving the chunk = Phi lam entering + beta (ns homogeneous runs
+//           leaves them in rpart [T][5][B] = {Da, b, d b/d R_port, D_L, D_V} (two different diodes: [T][7][B] = {Da, b,
+//           d b/d R_port, cf0..cf3}; and a, log R_port for the network's weight gradient), and carries the chunk's adjoint map: lam leaving the chunk = Phi lam entering + beta (ns homogeneous runs
 //           and the particular one) -> rec [K][(ns + 1) ns][B];
 //   ss_dyn_bwd_combine_kernel walks a sequence's K maps last to first -> the adjoint entering every chunk, lam_in [K][ns][B];
 //   MODE 2  re-walks every chunk from its true entering adjoint reading rpart -- no root evaluation -- and emits what MODE 0 emits.
 // MODE 0 (K = 1) is the sequential sweep: root evaluated and rows emitted in one walk.
 constexpr int kDynRpart = 5;
+template <int ROOT> constexpr int kDynRpartOf = ROOT == kDynRootAsym ? 7 : kDynRpart;
 
 template <int ROOT, bool SYM, int H, int NL, int MODE, int MS = 4>
 __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict__ x, const float* __restrict__ crow, int64_t cs,
@@ -264,6 +299,7 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
             for (int s = 0; s < MS; ++s) hom[j][s] = (j == s && j < ns) ? 1.0f : 0.0f;
     }
     double sL = 0.0, sV = 0.0;
+    [[maybe_unused]] double sA[4] = {0.0, 0.0, 0.0, 0.0};          // two different diodes: sum gb cf[0..3]
     // accumulators of the acc mode at compile-time slots: A s MS + s2 | Bx | E | ca | da | cy | dy | fy | R_port
     constexpr int gA = 0, gB = MS * MS, gE = gB + 2 * MS, gCa = gE + MS, gDa = gCa + MS, gCy = gDa + 2, gDy = gCy + MS, gFy = gDy + 2,
                   gRp = gFy + 1, gN = gRp + 1;
@@ -277,11 +313,13 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
     [[maybe_unused]] float lroot = 0.0f;
     if constexpr (ROOT == kDynRootDiode && MODE != 2) lroot = logf(c.rp * root.Is / root.V);
     if constexpr (kEval) lroot = logf(c.rp);
+    if constexpr (ROOT == kDynRootAsym && MODE != 2) root.port(c.rp);
     for (int64_t t = t1 - 1; t >= t0; --t) {
         if (ts != 0 && t != t1 - 1) {                              // wave-uniform
             c = dyn_load_row<MS>(cp + t * ts, cs, L, ns, ni);
             if constexpr (ROOT == kDynRootDiode && MODE != 2) lroot = logf(c.rp * root.Is / root.V);
             if constexpr (kEval) lroot = logf(c.rp);
+            if constexpr (ROOT == kDynRootAsym && MODE != 2) root.port(c.rp);
         }
         float xv[kDynMaxI], z[MS];
 #pragma unroll
@@ -296,11 +334,16 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
         for (int i = 0; i < kDynMaxI; ++i) a = fmaf(c.da[i], xv[i], a);
         float broot = 0.0f, Da = 0.0f, Drp = 0.0f;                 // d b / d a, d b / d R_port
         [[maybe_unused]] float DL = 0.0f, DV = 0.0f, lr = 0.0f;
+        [[maybe_unused]] float cf[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (MODE == 2) {
             if constexpr (ROOT != kDynRootNone) {
-                const float* __restrict__ rp_ = rpart + (t * kDynRpart) * B + b;
+                const float* __restrict__ rp_ = rpart + (t * kDynRpartOf<ROOT>) * B + b;
                 Da = rp_[0]; broot = rp_[B]; Drp = rp_[2 * B];
                 if constexpr (ROOT == kDynRootDiode) { DL = rp_[3 * B]; DV = rp_[4 * B]; }
+                if constexpr (ROOT == kDynRootAsym) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) cf[i] = rp_[(3 + i) * B];
+                }
             }
         } else
         if constexpr (ROOT == kDynRootDiode) {
@@ -312,6 +355,13 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
             DL = -root.d.two_v * o.lam * (o.m0 * w0p - o.m1 * w1p);
             DV = fmaf(2.0f * l2 * a, sp * fast_rcp(root.V), -2.0f * o.lam * (o.m0 * o.w0 - o.m1 * o.w1));
             Drp = DL / c.rp;                                        // L = log(R_port Is / nVt)
+        }
+        if constexpr (ROOT == kDynRootAsym && MODE != 2) {        // (every lane of the wave: the stop rule is a ballot)
+            int iters = 0;
+            float v, e1, e2;
+            broot = asym_newton32_solve(root.c, a, kSsAsymTol, kSsAsymMaxIter, iters, v, e1, e2);
+            asym_newton_partials(root.c, v, e1, e2, Da, cf);
+            Drp = cf[4];                                            // with respect to R_port itself
         }
         if constexpr (kEval) {
             lr = lroot;
@@ -329,8 +379,14 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
             // what MODE 2 needs of this step's root, and the network's operands; then the adjoint maps -- no rows
             if constexpr (ROOT != kDynRootNone) {
                 if (writer) {
-                    float* __restrict__ rp_ = rpart + (t * kDynRpart) * B + b;
-                    rp_[0] = Da; rp_[B] = broot; rp_[2 * B] = Drp; rp_[3 * B] = DL; rp_[4 * B] = DV;
+                    float* __restrict__ rp_ = rpart + (t * kDynRpartOf<ROOT>) * B + b;
+                    rp_[0] = Da; rp_[B] = broot; rp_[2 * B] = Drp;
+                    if constexpr (ROOT == kDynRootAsym) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) rp_[(3 + i) * B] = cf[i];
+                    } else {
+                        rp_[3 * B] = DL; rp_[4 * B] = DV;
+                    }
                 }
             }
             if constexpr (ROOT == kDynRootMlp) {
@@ -407,6 +463,10 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
             sL += (double)(gb * DL);
             sV += (double)(gb * DV);
         }
+        if constexpr (ROOT == kDynRootAsym) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sA[i] += (double)(gb * cf[i]);
+        }
         if constexpr (ROOT == kDynRootMlp) {
             gbroot[t * B + b] = gb;
             if constexpr (MODE == 0) {
@@ -481,6 +541,13 @@ __global__ __launch_bounds__(64) void ss_dyn_bwd_kernel(const float* __restrict_
             const int64_t slot = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
             ws[slot * 2 + 0] = sL;
             ws[slot * 2 + 1] = sV;
+        }
+    }
+    if constexpr (ROOT == kDynRootAsym) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double v = wave_sum(live ? sA[i] : 0.0);
+            if (threadIdx.x == 0 && ws) ws[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + i] = v;
         }
     }
 }

@@ -287,14 +287,25 @@ class AsymDiodePair(_Element):
     forward.  Trees of one or two capacitors also have a one-pass training step there (csrc/wdf_ss_asym_step.h: forward, loss
     and every gradient in one sweep, Circuit._asym_tree_step; mse / mse_esr take it for a loss once tools/ss_asym_step_bench.py
     has shown it faster than composing: lowering.ASYM_TREE_STEP_SERVES).  The clipper tree probed at its capacitor keeps its own kernels and one-pass steps.  On the generic kernels the
-    root takes solver="newton_f32" only and no per_sample_R / per_sequence_R; to_device() stays unsupported.'''
+    root takes solver="newton_f32" only and no per_sample_R / per_sequence_R; to_device() stays unsupported.
+
+    streamed=True (default False: every refusal above stays) runs the root on the streamed-coefficient kernels
+    (csrc/wdf_ss_dyn.h, root kind WDF_ROOT_ASYM_PAIR with R_port taken from the step's coefficient row) on ANY tree of at most
+    four capacitors and two sources, any probe, the clipper tree included.  That adds what the other two ways refuse: a
+    resistance that MOVES -- Circuit(..., per_sample_R=elem) for any Resistor / ResistiveVoltageSource of the tree, input
+    [B,T,ni+1], the reference's set_resistance + calc_impedance every step (clipper_pot.py:116-117); a channel that is constant
+    along every sequence is noticed and lowered to one row per sequence by itself, so per_sequence_R is refused there -- and a
+    fourth capacitor (a tree without a pot runs with one static row).  Forward in verified time chunks with warm starts, exact
+    chunked reverse sweep; gradients reach the four diode Variables and every component but the pot's.  solver="newton_f32"
+    only; mse / mse_esr / loss compose from the forward (no one-pass step under a pot); to_device() stays unsupported.'''
 
     SOLVERS = {"omega_f32": 0, "newton_f64": 1, "newton_f32": 2}          # wdf_hip.binding.ASYM_*
 
     def __init__(self, next, Is_up, Is_down, Vt=25.85e-3, nDiodes_up=1.0, nDiodes_down=1.0, trainable=False,  # noqa: A002
-                 solver="newton_f32", any_tree=False):
+                 solver="newton_f32", any_tree=False, streamed=False):
         super().__init__()
         self.any_tree = bool(any_tree)
+        self.streamed = bool(streamed)
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {sorted(self.SOLVERS)}, got {solver!r}")
         self.next = next
@@ -314,7 +325,7 @@ class AsymDiodePair(_Element):
     def reflected(self):
         raise _lowering.binding.WdfHipError(
             "AsymDiodePair has no element-wise reflected(): run it as the root of tf_wdf.Circuit on the diode-clipper tree "
-            "(Parallel(ResistiveVoltageSource, Capacitor), probe = the capacitor), or with any_tree=True on any small tree")
+            "(Parallel(ResistiveVoltageSource, Capacitor), probe = the capacitor), or with any_tree=True / streamed=True on any small tree")
 
 
 # ---- fast tier ------------------------------------------------------------------------------

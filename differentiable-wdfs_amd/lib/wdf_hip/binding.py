@@ -150,6 +150,10 @@ def lib():
     L.wdf_ss_dyn_fwd.argtypes = [fp, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, vp]
     L.wdf_ss_dyn_bwd_ws_bytes.restype = C.c_size_t
     L.wdf_ss_dyn_bwd_ws_bytes.argtypes = [i64]
+    L.wdf_ss_dyn_bwd_root_ws_bytes.restype = C.c_size_t
+    L.wdf_ss_dyn_bwd_root_ws_bytes.argtypes = [ci, i64]
+    L.wdf_ss_dyn_bwd_tp_root_ws_bytes.restype = C.c_size_t
+    L.wdf_ss_dyn_bwd_tp_root_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
     L.wdf_ss_dyn_bwd.restype = ci
     L.wdf_ss_dyn_bwd.argtypes = [fp, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, vp, fp, fp, fp, fp, i64, i64, vp]
     L.wdf_ss_dyn_fwd_tp_ws_bytes.restype = C.c_size_t
@@ -342,6 +346,7 @@ EXPORTED_SYMBOLS = (
     "wdf_clipper_asym_step_mse_rseq", "wdf_clipper_asym_step_esr_rseq",
     "wdf_ss_dyn_row_len", "wdf_ss_dyn_fwd", "wdf_ss_dyn_bwd_ws_bytes", "wdf_ss_dyn_bwd", "wdf_clipper_mlp_wgrad_matrix_core_chunks",
     "wdf_ss_dyn_fwd_tp_ws_bytes", "wdf_ss_dyn_fwd_tp", "wdf_ss_dyn_bwd_tp_ws_bytes", "wdf_ss_dyn_bwd_tp",
+    "wdf_ss_dyn_bwd_root_ws_bytes", "wdf_ss_dyn_bwd_tp_root_ws_bytes",
     "wdf_ss_dyn_rows", "wdf_ss_dyn_rows_bwd_ws_bytes", "wdf_ss_dyn_rows_bwd",
     "wdf_mlp_weight_count", "wdf_clipper_mlp_fwd", "wdf_clipper_mlp_bwd", "wdf_clipper_mlp_bwd_ws_bytes",
     "wdf_clipper_mlp_bwd_w_ws_bytes", "wdf_clipper_mlp_bwd_w",
@@ -1421,6 +1426,7 @@ def asym_root(a, theta6, fs, mode, tol=1e-12, max_iter=50):
 
 ROOT_NONE, ROOT_DIODE_PAIR, ROOT_MLP = 0, 2, 3
 ROOT_ASYM_PAIR = 4        # two different diodes, exact, fp32 Newton: ss_fwd / ss_bwd / ss_fwd_tp / ss_bwd_tp; rootp [5], groot [5]
+#                           (ss_dyn_*: rootp [4] = {Is_up, nVt_up, Is_down, nVt_down}, groot float64 [4], R_port in the row)
 
 
 def _ss_groot(root_kind, device):
@@ -1659,8 +1665,8 @@ def ss_dyn_fwd(x, rows, ns, ni, root_kind=ROOT_NONE, rootp=None, w=None, hidden=
 def ss_dyn_bwd(x, rows, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, w=None, hidden=0, n_tanh=0, n_up=1, n_down=1, want_gz0=False):
     """Reverse sweep of ss_dyn_fwd for dL/dy = gy [T,B] (wdf_ss_dyn_bwd).
     -> grows [T,n,B] (dL/d row entry of every sample; rows constant in time -- [n] or [1,n,B] -- : [1,n,B], summed over the steps by
-    the kernel), groot (diode: float64 [2] = dL/d{Is, nVt}; MLP: the flat weight gradient;
-    else None), gz0 [ns,B] | None."""
+    the kernel), groot (diode: float64 [2] = dL/d{Is, nVt}; two different diodes: float64 [4] = dL/d{Is_up, nVt_up, Is_down,
+    nVt_down}, the sum over the waves with no chain rule; MLP: the flat weight gradient; else None), gz0 [ns,B] | None."""
     require_gpu()
     x, rows, rootp, w = _f32_dev(x, "x"), _f32_dev(rows, "rows"), _f32_dev(rootp, "rootp"), _f32_dev(w, "w")
     zstash, gy = _f32_dev(zstash, "zstash"), _f32_dev(gy, "gy")
@@ -1670,7 +1676,10 @@ def ss_dyn_bwd(x, rows, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, w=N
     dev = x.device
     # per sample: dL/d(row) of every sample [T,n,B]; rows constant in time: the kernel's own sum over the steps [1,n,B]
     grows = torch.empty((T if per == 1 else 1, n, B), dtype=torch.float32, device=dev)
-    ws = torch.zeros(((B + 63) // 64, 2), dtype=torch.float64, device=dev)
+    nsum = lib().wdf_ss_dyn_bwd_root_ws_bytes(int(root_kind), B) // (8 * ((B + 63) // 64))
+    if nsum == 0:
+        raise WdfHipError(f"ss_dyn_bwd: unknown root kind {root_kind}")
+    ws = torch.zeros(((B + 63) // 64, nsum), dtype=torch.float64, device=dev)
     mlp = root_kind == ROOT_MLP
     gb, ain, lrin = (torch.empty((T, B), dtype=torch.float32, device=dev) for _ in range(3)) if mlp else (None, None, None)
     gz0 = torch.empty((max(ns, 1), B), dtype=torch.float32, device=dev) if want_gz0 else None
@@ -1683,6 +1692,8 @@ def ss_dyn_bwd(x, rows, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, w=N
         s = ws.sum(dim=0)
         rp = rootp.double()
         groot = torch.stack([s[0] / rp[0], s[1] - s[0] / rp[1]])
+    elif root_kind == ROOT_ASYM_PAIR:
+        groot = ws.sum(dim=0)
     elif mlp:
         groot = clipper_mlp_wgrad(ain.reshape(-1), lrin.reshape(-1), gb.reshape(-1), None, w, hidden, n_tanh, 1.0)
     return grows, groot, gz0
@@ -1794,7 +1805,10 @@ def ss_dyn_bwd_tp(x, rows, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, ro
     K = dyn_chunks(T, n_chunks)
     # per sample: [T,n,B]; rows constant in time: one partial per chunk [K,n,B], added up below
     grows = torch.empty((T if per == 1 else K, n, B), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib().wdf_ss_dyn_bwd_tp_ws_bytes(int(ns), B, T, K),), dtype=torch.uint8, device=dev)
+    nws = lib().wdf_ss_dyn_bwd_tp_root_ws_bytes(int(root_kind), int(ns), B, T, K)
+    if nws == 0:
+        raise WdfHipError(f"ss_dyn_bwd_tp: no workspace for root kind {root_kind}, ns={ns}, B={B}, T={T}, {K} chunks")
+    ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
     mlp = root_kind == ROOT_MLP
     gb, ain, lrin = (torch.empty((T, B), dtype=torch.float32, device=dev) for _ in range(3)) if mlp else (None, None, None)
     gz0 = torch.empty((ns, B), dtype=torch.float32, device=dev) if want_gz0 else None
@@ -1808,6 +1822,9 @@ def ss_dyn_bwd_tp(x, rows, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, ro
         s = ws[:nparts * 16].view(torch.float64).reshape(nparts, 2).sum(dim=0)
         rp = rootp.double()
         groot = torch.stack([s[0] / rp[0], s[1] - s[0] / rp[1]])
+    elif root_kind == ROOT_ASYM_PAIR:
+        nparts = K * ((B + 63) // 64)
+        groot = ws[:nparts * 32].view(torch.float64).reshape(nparts, 4).sum(dim=0)
     elif mlp:
         groot = clipper_mlp_wgrad(ain.reshape(-1), lrin.reshape(-1), gb.reshape(-1), None, w, hidden, n_tanh, 1.0)
     if per != 1:

@@ -293,7 +293,7 @@ class _DynRowsFn(torch.autograd.Function):
 class _SsDynFn(torch.autograd.Function):
     """y [T,B] = the state-space recursion with streamed coefficient rows and / or the MLP root (csrc/wdf_ss_dyn.h).
     rows: [T,n,B] (per-sample impedance) or [n] (static), n = A | Bx | E | ca | da | cy | dy | fy | R_port.
-    rootvec: {Is, nVt} (diode root), the flat weights (MLP root) or None.  The reverse sweep hands back dL/d(row entry) for
+    rootvec: {Is, nVt} (diode root), {Is_up, nVt_up, Is_down, nVt_down} (two different diodes), the flat weights (MLP root) or None.  The reverse sweep hands back dL/d(row entry) for
     every sample; torch chains it through the rows' own graph (the probe tape evaluated over the resistance channel) to the
     component values -- calc_impedance's chain rule per sample (tf_wdf.py:114-115,139-145,168-177)."""
 
@@ -307,7 +307,7 @@ class _SsDynFn(torch.autograd.Function):
         r = rows.detach().float().contiguous()
         rv = None if rootvec is None else rootvec.detach().float().contiguous()
         z0d = None if z0 is None else z0.detach().float().contiguous()
-        rootp, w = (rv, None) if kind == binding.ROOT_DIODE_PAIR else (None, rv)
+        rootp, w = (rv, None) if kind in (binding.ROOT_DIODE_PAIR, binding.ROOT_ASYM_PAIR) else (None, rv)
         if tp is not None and tp.k_fwd >= 2 and ns >= 1:       # verified time chunks; the waves that missed re-run sequentially
             y, zs, zT, st = binding.ss_dyn_fwd_tp(x, r, ns, ni, tp.k_fwd, tp.warmup, tp.tol, kind, rootp=rootp, w=w, hidden=hidden,
                                                   n_tanh=n_tanh, n_up=n_up, n_down=n_down, want_stash=need, z0=z0d, want_zT=want_zT,
@@ -332,7 +332,7 @@ class _SsDynFn(torch.autograd.Function):
     def backward(ctx, gy, _gzT):
         ns, ni, kind, hidden, n_tanh, n_up, n_down, has_z0, per_sample = ctx.cfg
         r, rv, x, zs = ctx.saved_tensors
-        rootp, w = (rv, None) if kind == binding.ROOT_DIODE_PAIR else (None, rv)
+        rootp, w = (rv, None) if kind in (binding.ROOT_DIODE_PAIR, binding.ROOT_ASYM_PAIR) else (None, rv)
         if zs is None:
             zs = torch.zeros((x.shape[1], 1, x.shape[0]), dtype=torch.float32, device=x.device)      # (ns = 0: nothing to read)
         tp = ctx.tp
@@ -769,7 +769,11 @@ class Circuit:
     every step, gradients flow to the four diode Variables and, through the port resistance and the step's matrices, to the
     components; mse / mse_esr compose the loss from the forward there, and trees of one or two capacitors have a one-pass step
     (csrc/wdf_ss_asym_step.h: _asym_tree_step; ASYM_TREE_STEP_SERVES says for which loss mse / mse_esr take it).  Off the clipper's own kernels the root takes
-    solver="newton_f32" only, no per_sample_R / per_sequence_R and no to_device().
+    solver="newton_f32" only, no per_sample_R / per_sequence_R and no to_device().  Built with streamed=True the root runs on
+    the streamed-coefficient kernels instead (csrc/wdf_ss_dyn.h) on any tree of at most four capacitors and two sources:
+    per_sample_R on any Resistor / ResistiveVoltageSource (a channel constant along every sequence is lowered to one row per
+    sequence by itself; per_sequence_R is refused), one static row without a pot; newton_f32 only, losses composed from the
+    forward, no to_device().
 
     Input channels: channel k of x feeds the k-th voltage source found walking the tree in
     post-order (ResistiveVoltageSource leaves), then the ideal-source root if there is one.
@@ -805,19 +809,35 @@ class Circuit:
         if self.ni < 1:
             raise ValueError("the circuit has no voltage source")
         asym = self.root_kind == "AsymDiodePair"
-        own = self._is_clipper() and not self.force_generic       # the two-different-diode clipper's own kernels (csrc/wdf_asym.h)
-        if asym and not getattr(root, "any_tree", False) and not (own and per_sample_R is None):
+        # AsymDiodePair(streamed=True): the streamed-coefficient kernels (csrc/wdf_ss_dyn.h, root kind ROOT_ASYM_PAIR) on any
+        # tree, the clipper's included -- a pot that moves (per_sample_R on any Resistor / ResistiveVoltageSource), a fourth capacitor
+        streamed = asym and bool(getattr(root, "streamed", False))
+        own = self._is_clipper() and not self.force_generic and not streamed   # the two-different-diode clipper's own kernels (csrc/wdf_asym.h)
+        if streamed:
+            if root.mode != binding.ASYM_NEWTON_F32:
+                raise binding.WdfHipError("AsymDiodePair(streamed=True) takes solver='newton_f32' only "
+                                          f"(got {root.solver!r}): the streamed-coefficient kernels solve the pair in fp32")
+            if per_sequence_R is not None:
+                raise binding.WdfHipError("per_sequence_R is not taken under AsymDiodePair(streamed=True): pass the pot as "
+                                          "per_sample_R -- a channel that is constant along every sequence is noticed and "
+                                          "lowered to one coefficient row per sequence by itself")
+            if self.ns > 4 or self.ni > 2:
+                raise binding.WdfHipError("AsymDiodePair(streamed=True) runs on trees of at most four capacitors and two sources "
+                                          f"(this one has {self.ns} and {self.ni}): the eight-slot streamed kernels' reverse "
+                                          "sweep needs scratch under this root and is not built")
+        if asym and not streamed and not getattr(root, "any_tree", False) and not (own and per_sample_R is None):
             raise binding.WdfHipError("an AsymDiodePair root runs on the diode-clipper tree only: top = Parallel(ResistiveVoltageSource, "
                                       "Capacitor), probe = the capacitor, no per_sample_R (a pot that is constant along every "
                                       "sequence goes in as per_sequence_R), not force_generic (csrc/wdf_asym.h); "
                                       "AsymDiodePair(..., any_tree=True) takes the generic state-space kernels on any small tree")
         # AsymDiodePair(any_tree=True) off the clipper's own kernels: the generic state-space kernels, root kind ROOT_ASYM_PAIR
         self._asym_generic = asym and not own
-        if asym and per_sample_R is not None:
+        self._asym_streamed = streamed
+        if asym and per_sample_R is not None and not streamed:
             raise binding.WdfHipError("per_sample_R is not supported under an AsymDiodePair root: the root's kernels take static "
                                       "coefficients (a pot that is constant along every sequence goes in as per_sequence_R on "
                                       "the diode-clipper tree)")
-        if self._asym_generic:
+        if self._asym_generic and not streamed:
             if root.mode != binding.ASYM_NEWTON_F32:
                 raise binding.WdfHipError("an AsymDiodePair root on the generic state-space kernels takes solver='newton_f32' only "
                                           f"(got {root.solver!r}): the fp64 Newton mode and the omega closed form run on the "
@@ -846,7 +866,7 @@ class Circuit:
         # (csrc/wdf_ss_dyn.h) -- and so does, since round 6, ANY tree of five to eight capacitors (the static-coefficient kernels
         # of csrc/wdf_statespace.h are compiled for at most four: a larger tree hands the streamed kernels one static row)
         self._dyn = ((per_sample_R is not None or self.root_kind == "DenseRootModel") and (self.force_generic or not self._is_clipper())) \
-            or self.ns > 4
+            or self.ns > 4 or streamed                            # (a streamed two-diode root without a pot: one static row)
         if self._dyn and (self.ns > 8 or self.ni > 2):
             raise binding.WdfHipError("trees of at most eight capacitors and two sources run on the GPU kernels "
                                       f"(this one has {self.ns} and {self.ni})")
@@ -1079,6 +1099,8 @@ class Circuit:
         (kind="mse_esr") on this circuit: an AsymDiodePair(any_tree=True) root on the generic state-space kernels, a tree the
         step is built for under this loss (one or two capacitors, one or two sources), tensors in, 0 <= skip < T."""
         if not getattr(self, "_asym_generic", False) or kind not in ("mse", "mse_esr"):
+            return False
+        if getattr(self, "_asym_streamed", False):                # (the streamed-coefficient kernels have no one-pass step)
             return False
         if not (isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)):
             return False
@@ -1425,6 +1447,12 @@ class Circuit:
             rootvec = torch.stack([dp.Is.as_subclass(torch.Tensor).double().reshape(()),
                                    dp.nVt.as_subclass(torch.Tensor).double().reshape(())]).to(device=dev, dtype=torch.float32)
             kind, n_up, n_down = binding.ROOT_DIODE_PAIR, dp.N_up, dp.N_down
+        elif self.root_kind == "AsymDiodePair":
+            # two different diodes (streamed=True): the four diode Variables; the port resistance is the row's last entry
+            dp = self.root
+            rootvec = torch.stack([v.as_subclass(torch.Tensor).double().reshape(()) for v in
+                                   (dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down)]).to(device=dev, dtype=torch.float32)
+            kind = binding.ROOT_ASYM_PAIR
         elif self.root_kind == "DenseRootModel":
             from . import mlp_root
             dense, hidden, n_tanh, act = mlp_root.describe(self.root, with_activation=True)
@@ -1492,7 +1520,7 @@ class Circuit:
                                                       [math.log(max(float(c[-1]), 1e-30))], a_max)
                     slopes = tuple(np.linspace(s_lo, s_hi, 5))          # (the radius need not peak at an end of the range)
                 else:
-                    slopes = (1.0, -1.0)
+                    slopes = (1.0, -1.0)                                # (two different diodes too: Da = 2/F - 1, F >= 1)
                 rho = max(rho, max(float(np.max(np.abs(np.linalg.eigvals(A + sgn * np.outer(E, ca))))) for sgn in slopes))
         k_fwd, W = 1, 0
         if rho < 1.0 - 1e-9:

@@ -485,7 +485,8 @@ int wdf_clipper_mlp_step(const float* x, const float* p, const float* lr, const 
  * five sums; the *_ws_bytes functions take no root and size for it whatever the root (the other roots use kN + 2 of a row).
  * ---------------------------------------------------------------------------------- */
 enum { WDF_ROOT_NONE = 0, WDF_ROOT_DIODE_PAIR = 2, WDF_ROOT_MLP = 3 /* wdf_ss_dyn_* only */,
-       WDF_ROOT_ASYM_PAIR = 4 /* wdf_ss_fwd / _bwd / _fwd_tp_root / _bwd_tp only */ };
+       WDF_ROOT_ASYM_PAIR = 4 /* wdf_ss_fwd / _bwd / _fwd_tp_root / _bwd_tp (rootp float[5]) and wdf_ss_dyn_fwd / _fwd_tp / _bwd /
+                                 _bwd_tp (rootp float[4], ns <= 4: R_port comes from the row) */ };
 
 int wdf_ss_ncoef(int ns, int ni);
 int wdf_ss_fwd(const float* x, const float* coef, const float* rootp,
@@ -572,8 +573,15 @@ int wdf_ss_asym_step_esr(const float* x, const float* coef, const float* rootp, 
  *            resistance down the channel): calc_impedance's result does not change along the sequence;
  *            n = wdf_ss_dyn_row_len(ns, ni) =
  *            wdf_ss_ncoef(ns, ni) + 1:  A | Bx | E | ca | da | cy | dy | fy | R_port   (the coef layout above, then the port resistance)
- * root       WDF_ROOT_NONE, WDF_ROOT_DIODE_PAIR (rootp = device float[2] {Is, nVt}; R_port comes from the row) or WDF_ROOT_MLP
- *            (w: flat weights, hidden in {4, 8, 16} with 3 tanh layers, {4, 8} with 5; tanh only)
+ * root       WDF_ROOT_NONE, WDF_ROOT_DIODE_PAIR (rootp = device float[2] {Is, nVt}; R_port comes from the row), WDF_ROOT_MLP
+ *            (w: flat weights, hidden in {4, 8, 16} with 3 tanh layers, {4, 8} with 5; tanh only) or WDF_ROOT_ASYM_PAIR (two
+ *            different diodes, the exact Shockley pair solved by Newton in fp32 at every step as under wdf_ss_fwd: rootp = device
+ *            float[4] {Is_up, nVt_up, Is_down, nVt_down}, R_port from the row; ns <= 4 -- WDF_EUNSUPPORTED above: the eight-slot
+ *            reverse sweep would need scratch under this root; n_up / n_down are ignored).  Its reverse sweeps size their
+ *            workspaces with the root-aware wdf_ss_dyn_bwd_root_ws_bytes / wdf_ss_dyn_bwd_tp_root_ws_bytes (which return the
+ *            plain functions' values for the other roots): per wave double [4] = sum gb d b / d{Is_up, nVt_up, Is_down,
+ *            nVt_down} -- dL/d(those values) after the sum over waves, no chain rule left -- and seven floats per step
+ *            instead of five between the chunked sweep's two walks.
  * x [B][T][ni]; y, gy [T][B]; zstash [T][ns][B]; z0 / zT / gz0 [ns][B] (optional).
  * wdf_ss_dyn_bwd: reverse sweep for dL/dy = gy.  per_sample = 1: grows [T][n][B] receives dL/d(row entry) of EVERY sample.
  *            per_sample = 0 / 2 (round 6: rows constant in time): the kernel sums over the steps itself (float64 accumulators):
@@ -601,10 +609,12 @@ int wdf_ss_dyn_fwd_tp(const float* x, const float* rows, int per_sample, int ns,
                       int hidden, int n_tanh_layers, int n_up, int n_down, float* y, float* zstash, const float* z0, float* zT,
                       int64_t B, int64_t T, int n_chunks, int warmup, float tol, const float* zinit, void* ws, void* status, void* stream);
 size_t wdf_ss_dyn_bwd_tp_ws_bytes(int ns, int64_t B, int64_t T, int n_chunks);
+size_t wdf_ss_dyn_bwd_tp_root_ws_bytes(int root, int ns, int64_t B, int64_t T, int n_chunks);
 int wdf_ss_dyn_bwd_tp(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
                       int hidden, int n_tanh_layers, int n_up, int n_down, const float* zstash, const float* gy, float* grows,
                       void* ws, float* gb, float* ain, float* lrin, float* gz0, int64_t B, int64_t T, int n_chunks, void* stream);
 size_t wdf_ss_dyn_bwd_ws_bytes(int64_t B);
+size_t wdf_ss_dyn_bwd_root_ws_bytes(int root, int64_t B);
 int wdf_ss_dyn_bwd(const float* x, const float* rows, int per_sample, int ns, int ni, int root, const float* rootp, const float* w,
                    int hidden, int n_tanh_layers, int n_up, int n_down, const float* zstash, const float* gy, float* grows,
                    void* ws, float* gb, float* ain, float* lrin, float* gz0, int64_t B, int64_t T, void* stream);

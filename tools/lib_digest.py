@@ -31,7 +31,7 @@ HEADER = os.path.join(HERE, "..", "include", "wdf_hip.h")
 GRID = {
     "B": [1, 63, 64, 129, 1340, 8192], "S": [1, 63, 64, 129, 1340, 8192], "T": [1, 31, 257, 2048, 4096],
     "n_chunks": [1, 2, 5, 32, 47], "wgrad_chunks": [1, 2, 5, 32, 47], "warmup": [0, 7, 64], "max_warm_tiles": [1, 4],
-    "n_params": [1, 4, 7],
+    "n_params": [1, 4, 7], "root": [0, 1, 2, 3, 4],                              # (root: the WDF_ROOT_* values and one that is none)
 }
 SS_SHAPES = [(ns, ni) for ni in (1, 2) for ns in range(0, 9)]                 # every export answers 0 outside its own range
 MLP_ARCHS = [(4, 3), (8, 3), (16, 3), (4, 4), (8, 4), (4, 5), (8, 5), (16, 5), (2, 3)]
