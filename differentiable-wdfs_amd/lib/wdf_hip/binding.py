@@ -1641,6 +1641,24 @@ def _dyn_rows_mode(rows, T, n, B, who):
     raise WdfHipError(f"{who}: rows [T,{n},B] (per sample), [1,{n},B] (per sequence) or [{n}] (static), got {shp}")
 
 
+def _dyn_check_shapes(who, ns, B, T, root_kind, rootp, z0=None, zstash=None, gy=None, sweep=False):
+    """What the wdf_ss_dyn_* kernels index by (ns, B, T) without the C ABI knowing the arrays' sizes: z0 [ns,B], and for the reverse
+    sweep (sweep=True) zstash [T,ns,B] and gy [T,B]; rootp {Is, nVt} under the diode pair, {Is_up, nVt_up, Is_down, nVt_down} under
+    two different diodes (a missing rootp is the C ABI's to refuse).  ns = 0 keeps one unread state slot, as ss_dyn_fwd allocates."""
+    s1 = max(int(ns), 1)
+    if z0 is not None and tuple(z0.shape) != (s1, B):
+        raise WdfHipError(f"{who}: z0 must be [ns,B] = [{s1},{B}], got {tuple(z0.shape)}")
+    if sweep:
+        if zstash is None or tuple(zstash.shape) != (T, s1, B):
+            raise WdfHipError(f"{who}: zstash must be [T,ns,B] = [{T},{s1},{B}], got {None if zstash is None else tuple(zstash.shape)}")
+        if gy is None or tuple(gy.shape) != (T, B):
+            raise WdfHipError(f"{who}: gy must be [T,B] = [{T},{B}], got {None if gy is None else tuple(gy.shape)}")
+    need = {ROOT_DIODE_PAIR: 2, ROOT_ASYM_PAIR: 4}.get(int(root_kind), 0)
+    if rootp is not None and rootp.numel() < need:
+        raise WdfHipError(f"{who}: rootp must hold {need} values for root kind {int(root_kind)} "
+                          f"({'Is, nVt' if need == 2 else 'Is_up, nVt_up, Is_down, nVt_down'}), got {rootp.numel()}")
+
+
 def ss_dyn_fwd(x, rows, ns, ni, root_kind=ROOT_NONE, rootp=None, w=None, hidden=0, n_tanh=0, n_up=1, n_down=1, want_stash=True,
                z0=None, want_zT=False):
     """State-space recursion with streamed coefficient rows / the MLP root on any small tree (wdf_ss_dyn_fwd).
@@ -1653,6 +1671,7 @@ def ss_dyn_fwd(x, rows, ns, ni, root_kind=ROOT_NONE, rootp=None, w=None, hidden=
     if x.dim() != 3 or int(x.shape[2]) != ni:
         raise WdfHipError(f"ss_dyn_fwd: x [B,T,{ni}] (got {tuple(x.shape)})")
     per = _dyn_rows_mode(rows, T, n, B, "ss_dyn_fwd")
+    _dyn_check_shapes("ss_dyn_fwd", ns, B, T, root_kind, rootp, z0=z0)
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, max(ns, 1), B), dtype=torch.float32, device=x.device) if (want_stash and ns > 0) else None
     zT = torch.empty((max(ns, 1), B), dtype=torch.float32, device=x.device) if want_zT else None
@@ -1673,6 +1692,7 @@ def ss_dyn_bwd(x, rows, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, w=N
     B, T = int(x.shape[0]), int(x.shape[1])
     n = lib().wdf_ss_dyn_row_len(int(ns), int(ni))
     per = _dyn_rows_mode(rows, T, n, B, "ss_dyn_bwd")
+    _dyn_check_shapes("ss_dyn_bwd", ns, B, T, root_kind, rootp, zstash=zstash, gy=gy, sweep=True)
     dev = x.device
     # per sample: dL/d(row) of every sample [T,n,B]; rows constant in time: the kernel's own sum over the steps [1,n,B]
     grows = torch.empty((T if per == 1 else 1, n, B), dtype=torch.float32, device=dev)
@@ -1719,6 +1739,7 @@ def ss_dyn_fwd_tp(x, rows, ns, ni, n_chunks, warmup, tol=1.0e-6, root_kind=ROOT_
     if x.dim() != 3 or int(x.shape[2]) != ni:
         raise WdfHipError(f"ss_dyn_fwd_tp: x [B,T,{ni}] (got {tuple(x.shape)})")
     per = _dyn_rows_mode(rows, T, n, B, "ss_dyn_fwd_tp")
+    _dyn_check_shapes("ss_dyn_fwd_tp", ns, B, T, root_kind, rootp, z0=z0)
     K = dyn_chunks(T, n_chunks)
     if zinit is not None and tuple(zinit.shape) != (K, ns, B):
         raise WdfHipError(f"ss_dyn_fwd_tp: zinit must be [{K},{ns},{B}], got {tuple(zinit.shape)}")
@@ -1801,6 +1822,7 @@ def ss_dyn_bwd_tp(x, rows, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, ro
     B, T = int(x.shape[0]), int(x.shape[1])
     n = lib().wdf_ss_dyn_row_len(int(ns), int(ni))
     per = _dyn_rows_mode(rows, T, n, B, "ss_dyn_bwd_tp")
+    _dyn_check_shapes("ss_dyn_bwd_tp", ns, B, T, root_kind, rootp, zstash=zstash, gy=gy, sweep=True)
     dev = x.device
     K = dyn_chunks(T, n_chunks)
     # per sample: [T,n,B]; rows constant in time: one partial per chunk [K,n,B], added up below

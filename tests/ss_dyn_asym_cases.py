@@ -39,6 +39,14 @@ CASES = {
     "two_state_vs2": dict(tree="two_state", shape=(70, 300, 2), pot=3, chan=lambda B, T: pot_channel(B, T, 2.0e3, 40.0e3, 3), seed=4),
     "four_state_small": dict(tree="four_state", shape=(5, 131, 1), pot=None, chan=None, seed=0),
     "four_state": dict(tree="four_state", shape=(70, 300, 1), pot=None, chan=None, seed=1),
+    # chunks beyond one state (tests/test_gpu_ss_dyn_chunks_state.py): 70 x 131 -- one full and one ragged wave; four chunks of
+    # 8-step units are 40, 40, 40 and 11 steps, the last one ragged and no whole unit
+    "two_state_vs2_c": dict(tree="two_state", shape=(70, 131, 2), pot=3, chan=lambda B, T: pot_channel(B, T, 2.0e3, 40.0e3, 3), seed=0),
+    "three_state_c": dict(tree="three_state", shape=(70, 131, 1), pot=None, chan=None, seed=4),
+    "three_state_r1": dict(tree="three_state", shape=(70, 131, 1), pot=2, chan=lambda B, T: pot_channel(B, T, 2.0e3, 20.0e3, 4), seed=1),
+    "four_state_c": dict(tree="four_state", shape=(70, 131, 1), pot=None, chan=None, seed=1),
+    "four_state_vs": dict(tree="four_state", shape=(70, 131, 1), pot=0, chan=lambda B, T: pot_channel(B, T, 300.0, 5.0e3, 1), seed=1),
+    "four_state_vs_seq": dict(tree="four_state", shape=(70, 131, 1), pot=0, chan=pot_grid, seed=1),
 }
 
 
@@ -77,9 +85,21 @@ def two_state(W, pot_on=None, time_parallel=None, root_kw=None, **kw):
     return W.Circuit(top, dp, C2, per_sample_R=pot, time_parallel=time_parallel, **kw), params
 
 
+def three_state(W, pot_on=None, time_parallel=None, **kw):
+    """ss_asym_cases.three_state's tree.  theta = [Vs.R, R0, R1, C0, C1, C2, diodes]; pot_on: None | "R1"."""
+    Vs = W.ResistiveVoltageSource(1.0e3, trainable=True)
+    Rs = [W.Resistor(v, True) for v in (33.0e3, 6.8e3)]
+    Cs = [W.Capacitor(v, FS, True) for v in (47.0e-9, 22.0e-9, 10.0e-9)]
+    top = W.Parallel(Cs[2], W.Series(Rs[1], W.Parallel(Cs[1], W.Series(W.Series(Vs, Cs[0]), Rs[0]))))
+    dp = _root(W, top)
+    pot = {"R1": Rs[1], None: None}[pot_on]
+    params = [v for e, v in [(Vs, Vs.R)] + [(e, e.R) for e in Rs] + [(e, e.C) for e in Cs] if e is not pot] + _diode_vars(dp)
+    return W.Circuit(top, dp, Cs[2], per_sample_R=pot, time_parallel=time_parallel, **kw), params
+
+
 def four_state(W, pot_on=None, time_parallel=None, **kw):
-    """ss_asym_cases.four_state_top: four capacitors, what any_tree=True refuses.  theta = [Vs.R, R0, R1, R2, C0..C3, diodes]."""
-    assert pot_on is None
+    """ss_asym_cases.four_state_top: four capacitors, what any_tree=True refuses.  theta = [Vs.R, R0, R1, R2, C0..C3, diodes];
+    pot_on: None | "Vs"."""
     top, probe = base.four_state_top(W)
     s1 = top.P2                               # Series(R2, Parallel(C2, Series(R1, Parallel(C1, Series(Series(Vs, C0), R0)))))
     p2 = s1.P2
@@ -88,8 +108,9 @@ def four_state(W, pot_on=None, time_parallel=None, **kw):
     inner = p3.P2
     Vs, C0, R0 = inner.P1.P1, inner.P1.P2, inner.P2
     dp = _root(W, top)
-    params = [Vs.R, R0.R, s2.P1.R, s1.P1.R, C0.C, p3.P1.C, p2.P1.C, top.P1.C] + _diode_vars(dp)
-    return W.Circuit(top, dp, probe, time_parallel=time_parallel, **kw), params
+    pot = {"Vs": Vs, None: None}[pot_on]
+    params = ([] if pot is Vs else [Vs.R]) + [R0.R, s2.P1.R, s1.P1.R, C0.C, p3.P1.C, p2.P1.C, top.P1.C] + _diode_vars(dp)
+    return W.Circuit(top, dp, probe, per_sample_R=pot, time_parallel=time_parallel, **kw), params
 
 
 def four_state_ref():
@@ -99,9 +120,9 @@ def four_state_ref():
     return tree, c3, f32([1.0e3, 33.0e3, 6.8e3, 15.0e3, 47.0e-9, 22.0e-9, 10.0e-9, 4.7e-9] + base.DIODES)
 
 
-BUILD = {"hpf": hpf, "two_state": two_state, "four_state": four_state}
-REFS = {"hpf": base.hpf_ref, "two_state": base.two_state_ref, "four_state": four_state_ref}
-POT_NAME = {("hpf", 0): "R", ("hpf", 1): "Vs", ("two_state", 3): "Vs2"}
+BUILD = {"hpf": hpf, "two_state": two_state, "three_state": three_state, "four_state": four_state}
+REFS = {"hpf": base.hpf_ref, "two_state": base.two_state_ref, "three_state": base.three_state_ref, "four_state": four_state_ref}
+POT_NAME = {("hpf", 0): "R", ("hpf", 1): "Vs", ("two_state", 3): "Vs2", ("three_state", 2): "R1", ("four_state", 0): "Vs"}
 
 
 def build(W, name, time_parallel=None, **kw):
