@@ -1628,6 +1628,117 @@ def ss_asym_step_esr(x, coef, rootp, ns, ni, target, n_global, eps_energy, skip,
     return y, zT, sums, g, loss3, status
 
 
+def _lin_step_shape(x_tm, coef):
+    """(ns, ni, B, T, ncoef) of a linear one-pass step from x_tm [T,ni,B] and coef ([ncoef], or the probe's [ncoef + 1] with the
+    port resistance behind it): the ns in 0..2 whose wdf_ss_ncoef fits."""
+    if x_tm.dim() != 3 or x_tm.shape[1] not in (1, 2) or x_tm.shape[0] < 1 or x_tm.shape[2] < 1:
+        raise WdfHipError(f"ss_lin_step_mse: x_tm must be [T,ni,B] with ni in 1..2, got {tuple(x_tm.shape)}")
+    T, ni, B = (int(v) for v in x_tm.shape)
+    for ns in (0, 1, 2):
+        ncoef = lib().wdf_ss_ncoef(ns, ni)
+        if coef.dim() == 1 and coef.numel() in (ncoef, ncoef + 1):
+            return ns, ni, B, T, ncoef
+    raise WdfHipError(f"ss_lin_step_mse: coef {tuple(coef.shape)} is no coefficient vector of ns in 0..2 states and ni = {ni} inputs")
+
+
+def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=False, want_gcoef=False, ws=None, y=None):
+    """The MSE training step of a LINEAR tree in one pass (wdf_ss_lin_step_mse, csrc/wdf_ss_step.h): forward, the sum of squared
+    errors, d(gscale/2 x that sum)/d{A, Bx, cy, dy} carried forward in time and its contraction with jac.  x_tm [T,ni,B] time-major,
+    coef in SSCoef order (ns from its length), jac float64 [ncoef (+1), n_params] (ss_probe's), target [T,B]; z0 [ns,B] or None.
+    ws: zeroed wdf_ss_lin_step_ws_bytes() bytes when not given (the step leaves it clean); y, ws and z0 are used as they are --
+    the library pairs sequences up by their addresses.
+    -> dict: y [T,B], out [1 + n_params] = {SSE, gradients}, loss (0-dim), gcoef [ns^2 + ns ni + ns + ni] | None, zT [ns,B] | None, ws."""
+    require_gpu()
+    x_tm, coef, target, z0 = _f32_dev(x_tm, "x_tm"), _f32_dev(coef, "coef"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
+    ns, ni, B, T, ncoef = _lin_step_shape(x_tm, coef)
+    if not (isinstance(jac, torch.Tensor) and jac.is_cuda and jac.dtype == torch.float64 and jac.is_contiguous() and jac.dim() == 2
+            and jac.shape[0] in (ncoef, ncoef + 1) and 1 <= jac.shape[1] <= 15):
+        raise WdfHipError(f"ss_lin_step_mse: jac must be a contiguous float64 [{ncoef} (+1), 1..15] tensor on the GPU")
+    n_params = int(jac.shape[1])
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if ns > 0 and z0 is not None and tuple(z0.shape) != (ns, B):
+        raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
+    if y is None:
+        y = torch.empty((T, B), dtype=torch.float32, device=x_tm.device)
+    elif tuple(_f32_dev(y, "y").shape) != (T, B):
+        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    need = lib().wdf_ss_lin_step_ws_bytes(ns, ni, B, T, int(n_chunks))
+    if need == 0:
+        raise WdfHipError(f"ss_lin_step_mse: no step for ns={ns}, ni={ni}, B={B}, T={T}, n_chunks={n_chunks}")
+    if ws is None:
+        ws = torch.zeros((need,), dtype=torch.uint8, device=x_tm.device)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.is_contiguous()) or ws.numel() * ws.element_size() < need:
+        raise WdfHipError(f"ws must hold the {need} bytes the step needs, on the GPU")
+    out = torch.empty((1 + n_params,), dtype=torch.float32, device=x_tm.device)
+    loss = torch.empty((), dtype=torch.float32, device=x_tm.device)
+    gcoef = torch.empty((ns * ns + ns * ni + ns + ni,), dtype=torch.float32, device=x_tm.device) if want_gcoef else None
+    zT = torch.empty((ns, B), dtype=torch.float32, device=x_tm.device) if (want_zT and ns > 0) else None
+    _check(lib().wdf_ss_lin_step_mse(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), float(gscale), _ptr(y), _ptr(ws),
+                                     _ptr(out), _ptr(loss), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()),
+           "wdf_ss_lin_step_mse")
+    return {"y": y, "out": out, "loss": loss, "gcoef": gcoef, "zT": zT, "ws": ws}
+
+
+PROBE_MAX_OPS, PROBE_MAX_PARAMS = 384, 15                                            # csrc/wdf_ss_step.h
+
+
+def _probe_tape(ops, consts, outs, n_params):
+    """The host arrays of a probe tape, refused where the kernel would index its LDS arrays (or params / consts) out of range:
+    an operand is an EARLIER node, a leaf's index lies inside consts / the parameter block, an output is a node."""
+    ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 3)
+    consts = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+    outs = np.ascontiguousarray(outs, dtype=np.int32).reshape(-1)
+    n = len(ops)
+    if not 1 <= n <= PROBE_MAX_OPS or not 1 <= n_params <= PROBE_MAX_PARAMS or len(outs) < 1:
+        raise WdfHipError(f"ss_probe: 1..{PROBE_MAX_OPS} operations on 1..{PROBE_MAX_PARAMS} parameters, at least one output "
+                          f"(got {n}, {n_params}, {len(outs)})")
+    op, a, b = ops[:, 0], ops[:, 1], ops[:, 2]
+    i = np.arange(n)
+    two, one = (op >= 2) & (op <= 5), (op == 6) | (op == 7)                           # ADD SUB MUL DIV / NEG RECIP (probe_tape.OP_*)
+    bad = (op < 0) | (op > 7)
+    bad |= (op == 0) & ((a < 0) | (a >= len(consts)))
+    bad |= (op == 1) & ((a < 0) | (a >= n_params))
+    bad |= (two | one) & ((a < 0) | (a >= i))
+    bad |= two & ((b < 0) | (b >= i))
+    if bad.any():
+        k = int(np.argmax(bad))
+        raise WdfHipError(f"ss_probe: operation {k} = {ops[k].tolist()} names a later node or an index outside the tape")
+    if ((outs < 0) | (outs >= n)).any():
+        raise WdfHipError(f"ss_probe: an output names a node outside the tape's {n}")
+    return ops, consts, outs
+
+
+def ss_probe(ops, consts, params, outs, jobs=None):
+    """The probed step `ops` [n_ops,3] / `consts` (probe_tape.Tape.packed()) at the float32 parameter block `params` on the device,
+    in float64 with forward tangents (wdf_ss_probe): -> coef float32 [n_out], coef64 [n_out], jac float64 [n_out, n_params] of the
+    nodes `outs`.  jobs: [(Adam, theta, grad), ...] as for adam_jobs -- their updates are applied in the same launch BEFORE the
+    probe reads the parameters (wdf_ss_probe_adam)."""
+    require_gpu()
+    params = _f32_dev(params, "params")
+    n_params = int(params.numel())
+    ops, consts, outs = _probe_tape(ops, consts, outs, n_params)
+    jobs = list(jobs) if jobs else []
+    if len(jobs) > ADAM_MULTI_MAX:
+        raise WdfHipError(f"ss_probe: at most {ADAM_MULTI_MAX} jobs")
+    dev = params.device
+    tape_d = torch.as_tensor(ops, device=dev)
+    consts_d = torch.as_tensor(consts if len(consts) else np.zeros(1), device=dev)
+    outs_d = torch.as_tensor(outs, device=dev)
+    n_out = len(outs)
+    coef = torch.empty((n_out,), dtype=torch.float32, device=dev)
+    coef64 = torch.empty((n_out,), dtype=torch.float64, device=dev)
+    jac = torch.empty((n_out, n_params), dtype=torch.float64, device=dev)
+    tail = (_ptr(tape_d), len(ops), _ptr(consts_d), _ptr(params), n_params, _ptr(outs_d), n_out, _ptr(coef), _ptr(coef64), _ptr(jac),
+            _stream())
+    if jobs:
+        arr = adam_jobs(jobs)
+        _check(lib().wdf_ss_probe_adam(C.cast(arr, C.c_void_p), len(jobs), *tail), "wdf_ss_probe_adam")
+    else:
+        _check(lib().wdf_ss_probe(*tail), "wdf_ss_probe")
+    return coef, coef64, jac
+
+
 def _dyn_rows_mode(rows, T, n, B, who):
     """per_sample argument of the wdf_ss_dyn_* entry points from the rows' shape: [n] -> 0 (one static row), [T,n,B] -> 1 (a row
     per sample), [1,n,B] with T > 1 -> 2 (a row per sequence: constant along the time axis)."""

@@ -208,6 +208,23 @@ def test_state_space_chunked_argument_validation_without_gpu(lib):
     _cases(lib, "wdf_ss_lin_step_mse", lin, good,
            [(dict(x=None), -1, b"null"), (dict(ws=None), -1, b"null"), (dict(ns=3), -3, None), (dict(ni=0), -3, None), (dict(B=0), -1, None),
             (dict(n_chunks=0), -1, None), (dict(n_params=0), -1, None), (dict(z0=ONE, zT=ONE), -1, b"alias")])
+    # the linear step's device probe, alone and behind queued Adam jobs (every case fails its checks before the launch)
+    from wdf_hip import binding
+    probe = "tape n_ops consts params n_params outs n_out coef coef64 jac stream".split()
+    good = dict(tape=ONE, n_ops=12, consts=ONE, params=ONE, n_params=2, outs=ONE, n_out=9, coef=ONE, coef64=ONE, jac=ONE, stream=None)
+    bad = [(dict(tape=None), -1, b"null"), (dict(outs=None), -1, b"null"), (dict(jac=None), -1, b"null"), (dict(n_ops=0), -3, b"1..384"),
+           (dict(n_ops=385), -3, b"1..384"), (dict(n_params=0), -3, b"1..15"), (dict(n_params=16), -3, b"1..15"), (dict(n_out=0), -1, b"n_out")]
+    _cases(lib, "wdf_ss_probe", probe, good, bad)
+    job = (binding._AdamJob * 1)()
+    job[0].theta = job[0].grad = job[0].m = job[0].v = job[0].step = job[0].lr = 256
+    job[0].beta1, job[0].beta2, job[0].eps, job[0].n = 0.9, 0.999, 1e-7, 4
+    no_lr, too_long = (binding._AdamJob * 1)(job[0]), (binding._AdamJob * 1)(job[0])
+    no_lr[0].lr, too_long[0].n = None, 1025
+    good = dict(good, jobs=C.cast(job, C.c_void_p), n_jobs=1)
+    _cases(lib, "wdf_ss_probe_adam", ["jobs", "n_jobs"] + probe, good,
+           bad + [(dict(n_jobs=9), -1, b"0..8 jobs"), (dict(n_jobs=-1), -1, b"0..8 jobs"), (dict(jobs=None), -1, b"0..8 jobs"),
+                  (dict(jobs=C.cast(no_lr, C.c_void_p)), -1, b"job 0: null"), (dict(jobs=C.cast(too_long, C.c_void_p)), -1, b"1..1024"),
+                  (dict(jobs=C.cast(job, C.c_void_p), n_ops=385), -3, b"wdf_ss_probe_adam")])
     dyn = ("x rows per_sample ns ni root rootp w hidden n_tanh_layers n_up n_down y zstash z0 zT B T n_chunks warmup tol zinit ws status "
            "stream").split()
     good = dict(x=ONE, rows=ONE, per_sample=1, ns=2, ni=1, root=0, rootp=None, w=None, hidden=0, n_tanh_layers=0, n_up=1, n_down=1, y=ONE,
