@@ -148,12 +148,19 @@ inline TpBwdWs tp_bwd_ws(void* ws, int64_t B, int K)
 }
 
 // ---- the one-pass training step (wdf_clipper_fused.h) --------------------------------------------
-struct FusedWs { double* part; double* wpart; float* zwarm; float* zend; float* rec; unsigned* tickets; unsigned* gticket; size_t bytes; };
+struct FusedWs { double* part; double* wpart; float* zwarm; float* zend; float* rec; unsigned* tickets; unsigned* gticket; size_t clear_bytes;
+                 wdf::FusedGroupWs grp; size_t bytes; };
+
+// chunk waves per workgroup of the group form, and the groups a tile then has
+inline int fused_group_waves(int K) { return std::min(wdf::kGroupWaves, K); }
+inline int fused_groups(int K) { return (K + fused_group_waves(K) - 1) / fused_group_waves(K); }
 
 // ONE layout for both losses (sized for the larger, MSE + ESR; a workspace may serve either from call to call):
 // [tiles][8] doubles (the tiles' sums; MSE uses 4 of them), [tiles][K][slots][8] doubles (the chunk waves' own sums, one set
 // per sequence slot of a lane), zwarm / zend [K][B], the records (16-byte granules [K][3][lanes], lanes <= 64 x ceil(B / 64)),
-// then -- on a 64-byte line: wdf_clipper_step_mse_tp_ws_init clears from there on -- the tile tickets and the step's ticket line.
+// then -- on a 64-byte line: wdf_clipper_step_mse_tp_ws_init clears these -- the tile tickets and the step's ticket line.
+// Behind them what the group form's workgroups hand to their finish launch, per group of chunks as the areas above are per
+// chunk: the group records, the groups' own sums, their verdicts (8 bytes per tile and group).
 inline FusedWs fused_ws(void* ws, int64_t B, int K)
 {
     const size_t tiles = waves64(B) + 1;                       // >= tiles x slots for either lane form
@@ -165,20 +172,43 @@ inline FusedWs fused_ws(void* ws, int64_t B, int K)
     w.zend = c.take<float>((size_t)K * (size_t)B);
     w.rec = c.take<float>((size_t)K * wdf::kFsQuads * (waves64(B) * 64) * 4);
     c.align(64);
+    const size_t tickets_at = c.off;
     w.tickets = c.take<unsigned>(tp_ticket_bytes(B) / sizeof(unsigned));
     w.gticket = c.take<unsigned>(16);
+    w.clear_bytes = c.off - tickets_at;
+    c.align(16);
+    const size_t Kg = (size_t)fused_groups(K);
+    w.grp.rec = c.take<float>(Kg * wdf::kFsQuads * (waves64(B) * 64) * 4);
+    w.grp.part = c.take<double>(tiles * Kg * wdf::kFsPartEsr);
+    w.grp.verdict = c.take<unsigned long long>(tiles * Kg);
     w.bytes = c.off;
     return w;
+}
+
+// The form of the one-pass step's launches (launch_fused).  window: x goes through a per-workgroup window in LDS (those launches
+// keep one chunk wave to a workgroup); n_waves: chunk waves of the launch.  WDF_FUSED_FINISH = group | launch | inkernel names the
+// form (read at every call: tests and A/B runs switch it inside one process).  Unset: the finish launch of round 6.  The group
+// form is opt-in: at the headline shape it was measured 0.3 - 0.8 us ahead of that form on the same build, inside the spread
+// (profiles/README.md), and in workgroups of eight a launch of fewer than two chunk waves per SIMD leaves CUs idle.
+inline int fused_form(int K, bool window)
+{
+    if (K < 2) return wdf::kFusedInKernel;                   // one chunk: no boundary, no record walk, no second launch
+    const char* e = getenv("WDF_FUSED_FINISH");
+    if (e == nullptr) return wdf::kFusedFinishLater;
+    if (strcmp(e, "inkernel") == 0) return wdf::kFusedInKernel;
+    return (strcmp(e, "group") == 0 && !window) ? wdf::kFusedGroup : wdf::kFusedFinishLater;
 }
 
 // Skewed chunk spans (wdf_clipper_fused.h, chunk_span): only when the launch puts about two chunk waves on every SIMD --
 // that is the situation the skew answers -- the chunk count is even, the ragged last chunk keeps more than `skew` steps and
 // the shorter chunks still hold the warm-start snapshots.  WDF_FUSED_SKEW=0 switches it off, =force applies it whenever
-// the geometry allows (tests).
-inline int64_t fused_skew(int64_t n_waves, int K, int64_t L, int64_t T, int max_warm_tiles)
+// the geometry allows (tests).  grouped (the group form, whole groups only): the long and the short spans alternate by half
+// groups, returned as a negative skew.
+inline int64_t fused_skew(int64_t n_waves, int K, int64_t L, int64_t T, int max_warm_tiles, bool grouped)
 {
     static const int mode = []() { const char* e = getenv("WDF_FUSED_SKEW"); return !e ? 1 : (strcmp(e, "force") == 0 ? 2 : atoi(e) != 0); }();
     if (mode == 0 || K < 2 || (K & 1)) return 0;
+    if (grouped && K % wdf::kGroupWaves != 0) return 0;
     if (mode == 1) {
         static const int n_simd = []() { int dev = 0, cus = 256; (void)hipGetDevice(&dev);
                                          (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); return 4 * cus; }();
@@ -189,36 +219,46 @@ inline int64_t fused_skew(int64_t n_waves, int K, int64_t L, int64_t T, int max_
     if (skew <= 0 || skew >= L) return 0;
     if (T - (int64_t)(K - 1) * L <= skew) return 0;                                   // the last chunk would be empty
     if ((int64_t)max_warm_tiles * wdf::kWarmStep > L - skew) return 0;                      // snapshots reach further back than the short chunks
-    return skew;
+    return grouped ? -skew : skew;
 }
 
 template <int DYN_R, bool SYM, bool TM, bool V4>
 void launch_fused(const float* x, const float* r, const float* theta, float fs, int n_up, int n_down, const float* target,
                   float hgs, int64_t skip, float* y, const float* z0, float* zT, FusedWs w, wdf::TpStatus* status, float tol,
                   int64_t B, int64_t T, ChunkGeom g, int64_t W, TpWarm warm, int general, bool pairs, bool esr, wdf::FusedOut out,
-                  int64_t skew, hipStream_t s)
+                  int64_t skew, int form, hipStream_t s)
 {
     // pairs: two adjacent sequences per lane, packed fp32 arithmetic (wdf_clipper_fused.h); a tile is then 128 sequences
     const int per_tile = pairs ? 128 : 64;
-    const dim3 grid((unsigned)((B + per_tile - 1) / per_tile), (unsigned)g.K);
-    // Round 6: the step's tail (verification, walk over the chunk records, reduction, chain rule, warm-start steering, Adam) and the
-    // repair of missed tiles are ONE launch behind the chunk kernel, several waves per tile (clipper_fused_finish_kernel).
-    // WDF_FUSED_FINISH=inkernel restores the round-5 form (the tile's last chunk wave does the tail, an idle repair launch follows).
-    static const bool finish_inkernel = []() { const char* e = getenv("WDF_FUSED_FINISH"); return e && strcmp(e, "inkernel") == 0; }();
-    const int later = (g.K > 1 && !finish_inkernel) ? 1 : 0;
+    // The step's tail (verification, walk over the chunk records, reduction, chain rule, warm-start steering, Adam) and the repair
+    // of missed tiles are ONE launch behind the chunk kernel.  WDF_FUSED_FINISH picks the form:
+    //   group    G = min(8, K) chunk waves to a workgroup, which combine in LDS (wdf_clipper_fused.h, fused_group_compose); the finish
+    //            launch walks ceil(K / G) group records per tile with one wave (clipper_fused_group_finish_kernel).  Opt-in;
+    //            not where x goes through a per-workgroup window in LDS (batch-major x in 16-byte rows): those launches
+    //            take the next form.
+    //   launch   round 6, the default: one chunk wave to a workgroup, several finishing waves per tile (clipper_fused_finish_kernel).
+    //   inkernel round 5: the tile's last chunk wave does the tail, an idle repair launch follows.
+    // (fused_form above reads it.)
+    const int G = form == wdf::kFusedGroup ? fused_group_waves(g.K) : 1;
+    const dim3 grid((unsigned)((B + per_tile - 1) / per_tile), (unsigned)((g.K + G - 1) / G));
     // waves per tile of the finish launch: the chunks spread over as many of the kFinMaxWaves as leaves each at least kFinMinSeg
     // records (32 chunks: 8 waves of 4; 128: 8 waves of 16 in two register batches)
     const int fin_waves = (int)std::min<int64_t>(wdf::kFinMaxWaves, (g.K + wdf::kFinMinSeg - 1) / wdf::kFinMinSeg);
     dispatch([&](auto PAIRS, auto LOSS) {                      // LOSS 1: MSE, 2: MSE + ESR
         using V = std::conditional_t<PAIRS(), wdf::v2f, float>;
         constexpr int N = PAIRS() ? 2 : 1;                     // sequences per lane
+        const size_t lds = form == wdf::kFusedGroup ? (size_t)G * sizeof(wdf::GroupStage<N, LOSS()>) : 0;
         {
             EventBracket bracket(s);
-            hipLaunchKernelGGL((wdf::clipper_fused_tp_kernel<DYN_R, SYM, TM, V4, V, LOSS()>), grid, dim3(64), 0, s, x, r, theta, fs, n_up,
+            hipLaunchKernelGGL((wdf::clipper_fused_tp_kernel<DYN_R, SYM, TM, V4, V, LOSS()>), grid, dim3(64 * G), lds, s, x, r, theta, fs, n_up,
                                n_down, target, hgs, skip, y, z0, zT, w.zwarm, w.zend, w.rec, status, warm.ctl, warm.snap, warm.J, w.tickets,
-                               w.gticket, tol, B, T, g.L, W, general, w.part, out, skew, w.wpart, later);
+                               w.gticket, tol, B, T, (int64_t)g.K, g.L, W, general, w.part, out, skew, w.wpart, form, w.grp);
         }
-        if (later)
+        if (form == wdf::kFusedGroup)
+            hipLaunchKernelGGL((wdf::clipper_fused_group_finish_kernel<DYN_R, SYM, TM, N, LOSS()>), dim3(grid.x), dim3(64), 0, s, x, r, theta, fs,
+                               n_up, n_down, target, hgs, skip, y, zT, w.zwarm, w.zend, w.rec, B, T, (int64_t)g.K, g.L, tol, status, warm.ctl,
+                               warm.snap, warm.J, w.tickets, w.gticket, general, w.part, out, skew, w.wpart, W, G, w.grp);
+        else if (form == wdf::kFusedFinishLater)
             hipLaunchKernelGGL((wdf::clipper_fused_finish_kernel<DYN_R, SYM, TM, N, LOSS()>), dim3(grid.x), dim3(64 * fin_waves), 0, s, x, r,
                                theta, fs, n_up, n_down, target, hgs, skip, y, zT, w.zwarm, w.zend, w.rec, B, T, (int64_t)g.K, g.L, tol,
                                status, warm.ctl, warm.snap, warm.J, w.tickets, w.gticket, general, w.part, out, skew, w.wpart, W);
@@ -479,7 +519,7 @@ int wdf_clipper_step_mse_tp_ws_init(void* ws, int64_t B, int n_chunks, void* str
 {
     if (!ws || B <= 0 || n_chunks <= 0) return fail(WDF_EINVAL, "null ws / bad B, n_chunks");
     const FusedWs w = fused_ws(ws, B, n_chunks);
-    return memset_async(w.tickets, 0, (char*)ws + w.bytes - (char*)w.tickets, (hipStream_t)stream);
+    return memset_async(w.tickets, 0, w.clear_bytes, (hipStream_t)stream);
 }
 
 static int step_tp_common(const float* x, const float* r, float* theta, float fs, int n_up, int n_down, const float* target,
@@ -513,13 +553,15 @@ static int step_tp_common(const float* x, const float* r, float* theta, float fs
     // two adjacent sequences per lane (8-byte row accesses, packed arithmetic) whenever the rows allow it
     const bool pairs = !(flags & WDF_ONE_SEQUENCE_PER_LANE) && (B % 2 == 0) && aligned8(x) && aligned8(target) && aligned8(y) &&
                        (!r || aligned8(r));
-    const int64_t skew = fused_skew((B + (pairs ? 127 : 63)) / (pairs ? 128 : 64) * (int64_t)g.K, g.K, g.L, T, state ? max_warm_tiles : 0);
     // WDF_R_PER_SEQUENCE: one pot value per sequence (the caller vouches for it): calc_impedance once per chunk, the channel not streamed
     const int dyn = r == nullptr ? 0 : ((flags & WDF_R_PER_SEQUENCE) ? 2 : 1);
+    const int64_t n_waves = (B + (pairs ? 127 : 63)) / (pairs ? 128 : 64) * (int64_t)g.K;
+    const int form = fused_form(g.K, !tm && v4 && dyn != 1);    // (wdf::fused_x_window)
+    const int64_t skew = fused_skew(n_waves, g.K, g.L, T, state ? max_warm_tiles : 0, form == wdf::kFusedGroup);
     const bool ok = dispatch4([&](auto DYN, auto SYM, auto TM, auto V4) {
         launch_fused<DYN(), SYM(), TM(), V4()>(x, r, theta, fs, n_up, n_down, target, hgs, skip, y, z0, zT, fused_ws(ws, B, g.K),
                                                (wdf::TpStatus*)status, tol, B, T, g, W, warm, (flags & WDF_GENERAL_ROOT) ? 1 : 0, pairs, esr, out,
-                                               skew, (hipStream_t)stream);
+                                               skew, form, (hipStream_t)stream);
     }, Values<int, 0, 1, 2>{dyn}, n_up == n_down, tm, v4);
     if (!ok) return no_kernel(what);
     return check_launch(what);

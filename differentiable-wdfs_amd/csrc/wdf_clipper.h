@@ -579,7 +579,7 @@ struct TpCtl {
     float th2[4];     // theta of the call before
     float last_miss;  // largest boundary miss of the last call
     int n_calls;
-    int geom;         // tp_geom_tag(K, J, skewed spans?) of the calls that wrote the snapshots; another geometry restarts cold
+    int geom;         // tp_geom_tag(K, J, span scheme) of the calls that wrote the snapshots; another geometry restarts cold
     int j_floor;      // low byte: the controller never goes below this many warm-up tiles (host: 0; = max pins it); above: hold counter
     float th3[4];     // theta of the call before th2's (the quadratic extrapolation's third point)
     int cold_hold;    // > 0: the next calls start their chunks COLD (z = 0, the planned warm-up) while still leaving snapshots
@@ -590,7 +590,10 @@ static_assert(sizeof(TpCtl) == 128, "TpCtl layout");
 // What identifies the chunk boundaries the snapshots were taken at: chunk count, snapshot depth, and whether the one-pass
 // step's skewed spans (wdf_clipper_fused.h, chunk_span) were in force -- the forward kernel always runs equal spans, so a
 // state shared between the two kernels restarts cold instead of loading snapshots from the other kernel's boundaries.
-__device__ __forceinline__ int tp_geom_tag(int64_t K, int J, bool skewed) { return (int)((K << 8) | J) | (skewed ? (1 << 30) : 0); }
+// spans: 0 equal spans, 1 long spans in the first half of the chunks, 2 long spans in the first half of every group of chunks
+// (tp_span_scheme of the step's skew): another scheme has other boundaries, so its snapshots are not this one's either.
+__device__ __forceinline__ int tp_span_scheme(int64_t skew) { return skew > 0 ? 1 : (skew < 0 ? 2 : 0); }
+__device__ __forceinline__ int tp_geom_tag(int64_t K, int J, int spans) { return (int)((K << 8) | J) | (spans ? (1 << 30) : 0) | (spans == 2 ? (1 << 29) : 0); }
 
 // Where a chunk starts from: the snapshots of the last calls, extrapolated ALONG THE PARAMETER PATH to this call's theta.
 // With d1 = theta/th1 - 1 (this call against the last), d0 = th1/th2 - 1, d00 = th2/th3 - 1 (relative steps, 4-vectors) the
@@ -866,7 +869,7 @@ __device__ __forceinline__ bool tp_tile_last(unsigned* tickets)
 __device__ __forceinline__ void tp_publish_status_and_steer(const float* __restrict__ theta, TpStatus* __restrict__ status,
                                                             TpCtl* __restrict__ ctl, const TpCtl& c0, int J, unsigned* tickets,
                                                             float tol, int64_t K, int64_t L, int64_t W, int nb, float mm,
-                                                            bool keep_fallback_count, bool skewed = false)
+                                                            bool keep_fallback_count, int skewed = 0)
 {
     TpAcc* acc = reinterpret_cast<TpAcc*>(tickets);
     if (keep_fallback_count) { status->n_bad = nb; status->max_miss = mm; }      // (fallback_ran: the repair launch adds to it)
@@ -930,6 +933,9 @@ __device__ __forceinline__ void tp_publish_status_and_steer(const float* __restr
     c.geom = tp_geom_tag(K, J, skewed);
     c.last_miss = mm;
     c.n_calls = stateful ? c.n_calls + 1 : 1;
+#pragma unroll
+    for (int i = 0; i < 11; ++i) c.pad[i] = 0;                  // (copied through from the block as it was read, the padding is the one part of
+                                                                //  c that cannot live in registers: a private array, LDS or a scratch frame)
     *ctl = c;
 }
 
@@ -1240,7 +1246,7 @@ __device__ __forceinline__ void adam_tail_apply(const AdamTail& adam, const Adam
 
 // The verification's deferred half (one-pass step, tp_verify_tile<..., DEFER>): what the finishing wave needs to publish the
 // status and steer the warm start.  status == nullptr: nothing deferred (the reverse sweep).
-struct TpFinishCtx { TpStatus* status; TpCtl* ctl; int J; unsigned* tickets; float tol; int64_t K, L, W; bool skewed = false; };
+struct TpFinishCtx { TpStatus* status; TpCtl* ctl; int J; unsigned* tickets; float tol; int64_t K, L, W; int skewed = 0; };   // skewed: tp_span_scheme
 
 // Fetched as soon as a wave knows it finishes the step (every tile has added its share by then: the adds were awaited before
 // each tile's step ticket), used after the reduction.

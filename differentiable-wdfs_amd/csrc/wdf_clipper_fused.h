@@ -106,7 +106,7 @@ struct LaneOwn {
     bool live;
     __device__ __forceinline__ explicit LaneOwn(int64_t B)
     {
-        const int64_t raw = ((int64_t)blockIdx.x * 64 + threadIdx.x) * N;
+        const int64_t raw = ((int64_t)blockIdx.x * 64 + (threadIdx.x & 63u)) * N;   // (the group form: eight chunk waves to a workgroup)
         live = raw < B;
         b = live ? raw : B - N;
         boff = (uint32_t)b * 4u;
@@ -119,8 +119,20 @@ struct LaneOwn {
 // the older one has finished the younger runs alone at the single-wave rate for a third of the kernel (tools/dbg_times.py).
 // Giving the older wave the longer chunk lets both finish together: -5 % (one sequence per lane, 16 chunks) / -3.5 % (two
 // per lane, 32 chunks) on the same box.  The host applies it only when the launch is ~2 waves per SIMD (wdf_capi_clipper.hip).
+// skew < 0 (K a multiple of kGroupWaves; the group form, where the kGroupWaves consecutive chunks of a workgroup share a CU and
+// the waves w and w + 4 of it a SIMD): in every group of kGroupWaves chunks the first half own L + |skew| steps, the second half
+// L - |skew| -- every SIMD of the workgroup again holds one long chunk, on its older wave, and one short one.
+constexpr int kGroupWaves = 8;      // chunk waves per workgroup of the group form: 2 per SIMD of a CU
 __device__ __forceinline__ void chunk_span(int64_t k, int64_t K, int64_t L, int64_t skew, int64_t T, int64_t& t0, int64_t& t1)
 {
+    if (skew < 0) {
+        const int64_t s = -skew, w = k % kGroupWaves;
+        const bool first = w < kGroupWaves / 2;
+        t0 = k * L + s * (first ? w : kGroupWaves - w);
+        const int64_t len = first ? L + s : L - s;
+        t1 = (t0 + len < T) ? t0 + len : T;
+        return;
+    }
     const int64_t half = K / 2;
     const bool first = k < half;
     t0 = first ? k * (L + skew) : half * (L + skew) + (k - half) * (L - skew);
@@ -575,11 +587,12 @@ struct FusedScale { float L, V; };
 template <typename V, int LOSS, int NSEQ>
 __device__ __forceinline__ void fused_publish_record(float* rec, double* wpart, int64_t k, int64_t K, bool live,
                                                      int slot0, const FusedTan<V>& s, const FusedSums<V>& d, float hgs,
-                                                     FusedScale fsc = FusedScale{1.0f, 1.0f})
+                                                     FusedScale fsc = FusedScale{1.0f, 1.0f}, float4* lds_rec = nullptr,
+                                                     double* lds_part = nullptr)
 {
     constexpr int NREC = FusedRec<LOSS>::N, NP = FusedRec<LOSS>::NP, NQ = FusedQuads<NSEQ, LOSS>::NQ;
     const double inv = hgs != 0.0f ? 1.0 / (double)hgs : 0.0;
-    const uint32_t lanes = gridDim.x * 64u, lane = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t lanes = gridDim.x * 64u, lane = blockIdx.x * 64u + (threadIdx.x & 63u);
     float* chunk = rec_chunk(rec, k);
     float f[NQ * 4];
 #pragma unroll
@@ -606,7 +619,10 @@ __device__ __forceinline__ void fused_publish_record(float* rec, double* wpart, 
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             const double t = wave_sum_dpp(live ? p[i] : 0.0);
-            if (threadIdx.x == 0) __hip_atomic_store(w + i, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((threadIdx.x & 63u) == 0) {
+                __hip_atomic_store(w + i, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lds_part != nullptr) lds_part[(slot0 + j) * NP + i] = t;       // (the group form: the workgroup's wave 0 adds them up)
+            }
         }
     }
     if constexpr (VT<V>::N == NSEQ) {
@@ -615,11 +631,23 @@ __device__ __forceinline__ void fused_publish_record(float* rec, double* wpart, 
         for (int q = 0; q < NQ; ++q) {
             const float g[4] = {f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]};
             publish_quad(rs, lane * 16u, (uint32_t)q * lanes * 16u, g);
+            if (lds_rec != nullptr) lds_rec[q * 64 + (threadIdx.x & 63u)] = float4{g[0], g[1], g[2], g[3]};
         }
     }
 }
 
+// The group form's hand-over inside a workgroup (clipper_fused_tp_kernel, `G` chunk waves to a workgroup): what a chunk wave
+// leaves in LDS for the workgroup's wave 0 -- its record as it went to memory, the state it entered its owned span with, its
+// end state, its own sums.
+template <int NSEQ, int LOSS> struct GroupStage {
+    static constexpr int NQ = FusedQuads<NSEQ, LOSS == 2 ? 2 : 1>::NQ, NP = FusedRec<LOSS>::NP;
+    float4 rec[NQ][64];
+    float zin[NSEQ][64], zend[NSEQ][64];
+    double part[NSEQ * NP];
+};
+
 // Chunk geometry as clipper_fwd_tp_body (L, W multiples of kTile); target [T][B]; skip: steps below it carry no loss.
+// k of K: the wave's chunk (the kernels say which: a workgroup may hold several chunk waves).
 // LOSS = 0: the plain time-parallel forward (no target, no tangent, no record; STASH: the state before every step goes to
 // zstash [T][B] for the reverse sweep) -- clipper_fwd_tp_kernel below runs this same body.
 template <int DYN_R, bool SYM, bool TM, bool VEC4, int FAST, typename V, int LOSS, bool STASH = false>
@@ -627,8 +655,8 @@ __device__ __forceinline__ void clipper_fused_body(
     const ClipConsts& c_in, const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ target,
     float* __restrict__ y, float* __restrict__ zstash, const float* __restrict__ z0, float* __restrict__ zT, float* __restrict__ zwarm,
     float* __restrict__ zend, float* rec, const float* __restrict__ theta, const TpCtl* __restrict__ ctl,
-    float* __restrict__ snap, int J, int64_t B, int64_t T, int64_t L, int64_t W, float hgs, int64_t skip, int64_t skew = 0,
-    double* wpart = nullptr)
+    float* __restrict__ snap, int J, int64_t B, int64_t T, int64_t L, int64_t W, float hgs, int64_t skip, int64_t k, int64_t K,
+    int64_t skew = 0, double* wpart = nullptr, GroupStage<VT<V>::N, LOSS>* gs = nullptr)
 {
     constexpr int NR = FusedTile<V, DYN_R>::NR;
 #ifdef WDF_DBG_TIMES
@@ -638,7 +666,6 @@ __device__ __forceinline__ void clipper_fused_body(
     const LaneOwn<V> q(B);
     // (DYN_R = 2: the lane's sequences' pot values, read once -- their first sample -- and calc_impedance's result with them)
     const ClipConstsSeq<V> c = make_seq_consts<DYN_R, V>(c_in, DYN_R == 2 ? load_step<V, TM>(r, q, B, T, 0) : vsplat<V>(1.0f));
-    const int64_t k = blockIdx.y, K = gridDim.y;
     int64_t t0, t1;
     chunk_span(k, K, L, skew, T, t0, t1);
     int64_t tw = 0;
@@ -650,7 +677,7 @@ __device__ __forceinline__ void clipper_fused_body(
     TpCtl c0 = {};
     if (ctl != nullptr) c0 = *ctl;
     __builtin_amdgcn_sched_barrier(0);
-    const bool stateful = ctl != nullptr && c0.geom == tp_geom_tag(K, J, skew != 0);
+    const bool stateful = ctl != nullptr && c0.geom == tp_geom_tag(K, J, tp_span_scheme(skew));
     const int valid = stateful ? c0.valid : 0;
     const int head = stateful ? c0.head : 0;
     const bool warm_start = k > 0 && valid > 0 && !(stateful && c0.cold_hold > 0);   // (cold_hold: tp_publish_status_and_steer)
@@ -718,6 +745,10 @@ __device__ __forceinline__ void clipper_fused_body(
     dbg_p[2] = __builtin_amdgcn_s_memtime();
 #endif
     publish_own<V>(zwarm + k * B, q, z);
+    if (gs != nullptr) {
+#pragma unroll
+        for (int j = 0; j < VT<V>::N; ++j) gs->zin[j][threadIdx.x & 63u] = vget(z, j);
+    }
     wait_vmcnt<0>();
 #ifdef WDF_DBG_TIMES
     dbg_p[3] = __builtin_amdgcn_s_memtime();
@@ -797,17 +828,22 @@ __device__ __forceinline__ void clipper_fused_body(
     }
     d.template flush<LOSS>(s);
     publish_own<V>(zend + k * B, q, z);
+    if (gs != nullptr) {
+#pragma unroll
+        for (int j = 0; j < VT<V>::N; ++j) gs->zend[j][threadIdx.x & 63u] = vget(z, j);
+    }
     if (snapw != nullptr) store_own<V>(snapw, q, z);
     if (zT && t1 == T) store_own<V>(zT, q, z);
     if constexpr (LOSS != 0) {
         FusedScale fsc{1.0f, 1.0f};
         if constexpr (SYM && FAST == kRootLean && !DYN_R) fsc = FusedScale{-(c.d.two_v * c.d.m_dn), -1.0f / c.V};
-        fused_publish_record<V, LOSS, VT<V>::N>(rec, wpart, k, K, q.live, 0, s, d, hgs, fsc);
+        fused_publish_record<V, LOSS, VT<V>::N>(rec, wpart, k, K, q.live, 0, s, d, hgs, fsc, gs != nullptr ? &gs->rec[0][0] : nullptr,
+                                                gs != nullptr ? gs->part : nullptr);
     }
 #ifdef WDF_DBG_TIMES
     dbg_p[4] = __builtin_amdgcn_s_memtime();
-    if (threadIdx.x == 0 && g_dbg_times) {
-        unsigned long long* o = g_dbg_times + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+    if ((threadIdx.x & 63u) == 0 && g_dbg_times) {
+        unsigned long long* o = g_dbg_times + 8 * ((size_t)k * gridDim.x + blockIdx.x);
         o[2] = dbg_wait;
         o[4] = dbg_p[1] - dbg_p[0]; o[5] = dbg_p[2] - dbg_p[1]; o[6] = dbg_p[3] - dbg_p[2]; o[7] = dbg_p[4] - dbg_p[3];
     }
@@ -972,61 +1008,180 @@ __device__ __forceinline__ void fused_combine_tile(float* rec, double* wpart, in
     }
 }
 
+// ---- the group form: the chunk waves of a workgroup combine in LDS ----------------------------------------------------------
+// With G = min(kGroupWaves, K) consecutive chunks of a tile in one workgroup (at two waves per SIMD that is one CU: the same
+// occupancy as G workgroups of one wave), what the finish launch re-read from memory a microsecond after the chunk waves had it
+// in registers crosses through LDS instead: G - 1 of every G chunk boundaries are verified and the G records composed, in time
+// order and in double, into ONE record of the existing format by the workgroup's wave 0 -- to everything downstream a group looks
+// like one chunk of G times the length.  The finish launch (clipper_fused_group_finish_kernel) then has ceil(K / G) records per
+// tile to walk -- one wave, one flight of loads, no LDS phase.
+//   sigma entering chunk j of the group = P_<j sigma_g + q_<j   (P_<j = prod_{i<j} A_i,  q <- q A_j + c_j)
+//   group record {P, q[3], GA_g = sum_j GA_j P_<j, HA_g likewise};  sigma-independent sums: sum_j (G_j + GA_j q_<j)
+// The per-chunk records, sums and boundary states still go to memory: the repair of a missed tile starts from them.
+struct FusedGroupWs { float* rec; double* part; unsigned long long* verdict; };   // [Kg][kFsQuads][lanes] x 16 B, [tiles][Kg][slots][NP], [tiles][Kg] {bad pairs, largest miss}
+
+template <int NSEQ, int LOSS>
+__device__ __forceinline__ void fused_group_compose(const GroupStage<NSEQ, LOSS>* st, int n, int64_t g, int64_t Kg, int64_t B, float tol,
+                                                    const FusedGroupWs& gw)
+{
+    constexpr int NREC = FusedRec<LOSS>::N, NP = FusedRec<LOSS>::NP, NQ = FusedQuads<NSEQ, LOSS>::NQ;
+    const uint32_t lane = threadIdx.x;                      // (the workgroup's wave 0)
+    const bool live = ((int64_t)blockIdx.x * 64 + lane) * NSEQ < B;
+    double P[NSEQ], q[NSEQ][3], GAg[NSEQ], HAg[NSEQ], e[NSEQ][3], f[NSEQ][3];
+#pragma unroll
+    for (int h = 0; h < NSEQ; ++h) {
+        P[h] = 1.0; GAg[h] = HAg[h] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) q[h][i] = e[h][i] = f[h][i] = 0.0;
+    }
+    float miss = 0.0f;
+    int nbad = 0;
+#pragma unroll
+    for (int j = 0; j < kGroupWaves; ++j) {
+        if (j >= n) break;                                  // wave-uniform
+        float4 t[NQ];
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) t[i] = st[j].rec[i][lane];
+        auto el = [&](int i) { const float4& u = t[i / 4]; return i % 4 == 0 ? u.x : (i % 4 == 1 ? u.y : (i % 4 == 2 ? u.z : u.w)); };
+#pragma unroll
+        for (int h = 0; h < NSEQ; ++h) {
+            const double A = el(h * NREC), GA = el(h * NREC + 4);
+            GAg[h] += GA * P[h];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) e[h][i] += GA * q[h][i];
+            if constexpr (LOSS == 2) {
+                const double HA = el(h * NREC + 5);
+                HAg[h] += HA * P[h];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) f[h][i] += HA * q[h][i];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) q[h][i] = A * q[h][i] + (double)el(h * NREC + 1 + i);
+            P[h] *= A;
+            if (j > 0) {                                    // the boundary in front of chunk j: as the finish launch checks it
+                const float m = fabsf(st[j].zin[h][lane] - st[j - 1].zend[h][lane]);
+                miss = fmaxf(miss, m);
+                nbad += !(m <= tol) ? 1 : 0;                // NaN counts as bad
+            }
+        }
+    }
+    // the group's record, rounded once
+    const uint32_t lanes = gridDim.x * 64u, rl = blockIdx.x * 64u + lane;
+    float o[NQ * 4];
+#pragma unroll
+    for (int i = 0; i < NQ * 4; ++i) o[i] = 0.0f;
+#pragma unroll
+    for (int h = 0; h < NSEQ; ++h) {
+        o[h * NREC] = (float)P[h];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o[h * NREC + 1 + i] = (float)q[h][i];
+        o[h * NREC + 4] = (float)GAg[h];
+        if constexpr (LOSS == 2) o[h * NREC + 5] = (float)HAg[h];
+    }
+    const __amdgpu_buffer_rsrc_t rs = row_rsrc(rec_chunk(gw.rec, g));
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        const float t[4] = {o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]};
+        publish_quad(rs, rl * 16u, (uint32_t)i * lanes * 16u, t);
+    }
+    // the group's own sums: the chunk waves' in wave order, then what the tangent entering each chunk from INSIDE the group adds
+    double* w = gw.part + (((int64_t)blockIdx.x * Kg + g) * NSEQ) * NP;
+#pragma unroll
+    for (int h = 0; h < NSEQ; ++h) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            double t = 0.0;
+            for (int j = 0; j < n; ++j) t += st[j].part[h * NP + i];
+            if (i % 4 != 3) t += wave_sum_dpp(live ? (i < 4 ? e[h][i] : f[h][i - 4]) : 0.0);
+            if (lane == 0) __hip_atomic_store(w + h * NP + i, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    const float wmax = wave_max_dpp(miss);
+    const int wbad = wave_sum_dpp(nbad);
+    if (lane == 0)
+        __hip_atomic_store(gw.verdict + (int64_t)blockIdx.x * Kg + g, (unsigned long long)(unsigned)wbad | ((unsigned long long)__float_as_uint(wmax) << 32),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // tickets: the forward's verification area [TpAcc][per-tile tickets][per-tile repair flags];
 // gticket: [tiles combined, 0, 0, 0] -- both zero before the first launch and left zero by every step.
-// A tile is the 64 * VT<V>::N sequences of one wave.
+// A tile is the 64 * VT<V>::N sequences of one wave.  blockDim.x / 64 = G chunk waves to a workgroup, grid (tiles, ceil(K / G)):
+// wave w of workgroup (tile, g) owns chunk g G + w.  form 0: the tile's last chunk wave finishes the tile (G = 1); 1: the chunk
+// waves are done after their body (G = 1; clipper_fused_finish_kernel behind); 2: the group form (above; dynamic LDS:
+// G x sizeof(GroupStage); clipper_fused_group_finish_kernel behind).
+constexpr int kFusedInKernel = 0, kFusedFinishLater = 1, kFusedGroup = 2;
 template <int DYN_R, bool SYM, bool TM, bool VEC4, typename V, int LOSS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WDF_FUSED_WAVES, WDF_FUSED_WAVES))) void clipper_fused_tp_kernel(
+__global__ __launch_bounds__(64 * kGroupWaves) __attribute__((amdgpu_waves_per_eu(WDF_FUSED_WAVES, WDF_FUSED_WAVES))) void clipper_fused_tp_kernel(
     const float* __restrict__ x, const float* __restrict__ r, const float* theta, float fs, int n_up, int n_down,
     const float* __restrict__ target, float hgs, int64_t skip, float* __restrict__ y, const float* __restrict__ z0,
     float* __restrict__ zT, float* zwarm, float* zend, float* rec, TpStatus* __restrict__ status, TpCtl* ctl, float* snap,
-    int J, unsigned* tickets, unsigned* gticket, float tol, int64_t B, int64_t T, int64_t L, int64_t W, int general,
-    double* ws, FusedOut out, int64_t skew, double* wpart, int finish_later)
+    int J, unsigned* tickets, unsigned* gticket, float tol, int64_t B, int64_t T, int64_t K, int64_t L, int64_t W, int general,
+    double* ws, FusedOut out, int64_t skew, double* wpart, int form, FusedGroupWs gw)
 {
+    constexpr bool WIN = fused_x_window<DYN_R, TM, VEC4>();   // (x through a per-workgroup window in LDS: one chunk wave to a workgroup)
     double (*sh)[4];                                        // the in-kernel tail's scratch; where x has a window in LDS, inside it
-    if constexpr (fused_x_window<DYN_R, TM, VEC4>()) {
+    if constexpr (WIN) {
         sh = reinterpret_cast<double (*)[4]>(wave_lds<XWindow<V, true>::kFloats>());
     } else {
         __shared__ double sh_own[64][4];
         sh = sh_own;
     }
+    extern __shared__ __attribute__((aligned(16))) unsigned char fused_group_lds[];
+    typedef GroupStage<VT<V>::N, LOSS> Stage;
+    // (w through v_readfirstlane: the chunk index and everything formed from it stay in SGPRs)
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), G = (int)(blockDim.x >> 6);
+    const int64_t k = (int64_t)blockIdx.y * G + w;
+    Stage* gs = nullptr;
+    if constexpr (!WIN) { if (form == kFusedGroup) gs = reinterpret_cast<Stage*>(fused_group_lds) + w; }
 #ifdef WDF_DBG_TIMES
     const unsigned long long dbg_t0 = wall_clock64();
     const unsigned long long dbg_m0 = __builtin_amdgcn_s_memtime();
 #endif
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { status->fallback_ran = 0; status->pad = 0u; }   // (the repair launch counts)
-    const ClipConsts c = load_consts(theta, fs, n_up, n_down);
-    const int tier = root_tier<DYN_R, SYM>(c, general);
-    bool ran = false;
-    if constexpr (SYM && DYN_R != 1) {
-        if (tier == kRootLean) {
-            clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootLean, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
-                                                                         J, B, T, L, W, hgs, skip, skew, wpart);
-            ran = true;
+    if (k < K) {                                            // (a ragged last group: its spare waves only meet the barrier below)
+        const ClipConsts c = load_consts(theta, fs, n_up, n_down);
+        const int tier = root_tier<DYN_R, SYM>(c, general);
+        bool ran = false;
+        if constexpr (SYM && DYN_R != 1) {
+            if (tier == kRootLean) {
+                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootLean, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
+                                                                             J, B, T, L, W, hgs, skip, k, K, skew, wpart, gs);
+                ran = true;
+            }
+        }
+        if (!ran) {
+            if (tier != kRootGeneral)
+                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootFast, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
+                                                                             J, B, T, L, W, hgs, skip, k, K, skew, wpart, gs);
+            else
+                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootGeneral, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl,
+                                                                                snap, J, B, T, L, W, hgs, skip, k, K, skew, wpart, gs);
+        }
+#ifdef WDF_DBG_TIMES
+        if ((threadIdx.x & 63u) == 0 && g_dbg_times) {
+            unsigned long long* dbg_o = g_dbg_times + 8 * ((size_t)k * gridDim.x + blockIdx.x);
+            dbg_o[0] = dbg_t0; dbg_o[1] = wall_clock64(); dbg_o[3] = __builtin_amdgcn_s_memtime() - dbg_m0;
+#ifdef WDF_DBG_HWID                                          // where the wave ran instead of its back-edge wait: HW_ID | XCC_ID << 32
+            dbg_o[2] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
+                       ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
+#endif
+        }
+#endif
+    }
+    if constexpr (!WIN) {
+        if (form == kFusedGroup) {
+            __syncthreads();                                // the workgroup's records, states and sums are in LDS
+            if (w != 0) return;
+            const int64_t left = K - (int64_t)blockIdx.y * G;
+            fused_group_compose<VT<V>::N, LOSS>(reinterpret_cast<const Stage*>(fused_group_lds), (int)(left < G ? left : G), blockIdx.y, gridDim.y,
+                                                B, tol, gw);
+            return;
         }
     }
-    if (!ran) {
-        if (tier != kRootGeneral)
-            clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootFast, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
-                                                                         J, B, T, L, W, hgs, skip, skew, wpart);
-        else
-            clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootGeneral, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl,
-                                                                            snap, J, B, T, L, W, hgs, skip, skew, wpart);
-    }
-#ifdef WDF_DBG_TIMES
-    if (threadIdx.x == 0 && g_dbg_times) {
-        unsigned long long* dbg_o = g_dbg_times + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-        dbg_o[0] = dbg_t0; dbg_o[1] = wall_clock64(); dbg_o[3] = __builtin_amdgcn_s_memtime() - dbg_m0;
-#ifdef WDF_DBG_HWID                                          // where the wave ran instead of its back-edge wait: HW_ID | XCC_ID << 32
-        dbg_o[2] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
-                   ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
-#endif
-    }
-#endif
     WDF_DBG_STAMP(0);
-    // finish_later (round 6, the default): the chunk waves are done here -- no drain, no tile ticket -- and the launch behind this
+    // kFusedFinishLater (round 6): the chunk waves are done here -- no drain, no tile ticket -- and the launch behind this
     // one (clipper_fused_finish_kernel) verifies, repairs, combines and finishes the step with several waves per tile
-    if (finish_later) return;
+    if (form != kFusedInKernel) return;
     if (!tp_tile_last(tickets)) return;
     WDF_DBG_STAMP(1);
     // the tile adds its verification result to the accumulators; the status word and the warm-start steering are left to
@@ -1034,7 +1189,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WDF_FUSED_WA
     const bool failed = tp_verify_tile<DYN_R, VT<V>::N, true>(theta, zwarm, zend, status, ctl, J, tickets, tol, B, L, W);
     WDF_DBG_STAMP(2);
     if (failed) return;                                     // left to clipper_fused_repair_kernel
-    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, (int64_t)gridDim.y, L, W, skew != 0};
+    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, (int64_t)gridDim.y, L, W, tp_span_scheme(skew)};
     fused_combine_tile<VT<V>::N, LOSS>(rec, wpart, gridDim.y, B, ws, gticket, theta, fs, DYN_R ? 1 : 0, out, sh);
 }
 
@@ -1065,17 +1220,17 @@ __global__ __launch_bounds__(64) void clipper_fwd_tp_kernel(
     if constexpr (SYM && DYN_R != 1) {
         if (tier == kRootLean) {
             clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootLean, V, 0, STASH>(c, x, r, nullptr, y, zstash, z0, zT, zwarm, zend, nullptr, theta,
-                                                                             ctl, snap, J, B, T, L, W, 0.0f, 0);
+                                                                             ctl, snap, J, B, T, L, W, 0.0f, 0, blockIdx.y, gridDim.y);
             ran = true;
         }
     }
     if (!ran) {
         if (tier != kRootGeneral)
             clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootFast, V, 0, STASH>(c, x, r, nullptr, y, zstash, z0, zT, zwarm, zend, nullptr, theta,
-                                                                             ctl, snap, J, B, T, L, W, 0.0f, 0);
+                                                                             ctl, snap, J, B, T, L, W, 0.0f, 0, blockIdx.y, gridDim.y);
         else
             clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootGeneral, V, 0, STASH>(c, x, r, nullptr, y, zstash, z0, zT, zwarm, zend, nullptr, theta,
-                                                                                ctl, snap, J, B, T, L, W, 0.0f, 0);
+                                                                                ctl, snap, J, B, T, L, W, 0.0f, 0, blockIdx.y, gridDim.y);
     }
 #ifdef WDF_DBG_TIMES                                         // (tools/dbg_fwd_times.py: the wave's start, the end of its body, where it ran)
     if (threadIdx.x == 0 && g_dbg_times) {
@@ -1154,7 +1309,7 @@ __global__ __launch_bounds__(64) void clipper_fused_repair_kernel(
     // The ring slot the step wrote its snapshots to.  The control block is advanced by the wave that FINISHES the step, and with
     // a flagged tile that wave is the last of THIS launch's blocks to combine -- after every block has read this:
     int slot = 0;
-    if (ctl != nullptr && snap != nullptr) slot = ((ctl->geom == tp_geom_tag(K, J, skew != 0) ? ctl->head : 0) + 1) % kTpRing;
+    if (ctl != nullptr && snap != nullptr) slot = ((ctl->geom == tp_geom_tag(K, J, tp_span_scheme(skew)) ? ctl->head : 0) + 1) % kTpRing;
     int nrep = 0;
 #pragma unroll 1
     for (int h = 0; h < NSEQ; ++h) {
@@ -1193,7 +1348,7 @@ __global__ __launch_bounds__(64) void clipper_fused_repair_kernel(
         if (nrep) atomicAdd(&status->fallback_ran, nrep);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the re-written records have landed (write-through)
-    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, K, L, W, skew != 0};
+    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, K, L, W, tp_span_scheme(skew)};
     fused_combine_tile<NSEQ, LOSS>(rec, wpart, K, B, ws, gticket, theta, fs, DYN_R ? 1 : 0, out, sh);
 }
 
@@ -1217,6 +1372,60 @@ __global__ __launch_bounds__(64) void clipper_fused_repair_kernel(
 //     reduces, applies the chain rule, publishes the status, steers the warm start and runs Adam.
 // Measured on the trial of round 5 (profiles/README.md): the one-pass kernel without its tail runs 0.089-0.090 ms instead of
 // 0.107-0.109; the serial tail as a second launch cost 19 us and gave all of it back.
+
+// The rare path of a finish launch: one wave re-runs, in time order, every chunk of its tile that was entered more than tol off
+// (clipper_fused_repair_kernel's walk: from the exact state, one sequence per lane -- outputs, snapshots, records, sums), behind
+// the kernel boundary: the re-run rewrites rows that waves on another XCD wrote.
+template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS>
+__device__ __forceinline__ void fused_repair_tile(
+    const float* __restrict__ x, const float* __restrict__ r, const float* theta, float fs, int n_up, int n_down,
+    const float* __restrict__ target, float hgs, int64_t skip, float* __restrict__ y, float* __restrict__ zT, const float* zwarm,
+    float* zend, float* rec, int64_t B, int64_t T, int64_t K, int64_t L, float tol, TpStatus* __restrict__ status, TpCtl* ctl,
+    float* __restrict__ snap, int J, int general, int64_t skew, double* wpart, int64_t b_first, bool live, int lane)
+{
+    const ClipConsts c = load_consts(theta, fs, n_up, n_down);
+    const int tier = root_tier<DYN_R, SYM>(c, general);
+    // the ring slot the step wrote its snapshots to (the control block is advanced by the wave that finishes the step:
+    // the last of this launch's tiles through the ticket below -- after every tile has read this)
+    int slot = 0;
+    if (ctl != nullptr && snap != nullptr) slot = ((ctl->geom == tp_geom_tag(K, J, tp_span_scheme(skew)) ? ctl->head : 0) + 1) % kTpRing;
+    int nrep = 0;
+#pragma unroll 1
+    for (int h = 0; h < NSEQ; ++h) {
+        const int64_t b = b_first + h;
+        bool fixed_prev = false;
+        float ze_fix = 0.0f;
+        for (int64_t k = 1; k < K; ++k) {
+            const float e = fixed_prev ? ze_fix : load_published(zend + (k - 1) * B + b);
+            const float m = fabsf(load_published(zwarm + k * B + b) - e);
+            fixed_prev = false;
+            if (__builtin_amdgcn_ballot_w64(!(m <= tol)) == 0) continue;
+            int64_t t0, t1;
+            chunk_span(k, K, L, skew, T, t0, t1);
+            float* __restrict__ snapw = (snap != nullptr && k + 1 < K) ? snap + ((int64_t)slot * J * K + k) * B : nullptr;
+            float z = e;
+            bool ran = false;
+            if constexpr (SYM && DYN_R != 1) {
+                if (tier == kRootLean) {
+                    fused_rerun_chunk<DYN_R, SYM, TM, kRootLean, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
+                    ran = true;
+                }
+            }
+            if (!ran) {
+                if (tier != kRootGeneral) fused_rerun_chunk<DYN_R, SYM, TM, kRootFast, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
+                else fused_rerun_chunk<DYN_R, SYM, TM, kRootGeneral, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
+            }
+            __hip_atomic_store(zend + k * B + b, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (zT && t1 == T) zT[b] = z;
+            ze_fix = z;
+            fixed_prev = true;
+            ++nrep;
+        }
+    }
+    if (lane == 0 && nrep) atomicAdd(&status->fallback_ran, nrep);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the re-written records have landed (write-through)
+}
+
 #ifdef WDF_DBG_TIMES      // tools/dbg_fin_times.py: wall-clock stamps of every tile's wave 0 along the finish launch: [8 tiles K + 8 tile + i]
 #define WDF_FIN_STAMP(i)                                                                                      \
     do { if (threadIdx.x == 0 && g_dbg_times) g_dbg_times[8 * ((size_t)gridDim.x * (size_t)K) + 8 * (size_t)blockIdx.x + (i)] = wall_clock64(); } while (0)
@@ -1357,47 +1566,8 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     if (tile_bad_pairs != 0) {
         // ---- the rare path: wave 0 re-runs the chunks that were entered off (clipper_fused_repair_kernel's walk)
         if (w == 0) {
-            const ClipConsts c = load_consts(theta, fs, n_up, n_down);
-            const int tier = root_tier<DYN_R, SYM>(c, general);
-            // the ring slot the step wrote its snapshots to (the control block is advanced by the wave that finishes the step:
-            // the last of this launch's tiles through the ticket below -- after every tile has read this)
-            int slot = 0;
-            if (ctl != nullptr && snap != nullptr) slot = ((ctl->geom == tp_geom_tag(K, J, skew != 0) ? ctl->head : 0) + 1) % kTpRing;
-            int nrep = 0;
-#pragma unroll 1
-            for (int h = 0; h < NSEQ; ++h) {
-                const int64_t b = b_first + h;
-                bool fixed_prev = false;
-                float ze_fix = 0.0f;
-                for (int64_t k = 1; k < K; ++k) {
-                    const float e = fixed_prev ? ze_fix : load_published(zend + (k - 1) * B + b);
-                    const float m = fabsf(load_published(zwarm + k * B + b) - e);
-                    fixed_prev = false;
-                    if (__builtin_amdgcn_ballot_w64(!(m <= tol)) == 0) continue;
-                    int64_t t0, t1;
-                    chunk_span(k, K, L, skew, T, t0, t1);
-                    float* __restrict__ snapw = (snap != nullptr && k + 1 < K) ? snap + ((int64_t)slot * J * K + k) * B : nullptr;
-                    float z = e;
-                    bool ran = false;
-                    if constexpr (SYM && DYN_R != 1) {
-                        if (tier == kRootLean) {
-                            fused_rerun_chunk<DYN_R, SYM, TM, kRootLean, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
-                            ran = true;
-                        }
-                    }
-                    if (!ran) {
-                        if (tier != kRootGeneral) fused_rerun_chunk<DYN_R, SYM, TM, kRootFast, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
-                        else fused_rerun_chunk<DYN_R, SYM, TM, kRootGeneral, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
-                    }
-                    __hip_atomic_store(zend + k * B + b, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (zT && t1 == T) zT[b] = z;
-                    ze_fix = z;
-                    fixed_prev = true;
-                    ++nrep;
-                }
-            }
-            if (lane == 0 && nrep) atomicAdd(&status->fallback_ran, nrep);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the re-written records have landed (write-through)
+            fused_repair_tile<DYN_R, SYM, TM, NSEQ, LOSS>(x, r, theta, fs, n_up, n_down, target, hgs, skip, y, zT, zwarm, zend, rec, B, T, K, L, tol,
+                                                          status, ctl, snap, J, general, skew, wpart, b_first, live, lane);
         }
         __syncthreads();
         load_batch(k0);                                        // (agent-scope loads: past this CU's L1)
@@ -1477,11 +1647,167 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     for (int ww = 0; ww < NW; ++ww)
 #pragma unroll
         for (int i = 0; i < (LOSS == 2 ? 8 : 4); ++i) tot[i] += s_sum[ww][i];
-    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, K, L, W, skew != 0};
+    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, K, L, W, tp_span_scheme(skew)};
     WDF_FIN_STAMP(4);
     if constexpr (LOSS == 2) esr_tile_partial_and_finish<true>(tot, ws, gticket, theta, fs, DYN_R ? 1 : 0, out);
     else tile_partial_and_finish<true>(tot[0], tot[1], tot[2], tot[3], ws, gticket, theta, fs, DYN_R ? 1 : 0, out.gtheta, out.accumulate,
                                        out.sse_out, out.adam, sh, out.fc);
+}
+
+// ---- the finish launch of the group form --------------------------------------------------------------------------------------
+// One wave per tile.  The chunk kernel's workgroups left Kg = ceil(K / G) group records per tile, the groups' own sums and their
+// verdicts on the boundaries inside them; what is left to verify are the Kg - 1 boundaries BETWEEN groups.  All of it -- records,
+// sums, verdicts, boundaries -- is requested in one flight; a tile without a miss walks its Kg records (4 at 32 chunks: one register
+// batch; 16 at 128: two) and hands its totals to tile_partial_and_finish / esr_tile_partial_and_finish.  A tile with a miss, inside a
+// group or between two, takes the parent's rare path: fused_repair_tile, then the combine of the re-written PER-CHUNK records
+// (fused_combine_tile: the arithmetic of the in-kernel form).
+constexpr int kGrpBatch = 8;        // group records in registers at a time (loaded in quarters of 2)
+
+template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS>
+__global__ __launch_bounds__(64) void clipper_fused_group_finish_kernel(
+    const float* __restrict__ x, const float* __restrict__ r, const float* theta, float fs, int n_up, int n_down,
+    const float* __restrict__ target, float hgs, int64_t skip, float* __restrict__ y, float* __restrict__ zT,
+    const float* zwarm, float* zend, float* rec, int64_t B, int64_t T, int64_t K, int64_t L, float tol,
+    TpStatus* __restrict__ status, TpCtl* ctl, float* __restrict__ snap, int J, unsigned* tickets,
+    unsigned* gticket, int general, double* ws, FusedOut out, int64_t skew, double* wpart, int64_t W, int G, FusedGroupWs gw)
+{
+    constexpr int NREC = FusedRec<LOSS>::N, NP = FusedRec<LOSS>::NP, NQ = FusedQuads<NSEQ, LOSS>::NQ;
+    constexpr int NWQ = NSEQ * NP / 2;                     // 16-byte loads of a group's own sums
+    __shared__ double sh[64][4];
+    const int lane = threadIdx.x;
+    const int64_t Kg = (K + G - 1) / G;
+    const int64_t raw = ((int64_t)blockIdx.x * 64 + lane) * NSEQ;
+    const bool live = raw < B;
+    const int64_t b_first = live ? raw : B - NSEQ;
+    const uint32_t lanes = gridDim.x * 64u, rl = blockIdx.x * 64u + (uint32_t)lane;
+    WDF_FIN_STAMP(0);
+    // ---- one flight: the first batch of group records, the groups' sums and verdicts, the boundaries between groups
+    v4u g[kGrpBatch][NQ];
+    auto load_quarter = [&](int64_t kb, auto J0) {
+#pragma unroll
+        for (int j = decltype(J0)::value; j < decltype(J0)::value + kGrpBatch / 4; ++j) {
+            const int64_t k = (kb + j < Kg) ? kb + j : Kg - 1;
+            const __amdgpu_buffer_rsrc_t rs = row_rsrc(rec_chunk(gw.rec, k));
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) g[j][q] = load_published_quad(rs, rl * 16u, (uint32_t)q * lanes * 16u);
+        }
+    };
+    auto load_batch = [&](int64_t kb) {
+        load_quarter(kb, std::integral_constant<int, 0>{});
+        if (kb + kGrpBatch / 4 < Kg) load_quarter(kb, std::integral_constant<int, kGrpBatch / 4>{});
+        if (kb + kGrpBatch / 2 < Kg) {
+            load_quarter(kb, std::integral_constant<int, kGrpBatch / 2>{});
+            load_quarter(kb, std::integral_constant<int, 3 * kGrpBatch / 4>{});
+        }
+    };
+    load_batch(0);
+    const __amdgpu_buffer_rsrc_t rw = row_rsrc(reinterpret_cast<float*>(gw.part + (int64_t)blockIdx.x * Kg * NSEQ * NP));
+    v4u wq[NWQ];
+    auto load_part = [&](int64_t kk) {                      // lane i: group kk (clamped, unused past the last)
+        const uint32_t kc = (uint32_t)(kk < Kg ? kk : Kg - 1);
+#pragma unroll
+        for (int i = 0; i < NWQ; ++i) wq[i] = load_published_quad(rw, kc * (uint32_t)(NSEQ * NP * 8) + 16u * i, 0);
+    };
+    load_part(lane);
+    float miss = 0.0f;
+    int nbad = 0;
+    for (int64_t kk = lane; kk < Kg; kk += 64) {            // the groups' verdicts: lane i takes group i
+        const unsigned long long v = __hip_atomic_load(gw.verdict + (int64_t)blockIdx.x * Kg + kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        nbad += (int)(unsigned)v;
+        miss = fmaxf(miss, __uint_as_float((unsigned)(v >> 32)));
+    }
+    constexpr int kBnd = 8;                                 // boundaries between groups checked together
+    for (int64_t g0 = 1; g0 < Kg; g0 += kBnd) {
+        float zw[kBnd][NSEQ], ze[kBnd][NSEQ];
+#pragma unroll
+        for (int j = 0; j < kBnd; ++j) {
+            const int64_t k = ((g0 + j < Kg) ? g0 + j : Kg - 1) * G;     // the first chunk of group g0 + j (clamped: re-reads the last)
+            load_published_row<NSEQ>(zwarm + k * B, (uint32_t)b_first * 4u, zw[j]);
+            load_published_row<NSEQ>(zend + (k - 1) * B, (uint32_t)b_first * 4u, ze[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kBnd; ++j)
+#pragma unroll
+            for (int h = 0; h < NSEQ; ++h) {
+                const float m = fabsf(zw[j][h] - ze[j][h]);
+                if (g0 + j < Kg) {
+                    miss = fmaxf(miss, m);
+                    nbad += !(m <= tol) ? 1 : 0;            // NaN counts as bad
+                }
+            }
+    }
+    const float tile_miss = wave_max_dpp(miss);
+    const int tile_bad_pairs = wave_sum_dpp(nbad);
+    if (lane == 0) {                                         // the tile's share of the verification totals (tp_verify_tile, DEFER)
+        TpAcc* acc = reinterpret_cast<TpAcc*>(tickets);
+        if (tile_miss > 0.0f) (void)atomicMax(&acc->max_miss_bits, __float_as_int(tile_miss));
+        if (tile_bad_pairs) (void)atomicAdd(&acc->n_bad, (unsigned)tile_bad_pairs);
+    }
+    WDF_FIN_STAMP(1);
+    out.fc = TpFinishCtx{status, ctl, J, tickets, tol, K, L, W, tp_span_scheme(skew)};
+    if (tile_bad_pairs != 0) {
+        fused_repair_tile<DYN_R, SYM, TM, NSEQ, LOSS>(x, r, theta, fs, n_up, n_down, target, hgs, skip, y, zT, zwarm, zend, rec, B, T, K, L, tol,
+                                                      status, ctl, snap, J, general, skew, wpart, b_first, live, lane);
+        fused_combine_tile<NSEQ, LOSS>(rec, wpart, K, B, ws, gticket, theta, fs, DYN_R ? 1 : 0, out, sh);
+        return;
+    }
+    // ---- the walk over the tile's group records, with the sums
+    double sL[NSEQ], sV[NSEQ], sP[NSEQ];                   // (the tangent entering the tile is 0: z0 does not depend on theta)
+#pragma unroll
+    for (int h = 0; h < NSEQ; ++h) sL[h] = sV[h] = sP[h] = 0.0;
+    double dL = 0.0, dV = 0.0, dP = 0.0, dS = 0.0, qL = 0.0, qV = 0.0, qP = 0.0, qE = 0.0;
+    for (int64_t kb = 0; kb < Kg; kb += kGrpBatch) {
+        if (kb > 0) load_batch(kb);
+#pragma unroll
+        for (int j = 0; j < kGrpBatch; ++j) {
+            if (kb + j >= Kg) break;                            // wave-uniform
+            float v[NQ * 4];
+#pragma unroll
+            for (int i = 0; i < NQ * 4; ++i) v[i] = __uint_as_float(g[j][i / 4][i % 4]);
+#pragma unroll
+            for (int h = 0; h < NSEQ; ++h) {
+                const float* rr = v + h * NREC;
+                const double A = rr[0], GA = rr[4];
+                dL += sL[h] * GA;
+                dV += sV[h] * GA;
+                dP += sP[h] * GA;
+                if constexpr (LOSS == 2) {
+                    const double HA = rr[5];
+                    qL += sL[h] * HA;
+                    qV += sV[h] * HA;
+                    qP += sP[h] * HA;
+                }
+                sL[h] = A * sL[h] + (double)rr[1];
+                sV[h] = A * sV[h] + (double)rr[2];
+                sP[h] = A * sP[h] + (double)rr[3];
+            }
+        }
+    }
+    if (!live) { dL = dV = dP = dS = qL = qV = qP = qE = 0.0; }
+    auto add_part = [&]() {                                 // a group's own sums (already masked to the live lanes)
+#pragma unroll
+        for (int h = 0; h < NSEQ; ++h) {
+            double p[NP];
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                const int e = h * NP + i;                     // double e of the group's block = dwords 2e, 2e + 1
+                p[i] = __hiloint2double((int)wq[e / 2][(e % 2) * 2 + 1], (int)wq[e / 2][(e % 2) * 2]);
+            }
+            dL += p[0]; dV += p[1]; dP += p[2]; dS += p[3];
+            if constexpr (LOSS == 2) { qL += p[4]; qV += p[5]; qP += p[6]; qE += p[7]; }
+        }
+    };
+    if (lane < Kg) add_part();                              // lane i: group i
+    for (int64_t kk = lane + 64; kk < Kg; kk += 64) { load_part(kk); add_part(); }   // (more than 64 groups)
+    WDF_FIN_STAMP(3);
+    WDF_FIN_STAMP(4);
+    if constexpr (LOSS == 2) {
+        const double v8[8] = {dL, dV, dP, dS, qL, qV, qP, qE};
+        esr_tile_partial_and_finish(v8, ws, gticket, theta, fs, DYN_R ? 1 : 0, out);
+    } else {
+        tile_partial_and_finish(dL, dV, dP, dS, ws, gticket, theta, fs, DYN_R ? 1 : 0, out.gtheta, out.accumulate, out.sse_out, out.adam, sh,
+                                out.fc);
+    }
 }
 
 }  // namespace wdf

@@ -1,4 +1,5 @@
-"""Per-step timeline of the headline step from a rocprofv3 --kernel-trace run (round 6: chunk kernel + finish launch):
+"""Per-step timeline of the headline step from a rocprofv3 --kernel-trace run (chunk kernel + the launch behind it, whichever
+form ran: clipper_fused_group_finish_kernel, clipper_fused_finish_kernel or clipper_fused_repair_kernel -- its name is printed):
 for the last `n` steps the median of {chunk kernel, gap to the finish launch, finish launch, gap to the next step's chunk kernel}.
 usage: python tools/step_timeline.py <trace dir> [n]"""
 import csv, glob, os, re, statistics, sys
