@@ -1435,6 +1435,33 @@ def _ss_groot(root_kind, device):
     return None if n is None else torch.empty((n,), dtype=torch.float32, device=device)
 
 
+def _ss_check_shapes(who, x, coef, ns, ni, root_kind, rootp, z0=None, zstash=None, gy=None, sweep=False):
+    """What the wdf_ss_* kernels index by (ns, ni, B, T) without the C ABI knowing the arrays' sizes -> (B, T): x holds B T ni values,
+    coef wdf_ss_ncoef(ns, ni); z0 [ns,B]; for a reverse sweep (sweep=True) zstash [T,ns,B] (ns > 0) and gy [T,B]; rootp at least
+    the 3 values the diode pair reads ({Is, nVt, R_port}) or the 5 of two different diodes, and there at all under either root."""
+    ns, ni = int(ns), int(ni)
+    if x.dim() < 2:
+        raise WdfHipError(f"{who}: x must be [B,T,ni] (or [B,T] when ni == 1), got {tuple(x.shape)}")
+    B, T = int(x.shape[0]), int(x.shape[1])
+    if x.numel() != B * T * ni:
+        raise WdfHipError(f"{who}: x has {x.numel()} elements, expected B*T*ni = {B * T * ni}")
+    if coef.numel() != lib().wdf_ss_ncoef(ns, ni):
+        raise WdfHipError(f"{who}: coef must hold {lib().wdf_ss_ncoef(ns, ni)} values for ns={ns}, ni={ni}, got {coef.numel()}")
+    if z0 is not None and ns > 0 and tuple(z0.shape) != (ns, B):
+        raise WdfHipError(f"{who}: z0 must be [ns,B] = [{ns},{B}], got {tuple(z0.shape)}")
+    if sweep:
+        if ns > 0 and (zstash is None or tuple(zstash.shape) != (T, ns, B)):
+            raise WdfHipError(f"{who}: zstash must be [T,ns,B] = [{T},{ns},{B}], got {None if zstash is None else tuple(zstash.shape)}")
+        if gy is None or tuple(gy.shape) != (T, B):
+            raise WdfHipError(f"{who}: gy must be [T,B] = [{T},{B}], got {None if gy is None else tuple(gy.shape)}")
+    need = {ROOT_DIODE_PAIR: 3, ROOT_ASYM_PAIR: 5}.get(int(root_kind), 0)
+    if need and (rootp is None or rootp.numel() < need):
+        raise WdfHipError(f"{who}: rootp must hold {need} values for root kind {int(root_kind)} "
+                          f"({'Is, nVt, R_port' if need == 3 else 'Is_up, nVt_up, Is_down, nVt_down, R_port'}), "
+                          f"got {None if rootp is None else rootp.numel()}")
+    return B, T
+
+
 def ss_fwd(x, coef, ns, ni, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, want_stash=True, z0=None,
            want_zT=False):
     """State-space recursion.  x [B,T,ni] (or [B,T] when ni == 1) -> y [T,B], zstash [T,ns,B] | None,
@@ -1444,11 +1471,7 @@ def ss_fwd(x, coef, ns, ni, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, w
     coef = _f32_dev(coef, "coef")
     rootp = _f32_dev(rootp, "rootp")
     z0 = _f32_dev(z0, "z0")
-    B, T = x.shape[0], x.shape[1]
-    if x.numel() != B * T * ni:
-        raise WdfHipError(f"x has {x.numel()} elements, expected B*T*ni = {B * T * ni}")
-    if coef.numel() != lib().wdf_ss_ncoef(ns, ni):
-        raise WdfHipError(f"coef must hold {lib().wdf_ss_ncoef(ns, ni)} values for ns={ns}, ni={ni}")
+    B, T = _ss_check_shapes("ss_fwd", x, coef, ns, ni, root_kind, rootp, z0=z0)
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, ns, B), dtype=torch.float32, device=x.device) if (want_stash and ns > 0) else None
     zT = torch.empty((ns, B), dtype=torch.float32, device=x.device) if want_zT else None
@@ -1462,9 +1485,7 @@ def ss_fwd_lin_tp(x, coef, ns, ni, n_chunks, want_stash=True, z0=None, want_zT=F
     """Exact chunked forward of a linear tree (root kind NONE); same returns as ss_fwd."""
     require_gpu()
     x, coef, z0 = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(z0, "z0")
-    B, T = x.shape[0], x.shape[1]
-    if x.numel() != B * T * ni or coef.numel() != lib().wdf_ss_ncoef(ns, ni):
-        raise WdfHipError("ss_fwd_lin_tp: x / coef do not match ns, ni")
+    B, T = _ss_check_shapes("ss_fwd_lin_tp", x, coef, ns, ni, ROOT_NONE, None, z0=z0)
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, ns, B), dtype=torch.float32, device=x.device) if want_stash else None
     zT = torch.empty((ns, B), dtype=torch.float32, device=x.device) if want_zT else None
@@ -1483,9 +1504,7 @@ def ss_bwd(x, coef, ns, ni, zstash, gy, root_kind=ROOT_NONE, rootp=None, n_up=1,
     rootp = _f32_dev(rootp, "rootp")
     zstash = _f32_dev(zstash, "zstash")
     gy = _f32_dev(gy, "gy")
-    B, T = x.shape[0], x.shape[1]
-    if tuple(gy.shape) != (T, B):
-        raise WdfHipError(f"gy must be [T,B] = [{T},{B}]")
+    B, T = _ss_check_shapes("ss_bwd", x, coef, ns, ni, root_kind, rootp, zstash=zstash, gy=gy, sweep=True)
     ncoef = lib().wdf_ss_ncoef(ns, ni)
     ws = torch.empty((lib().wdf_ss_bwd_ws_bytes(ns, ni, B),), dtype=torch.uint8, device=x.device)
     gcoef = torch.empty((ncoef,), dtype=torch.float32, device=x.device)
@@ -1515,9 +1534,7 @@ def ss_fwd_tp(x, coef, ns, ni, rootp, n_chunks, warmup, tol=1e-6, n_up=1, n_down
     require_gpu()
     x, coef, rootp, z0 = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(rootp, "rootp"), _f32_dev(z0, "z0")
     zinit = _f32_dev(zinit, "zinit")
-    B, T = x.shape[0], x.shape[1]
-    if x.numel() != B * T * ni or coef.numel() != lib().wdf_ss_ncoef(ns, ni):
-        raise WdfHipError("ss_fwd_tp: x / coef do not match ns, ni")
+    B, T = _ss_check_shapes("ss_fwd_tp", x, coef, ns, ni, root_kind, rootp, z0=z0)
     K = lib().wdf_ss_tp_chunks(T, int(n_chunks))
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, ns, B), dtype=torch.float32, device=x.device) if want_stash else None
@@ -1970,9 +1987,7 @@ def ss_bwd_tp(x, coef, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, rootp=
     require_gpu()
     x, coef, rootp = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(rootp, "rootp")
     zstash, gy = _f32_dev(zstash, "zstash"), _f32_dev(gy, "gy")
-    B, T = x.shape[0], x.shape[1]
-    if tuple(gy.shape) != (T, B):
-        raise WdfHipError(f"gy must be [T,B] = [{T},{B}]")
+    B, T = _ss_check_shapes("ss_bwd_tp", x, coef, ns, ni, root_kind, rootp, zstash=zstash, gy=gy, sweep=True)
     K = lib().wdf_ss_tp_chunks(T, int(n_chunks))
     ncoef = lib().wdf_ss_ncoef(ns, ni)
     ws = torch.empty((lib().wdf_ss_bwd_tp_ws_bytes(ns, ni, B, K),), dtype=torch.uint8, device=x.device)

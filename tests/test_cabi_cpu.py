@@ -236,6 +236,44 @@ def test_state_space_chunked_argument_validation_without_gpu(lib):
             (dict(n_chunks=5), -1, b"does not tile"), (dict(warmup=-1), -1, None)])
 
 
+def test_static_state_space_argument_validation_without_gpu(lib):
+    """wdf_ss_fwd, wdf_ss_bwd, wdf_ss_bwd_tp and wdf_ss_fwd_lin_tp: sizes the kernels are not built for, the two different diodes on
+    four states, diode counts, a root without rootp, no state in the chunked entry points -- refused before any HIP call."""
+    shape = [(dict(ns=5), -3, b"ns in [0,4]"), (dict(ns=-1), -3, None), (dict(ni=3), -3, b"ni in [1,2]"), (dict(ni=0), -3, None),
+             (dict(B=0), -1, None), (dict(T=0), -1, None), (dict(x=None), -1, b"null"), (dict(coef=None), -1, b"null")]
+    rooted = [(dict(root=4, ns=4), -3, b"at most 3 states"), (dict(root=2, n_up=17), -1, b"[1,16]"), (dict(root=2, n_down=0), -1, b"[1,16]"),
+              (dict(root=2, rootp=None), -1, b"rootp"), (dict(root=4, rootp=None), -1, b"rootp"), (dict(root=1), -1, b"unknown root"),
+              (dict(root=3), -1, b"unknown root")]
+    fwd = "x coef rootp ns ni root n_up n_down y zstash z0 zT B T flags stream".split()
+    good = dict(x=ONE, coef=ONE, rootp=ONE, ns=2, ni=1, root=0, n_up=1, n_down=1, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64, flags=0,
+                stream=None)
+    _cases(lib, "wdf_ss_fwd", fwd, good, shape + rooted + [(dict(y=None), -1, b"null"), (dict(flags=1), -1, b"flags")])
+    bwd = "x coef rootp ns ni root n_up n_down zstash gy ws gcoef groot gz0 B T flags stream".split()
+    good = dict(x=ONE, coef=ONE, rootp=ONE, ns=2, ni=1, root=0, n_up=1, n_down=1, zstash=ONE, gy=ONE, ws=ONE, gcoef=ONE, groot=ONE, gz0=None,
+                B=4, T=64, flags=0, stream=None)
+    _cases(lib, "wdf_ss_bwd", bwd, good,
+           shape + rooted + [(dict(gy=None), -1, b"null"), (dict(ws=None), -1, b"null"), (dict(gcoef=None), -1, b"null"),
+                             (dict(zstash=None), -1, b"zstash"), (dict(root=2, groot=None), -1, b"groot"), (dict(flags=1), -1, b"flags")])
+    btp = "x coef rootp ns ni root n_up n_down zstash gy ws gcoef groot gz0 B T n_chunks stream".split()
+    good = dict(x=ONE, coef=ONE, rootp=ONE, ns=2, ni=1, root=0, n_up=1, n_down=1, zstash=ONE, gy=ONE, ws=ONE, gcoef=ONE, groot=ONE, gz0=None,
+                B=4, T=64, n_chunks=4, stream=None)
+    _cases(lib, "wdf_ss_bwd_tp", btp, good,
+           shape + rooted + [(dict(ns=0), -1, b"without states"), (dict(zstash=None), -1, b"null"), (dict(root=2, groot=None), -1, b"groot"),
+                             (dict(n_chunks=5), -1, b"wdf_ss_tp_chunks")])
+    lin = "x coef ns ni y zstash z0 zT B T n_chunks ws stream".split()
+    good = dict(x=ONE, coef=ONE, ns=2, ni=1, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64, n_chunks=2, ws=ONE, stream=None)
+    _cases(lib, "wdf_ss_fwd_lin_tp", lin, good,
+           shape + [(dict(ns=0), -1, b"without states"), (dict(y=None), -1, b"null"), (dict(ws=None), -1, b"null"), (dict(n_chunks=0), -1, b"n_chunks")])
+    # the speculating forward: no root to speculate on, no state, the two different diodes on four states
+    tpr = "x coef rootp ns ni root n_up n_down y zstash z0 zT B T n_chunks warmup tol zinit ws status stream".split()
+    good = dict(x=ONE, coef=ONE, rootp=ONE, ns=2, ni=1, root=2, n_up=1, n_down=1, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64, n_chunks=4,
+                warmup=8, tol=1e-6, zinit=None, ws=ONE, status=ONE, stream=None)
+    _cases(lib, "wdf_ss_fwd_tp_root", tpr, good,
+           [(dict(root=0), -1, b"nothing to speculate"), (dict(ns=0), -1, b"without states"), (dict(root=4, ns=4), -3, b"at most 3 states"),
+            (dict(root=4, rootp=None), -1, b"rootp"), (dict(n_up=17), -1, b"[1,16]"), (dict(ns=5), -3, None), (dict(ni=3), -3, None)])
+    assert lib.wdf_ss_ncoef(4, 2) == 16 + 8 + 4 + 4 + 2 + 4 + 2 + 1 and lib.wdf_ss_ncoef(0, 1) == 3
+
+
 def test_mlp_chunked_argument_validation_without_gpu(lib):
     tp = "x r theta2 w hidden n_tanh_layers fs y zstash z0 zT B T n_chunks warmup warmup_per_wave tol ws status stream".split()
     good = dict(x=ONE, r=None, theta2=ONE, w=ONE, hidden=8, n_tanh_layers=3, fs=48000.0, y=ONE, zstash=None, z0=None, zT=None, B=4, T=64,
