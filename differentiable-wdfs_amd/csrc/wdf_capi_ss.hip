@@ -359,4 +359,62 @@ int wdf_ss_lin_step_mse(const float* x, const float* coef, const double* jac, in
     return ok ? check_launch("wdf_ss_lin_step_mse") : no_kernel("wdf_ss_lin_step_mse");
 }
 
+// The MSE + ESR step: the MSE step's layout with twice the partial sums per wave ({GP, S} and {GQ, E}).
+size_t wdf_ss_lin_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks)
+{
+    if (!lin_step_ok(ns, ni) || B <= 0 || T <= 0 || n_chunks < 1) return 0;
+    const int K = chunk_geom(T, n_chunks, kLinStepUnit).K;
+    const size_t waves = waves64(B) * (size_t)K;
+    return 256 + (size_t)K * (size_t)lin_step_d(ns, ni) * (size_t)B * sizeof(float) + 256 +
+           waves * (size_t)(2 * (lin_step_g(ns, ni) + 1)) * sizeof(double);
+}
+
+// x, coef, jac, target, y, z0 / zT, chunks as wdf_ss_lin_step_mse.  ws: wdf_ss_lin_step_esr_ws_bytes() bytes, ZERO before the first
+// call (the step leaves it clean).  Loss on the rows t >= skip: S/n + sqrt(S / (E + eps_energy) / n), n = n_global.
+// sums: float [2 + 2 n_params] = {S, E, gP, gQ} of this call, or NULL; g: float [n_params] (the step finished as a single rank), or
+// NULL (then only sums is written); loss3: float [3] or NULL; gcoef_out: float [2 (ns^2 + ns ni + ns + ni)] = {GP, GQ} or NULL.
+int wdf_ss_lin_step_esr(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni, const float* target,
+                        double n_global, double eps_energy, int64_t skip, float* y, void* ws, float* sums, float* g, float* loss3,
+                        float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0, float* zT, void* stream)
+{
+    if (z0 && z0 == zT) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: zT must not alias z0 (every chunk reads z0)");
+    if (!x || !coef || !jac || !target || !y || !ws) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: null argument");
+    if (!sums && !g) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: sums and g are both null (nothing to hand back)");
+    if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "wdf_ss_lin_step_esr: ns in 0..2, ni in 1..2 (got %d, %d)", ns, ni);
+    if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams)
+        return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
+    if (skip < 0 || skip >= T) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: skip must be in [0, T) (got %lld, T = %lld)", (long long)skip, (long long)T);
+    if (!(n_global > 0.0) || !(eps_energy >= 0.0)) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: n_global > 0 and eps_energy >= 0");
+    const ChunkGeom cg = chunk_geom(T, n_chunks, kLinStepUnit);
+    const int K = cg.K;
+    const int64_t L = cg.L;
+    const int D = lin_step_d(ns, ni);
+    unsigned* ticket = (unsigned*)ws;
+    float* uend0 = (float*)((char*)ws + 256);
+    double* part = (double*)round_up((uintptr_t)(uend0 + (size_t)K * (size_t)D * (size_t)B), 256);
+    // two sequences per lane: the MSE step's rule, on every tree (no instantiation needs scratch for it: DESIGN.md's table)
+    const bool pair = (B % 2 == 0) && ((((uintptr_t)x | (uintptr_t)target | (uintptr_t)y | (uintptr_t)ws | (uintptr_t)z0 | (uintptr_t)zT) & 7u) == 0);
+    const int64_t per_wave = pair ? 128 : 64;
+    const dim3 grid((unsigned)((B + per_wave - 1) / per_wave), (unsigned)K);
+    hipStream_t s = (hipStream_t)stream;
+    const bool ok = dispatch([&](auto NS, auto NI, auto PAIR) {
+        using V = std::conditional_t<PAIR(), wdf::v2f, float>;
+        if (NS() > 0 && K > 1) hipLaunchKernelGGL((wdf::ss_lin_step_zero_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, uend0, B, T, L);
+        EventBracket bracket(s);
+        hipLaunchKernelGGL((wdf::ss_lin_step_esr_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, (const float*)uend0, target, skip,
+                           n_global, eps_energy, y, part, ticket, jac, n_params, sums, g, loss3, gcoef_out, B, T, L, z0, zT);
+    }, Values<int, 0, 1, 2>{ns}, SsInputs{ni}, Bools{pair});
+    return ok ? check_launch("wdf_ss_lin_step_esr") : no_kernel("wdf_ss_lin_step_esr");
+}
+
+// sums: {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> g [n_params] and (optional) loss3, one small launch.
+int wdf_ss_lin_esr_finish(const float* sums, int n_params, double n_global, double eps_energy, float* g, float* loss3, void* stream)
+{
+    if (!sums || !g) return fail(WDF_EINVAL, "wdf_ss_lin_esr_finish: null sums/g");
+    if (n_params < 1 || n_params > wdf::kProbeMaxParams) return fail(WDF_EINVAL, "wdf_ss_lin_esr_finish: 1..%d parameters", wdf::kProbeMaxParams);
+    if (!(n_global > 0.0) || !(eps_energy >= 0.0)) return fail(WDF_EINVAL, "wdf_ss_lin_esr_finish: n_global > 0 and eps_energy >= 0");
+    hipLaunchKernelGGL(wdf::ss_lin_esr_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, n_params, n_global, eps_energy, g, loss3);
+    return check_launch("wdf_ss_lin_esr_finish");
+}
+
 }  // extern "C"

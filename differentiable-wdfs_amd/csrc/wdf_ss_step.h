@@ -491,4 +491,210 @@ __global__ __launch_bounds__(64) void ss_lin_step_kernel(const float* __restrict
     }
 }
 
+// the next block's x and target into xn / tn (what ss_lin_step_kernel's load_blk closure does, as a function)
+template <int NI, typename V>
+__device__ __forceinline__ void lin_load_blk2(const float* __restrict__ x, const float* __restrict__ target, int64_t B, int64_t b,
+                                              int64_t ts, int64_t t1, V (&xn)[kLinBlk2][NI], V (&tn)[kLinBlk2])
+{
+    const int n = t1 - ts < kLinBlk2 ? (int)(t1 - ts) : kLinBlk2;
+    lin_load_x2<NI, V>(x, B, b, ts, n, xn);
+#pragma unroll
+    for (int i = 0; i < kLinBlk2; ++i) tn[i] = (i < n) ? lin_ld<V>(target + (ts + i) * B + b) : vsplat<V>(0.0f);
+}
+
+// ---- pass 2 for the scripts' training loss: MSE + ESR on the rows t >= skip (clipper_pot.py:141-177,232,248) ------------------
+//     loss = S/n + sqrt(S / (E + eps) / n) ,  S = sum (y - target)^2 ,  E = sum y^2 ,  dLoss/dy = ga (y - target) + gb y
+// ga and gb are functions of the GLOBAL S and E, so the pass carries BOTH weighted sums of the tangents -- the P family with
+// weight e = y - target (unscaled: ss_lin_step_kernel's sums at gscale = 1), the Q family with weight y -- and the last wave
+// combines them.  A sibling of ss_lin_step_kernel, not a flag on it: the MSE kernels keep their code byte for byte.  Pass 1
+// (ss_lin_step_zero_kernel) and lin_walk_to are shared; state, tangents and y advance on every row as there.  Rows before skip
+// carry weight 0 through a wave-uniform select (a chunk wholly before skip contributes zeros), dead lanes carry weight 0.
+// part: double [waves][2 (kG + 1)] = {GP[kG], S, GQ[kG], E}; ticket: one word, left 0.
+// sums: (or NULL) float [2 + 2 n_params] = {S, E, gP[n_params], gQ[n_params]} of THIS call, gP = GP . jac, gQ = GQ . jac: what
+// several ranks all-reduce.  g: (or NULL) float [n_params] <- ga gP + gb gQ, the step finished as a single rank with
+// esr_coef_kernel's formulas in fp64 from the double totals (an ESR of 0 contributes 0); loss3: (or NULL; with g) {mse, esr,
+// mse + esr}.  gcoef_out: (or NULL) float [2 kG] = {GP, GQ} before the Jacobian.
+template <int NS, int NI, typename V>
+__global__ __launch_bounds__(64) void ss_lin_step_esr_kernel(const float* __restrict__ x, const float* __restrict__ coef,
+                                                             const float* __restrict__ uend0, const float* __restrict__ target,
+                                                             int64_t skip, double n_global, double eps, float* __restrict__ y,
+                                                             double* __restrict__ part, unsigned* __restrict__ ticket,
+                                                             const double* __restrict__ jac, int n_params, float* __restrict__ sums,
+                                                             float* __restrict__ g_out, float* __restrict__ loss3,
+                                                             float* __restrict__ gcoef_out, int64_t B, int64_t T, int64_t L,
+                                                             const float* __restrict__ z0, float* __restrict__ zT)
+{
+    using U = LinU<NS, NI, V>;
+    using C = SSCoef<NS, NI>;
+    constexpr int W = LinWidth<V>::w;
+    constexpr int kG = U::kG, kP = 2 * (kG + 1), oQ = kG + 1;     // accumulators: {GP[kG], S} then {GQ[kG], E}
+    const V zero = vsplat<V>(0.0f);
+    const int64_t b_raw = ((int64_t)blockIdx.x * 64 + threadIdx.x) * W;
+    const bool live = b_raw < B;
+    const int64_t b = live ? b_raw : B - W;
+    const int64_t k = blockIdx.y, t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
+    SSCoef<NS, NI> c;
+    c.load(coef);
+    U u;
+    u.zero();
+    if (NS > 0 && z0) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) u.z[s] = lin_ld<V>(z0 + s * B + b);
+    }
+    if (NS > 0 && k > 0) lin_walk_to<NS, NI, V>(c, uend0, B, b, k, L, u);
+    const float lv = live ? 1.0f : 0.0f;
+    double acc[kP];
+#pragma unroll
+    for (int i = 0; i < kP; ++i) acc[i] = 0.0;
+    V xn[kLinBlk2][NI], tn[kLinBlk2];
+    lin_load_blk2<NI, V>(x, target, B, b, t0, t1, xn, tn);
+    for (int64_t tb = t0; tb < t1; tb += 32) {                     // fp32 sums within 32 steps, fp64 across
+        V f[kP];
+#pragma unroll
+        for (int i = 0; i < kP; ++i) f[i] = zero;
+#pragma unroll 1
+        for (int64_t ts = tb; ts < tb + 32 && ts < t1; ts += kLinBlk2) {
+            const int n = t1 - ts < kLinBlk2 ? (int)(t1 - ts) : kLinBlk2;
+            V xs[kLinBlk2][NI], tg[kLinBlk2];
+#pragma unroll
+            for (int i = 0; i < kLinBlk2; ++i) {
+                tg[i] = tn[i];
+#pragma unroll
+                for (int j = 0; j < NI; ++j) xs[i][j] = xn[i][j];
+            }
+            if (ts + kLinBlk2 < t1) lin_load_blk2<NI, V>(x, target, B, b, ts + kLinBlk2, t1, xn, tn);
+#pragma unroll
+            for (int i = 0; i < kLinBlk2; ++i) {
+                if (i >= n) break;
+                V yv = zero;
+#pragma unroll
+                for (int j = 0; j < NI; ++j) yv = vfma(c.v[C::oDy + j], xs[i][j], yv);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) yv = vfma(c.v[C::oCy + s], u.z[s], yv);
+                const V e = yv - tg[i];
+                if (live) lin_st_nt<V>(y + (ts + i) * B + b, yv);
+                // rows before skip: the weights themselves are 0, by a select (ts, i, skip are the same in every lane) -- not
+                // 0 x e, which would let a NaN or Inf in a skipped row of target (padding) into every sum
+                const bool on = ts + i >= skip;
+                const V es = on ? e : zero;
+                const V ge = es * lv, gy = on ? yv * lv : zero;
+                f[kG] = vfma(ge, es, f[kG]);
+                f[oQ + kG] = vfma(gy, yv, f[oQ + kG]);
+#pragma unroll
+                for (int cc = 0; cc < U::nA; ++cc) {
+                    V d = zero;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) d = vfma(c.v[C::oCy + s], u.SA[cc][s], d);
+                    f[cc] = vfma(ge, d, f[cc]);
+                    f[oQ + cc] = vfma(gy, d, f[oQ + cc]);
+                }
+#pragma unroll
+                for (int cc = 0; cc < U::nB; ++cc) {
+                    V d = zero;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) d = vfma(c.v[C::oCy + s], u.SB[cc][s], d);
+                    f[U::nA + cc] = vfma(ge, d, f[U::nA + cc]);
+                    f[oQ + U::nA + cc] = vfma(gy, d, f[oQ + U::nA + cc]);
+                }
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    f[U::nA + U::nB + s] = vfma(ge, u.z[s], f[U::nA + U::nB + s]);
+                    f[oQ + U::nA + U::nB + s] = vfma(gy, u.z[s], f[oQ + U::nA + U::nB + s]);
+                }
+#pragma unroll
+                for (int j = 0; j < NI; ++j) {
+                    f[U::nA + U::nB + NS + j] = vfma(ge, xs[i][j], f[U::nA + U::nB + NS + j]);
+                    f[oQ + U::nA + U::nB + NS + j] = vfma(gy, xs[i][j], f[oQ + U::nA + U::nB + NS + j]);
+                }
+                lin_u_step<NS, NI, V>(c, xs[i], u);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kP; ++i) acc[i] += lin_hsum(f[i]);
+    }
+    if (NS > 0 && zT && t1 == T && live) {                          // the states the call ends in [NS][B] (never the z0 buffer)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) lin_st<V>(zT + s * B + b, u.z[s]);
+    }
+    // ---- this wave's partial; the last wave of the launch (the counted ticket of ss_lin_step_kernel: no wait on anything) adds
+    // them up in wave order, so the results repeat bit for bit, and finishes the step
+    const int64_t wave = (int64_t)blockIdx.y * gridDim.x + blockIdx.x, nwaves = (int64_t)gridDim.x * gridDim.y;
+#pragma unroll
+    for (int i = 0; i < kP; ++i) {
+        const double s = wave_sum_dpp(acc[i]);
+        if (threadIdx.x == 0) __hip_atomic_store(part + wave * kP + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned old = 0;
+    if (threadIdx.x == 0) old = atomicAdd(ticket, 1u);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (old != (unsigned)(nwaves - 1)) return;
+    if (threadIdx.x == 0) *ticket = 0u;
+    // (a wave's whole row per trip: its kP loads are in flight together -- one memory latency per 64 waves, not one per entry;
+    //  every entry still adds its waves in the same order)
+    double tot[kP];
+#pragma unroll
+    for (int i = 0; i < kP; ++i) tot[i] = 0.0;
+    for (int64_t w = threadIdx.x; w < nwaves; w += 64) {
+#pragma unroll
+        for (int i = 0; i < kP; ++i) tot[i] += __hip_atomic_load(part + w * kP + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int i = 0; i < kP; ++i) tot[i] = wave_sum_dpp(tot[i]);
+    const double S = tot[kG], E = tot[oQ + kG];
+    const int p = threadIdx.x;
+    if (p < n_params) {
+        double gP = 0.0, gQ = 0.0;
+#pragma unroll
+        for (int i = 0; i < kG; ++i) {
+            const int row = i < U::nA ? C::oA + i : (i < U::nA + U::nB ? C::oB + (i - U::nA)
+                                                     : (i < U::nA + U::nB + NS ? C::oCy + (i - U::nA - U::nB) : C::oDy + (i - U::nA - U::nB - NS)));
+            const double j = jac[row * n_params + p];
+            gP += tot[i] * j;
+            gQ += tot[oQ + i] * j;
+        }
+        if (sums) {
+            sums[2 + p] = (float)gP;
+            sums[2 + n_params + p] = (float)gQ;
+        }
+        if (g_out) {
+            const double Ee = E + eps, esr = sqrt(S / Ee / n_global);
+            const double ga = 2.0 / n_global + (esr > 0.0 ? 1.0 / (esr * Ee * n_global) : 0.0), gb = -esr / Ee;
+            g_out[p] = (float)(ga * gP + gb * gQ);
+        }
+    }
+    if (p == 0) {
+        if (sums) {
+            sums[0] = (float)S;
+            sums[1] = (float)E;
+        }
+        if (g_out && loss3) {
+            const double mse = S / n_global, esr = sqrt(S / (E + eps) / n_global);
+            loss3[0] = (float)mse;
+            loss3[1] = (float)esr;
+            loss3[2] = (float)(mse + esr);
+        }
+        if (gcoef_out) {
+#pragma unroll
+            for (int i = 0; i < kG; ++i) {
+                gcoef_out[i] = (float)tot[i];
+                gcoef_out[kG + i] = (float)tot[oQ + i];
+            }
+        }
+    }
+}
+
+// Several ranks: sums = {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> the global loss and its gradient (the
+// single-rank finish's formulas, on the floats).  One wave, lane p owns parameter p.
+static __global__ __launch_bounds__(64) void ss_lin_esr_finish_kernel(const float* __restrict__ sums, int n_params, double n, double eps,
+                                                                      float* __restrict__ g, float* __restrict__ loss3)
+{
+    const double S = sums[0], E = (double)sums[1] + eps;
+    const double mse = S / n, esr = sqrt(S / E / n);
+    const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0), gb = -esr / E;
+    const int p = threadIdx.x;
+    if (p < n_params) g[p] = (float)(ga * (double)sums[2 + p] + gb * (double)sums[2 + n_params + p]);
+    if (p == 0 && loss3) { loss3[0] = (float)mse; loss3[1] = (float)esr; loss3[2] = (float)(mse + esr); }
+}
+
 }  // namespace wdf

@@ -253,6 +253,12 @@ def lib():
     L.wdf_ss_lin_step_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
     L.wdf_ss_lin_step_mse.restype = ci
     L.wdf_ss_lin_step_mse.argtypes = [fp, fp, vp, ci, ci, ci, fp, cf, fp, vp, fp, fp, fp, i64, i64, ci, fp, fp, vp]
+    L.wdf_ss_lin_step_esr_ws_bytes.restype = C.c_size_t
+    L.wdf_ss_lin_step_esr_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
+    L.wdf_ss_lin_step_esr.restype = ci
+    L.wdf_ss_lin_step_esr.argtypes = [fp, fp, vp, ci, ci, ci, fp, C.c_double, C.c_double, i64, fp, vp, fp, fp, fp, fp, i64, i64, ci, fp, fp, vp]
+    L.wdf_ss_lin_esr_finish.restype = ci
+    L.wdf_ss_lin_esr_finish.argtypes = [fp, ci, C.c_double, C.c_double, fp, fp, vp]
     L.wdf_ss_nl_step_ws_bytes.restype = C.c_size_t
     L.wdf_ss_nl_step_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
     L.wdf_ss_nl_step_chunk_len.restype = ci
@@ -357,6 +363,7 @@ EXPORTED_SYMBOLS = (
     "wdf_clipper_mlp_step_state_bytes", "wdf_clipper_mlp_step_plan", "wdf_clipper_mlp_step_read", "wdf_clipper_mlp_step_set",
     "wdf_clipper_mlp_step_set_wcol", "wdf_clipper_mlp_step_prepare", "wdf_clipper_mlp_step",
     "wdf_ss_probe", "wdf_ss_probe_adam", "wdf_ss_lin_step_ws_bytes", "wdf_ss_lin_step_mse",
+    "wdf_ss_lin_step_esr_ws_bytes", "wdf_ss_lin_step_esr", "wdf_ss_lin_esr_finish",
     "wdf_ss_nl_step_ws_bytes", "wdf_ss_nl_step_chunk_len", "wdf_ss_nl_step_plan", "wdf_ss_nl_step_set", "wdf_ss_nl_step_read",
     "wdf_ss_nl_step_mse", "wdf_ss_nl_step_esr_ws_bytes", "wdf_ss_nl_step_esr",
     "wdf_ss_ncoef", "wdf_ss_fwd", "wdf_ss_bwd", "wdf_ss_bwd_ws_bytes", "wdf_ss_fwd_lin_tp_ws_bytes", "wdf_ss_fwd_lin_tp",
@@ -1645,17 +1652,44 @@ def ss_asym_step_esr(x, coef, rootp, ns, ni, target, n_global, eps_energy, skip,
     return y, zT, sums, g, loss3, status
 
 
-def _lin_step_shape(x_tm, coef):
+def _lin_step_shape(x_tm, coef, what="ss_lin_step_mse"):
     """(ns, ni, B, T, ncoef) of a linear one-pass step from x_tm [T,ni,B] and coef ([ncoef], or the probe's [ncoef + 1] with the
     port resistance behind it): the ns in 0..2 whose wdf_ss_ncoef fits."""
     if x_tm.dim() != 3 or x_tm.shape[1] not in (1, 2) or x_tm.shape[0] < 1 or x_tm.shape[2] < 1:
-        raise WdfHipError(f"ss_lin_step_mse: x_tm must be [T,ni,B] with ni in 1..2, got {tuple(x_tm.shape)}")
+        raise WdfHipError(f"{what}: x_tm must be [T,ni,B] with ni in 1..2, got {tuple(x_tm.shape)}")
     T, ni, B = (int(v) for v in x_tm.shape)
     for ns in (0, 1, 2):
         ncoef = lib().wdf_ss_ncoef(ns, ni)
         if coef.dim() == 1 and coef.numel() in (ncoef, ncoef + 1):
             return ns, ni, B, T, ncoef
-    raise WdfHipError(f"ss_lin_step_mse: coef {tuple(coef.shape)} is no coefficient vector of ns in 0..2 states and ni = {ni} inputs")
+    raise WdfHipError(f"{what}: coef {tuple(coef.shape)} is no coefficient vector of ns in 0..2 states and ni = {ni} inputs")
+
+
+def _lin_step_args(what, ws_bytes, x_tm, coef, jac, target, n_chunks, z0, want_zT, ws, y):
+    """The shape checks and buffers the two linear one-pass steps share -> x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT."""
+    x_tm, coef, target, z0 = _f32_dev(x_tm, "x_tm"), _f32_dev(coef, "coef"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
+    ns, ni, B, T, ncoef = _lin_step_shape(x_tm, coef, what)
+    if not (isinstance(jac, torch.Tensor) and jac.is_cuda and jac.dtype == torch.float64 and jac.is_contiguous() and jac.dim() == 2
+            and jac.shape[0] in (ncoef, ncoef + 1) and 1 <= jac.shape[1] <= 15):
+        raise WdfHipError(f"{what}: jac must be a contiguous float64 [{ncoef} (+1), 1..15] tensor on the GPU")
+    n_params = int(jac.shape[1])
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if ns > 0 and z0 is not None and tuple(z0.shape) != (ns, B):
+        raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
+    if y is None:
+        y = torch.empty((T, B), dtype=torch.float32, device=x_tm.device)
+    elif tuple(_f32_dev(y, "y").shape) != (T, B):
+        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    need = ws_bytes(ns, ni, B, T, int(n_chunks))
+    if need == 0:
+        raise WdfHipError(f"{what}: no step for ns={ns}, ni={ni}, B={B}, T={T}, n_chunks={n_chunks}")
+    if ws is None:
+        ws = torch.zeros((need,), dtype=torch.uint8, device=x_tm.device)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.is_contiguous()) or ws.numel() * ws.element_size() < need:
+        raise WdfHipError(f"ws must hold the {need} bytes the step needs, on the GPU")
+    zT = torch.empty((ns, B), dtype=torch.float32, device=x_tm.device) if (want_zT and ns > 0) else None
+    return x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT
 
 
 def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=False, want_gcoef=False, ws=None, y=None):
@@ -1666,35 +1700,70 @@ def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=
     the library pairs sequences up by their addresses.
     -> dict: y [T,B], out [1 + n_params] = {SSE, gradients}, loss (0-dim), gcoef [ns^2 + ns ni + ns + ni] | None, zT [ns,B] | None, ws."""
     require_gpu()
-    x_tm, coef, target, z0 = _f32_dev(x_tm, "x_tm"), _f32_dev(coef, "coef"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
-    ns, ni, B, T, ncoef = _lin_step_shape(x_tm, coef)
-    if not (isinstance(jac, torch.Tensor) and jac.is_cuda and jac.dtype == torch.float64 and jac.is_contiguous() and jac.dim() == 2
-            and jac.shape[0] in (ncoef, ncoef + 1) and 1 <= jac.shape[1] <= 15):
-        raise WdfHipError(f"ss_lin_step_mse: jac must be a contiguous float64 [{ncoef} (+1), 1..15] tensor on the GPU")
-    n_params = int(jac.shape[1])
-    if tuple(target.shape) != (T, B):
-        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
-    if ns > 0 and z0 is not None and tuple(z0.shape) != (ns, B):
-        raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=x_tm.device)
-    elif tuple(_f32_dev(y, "y").shape) != (T, B):
-        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
-    need = lib().wdf_ss_lin_step_ws_bytes(ns, ni, B, T, int(n_chunks))
-    if need == 0:
-        raise WdfHipError(f"ss_lin_step_mse: no step for ns={ns}, ni={ni}, B={B}, T={T}, n_chunks={n_chunks}")
-    if ws is None:
-        ws = torch.zeros((need,), dtype=torch.uint8, device=x_tm.device)
-    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.is_contiguous()) or ws.numel() * ws.element_size() < need:
-        raise WdfHipError(f"ws must hold the {need} bytes the step needs, on the GPU")
+    x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_mse", lib().wdf_ss_lin_step_ws_bytes, x_tm, coef,
+                                                                               jac, target, n_chunks, z0, want_zT, ws, y)
     out = torch.empty((1 + n_params,), dtype=torch.float32, device=x_tm.device)
     loss = torch.empty((), dtype=torch.float32, device=x_tm.device)
     gcoef = torch.empty((ns * ns + ns * ni + ns + ni,), dtype=torch.float32, device=x_tm.device) if want_gcoef else None
-    zT = torch.empty((ns, B), dtype=torch.float32, device=x_tm.device) if (want_zT and ns > 0) else None
     _check(lib().wdf_ss_lin_step_mse(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), float(gscale), _ptr(y), _ptr(ws),
                                      _ptr(out), _ptr(loss), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()),
            "wdf_ss_lin_step_mse")
     return {"y": y, "out": out, "loss": loss, "gcoef": gcoef, "zT": zT, "ws": ws}
+
+
+ESR_EPS = 2.220446049250313e-16      # what the scripts' esr_loss adds to the energy (clipper_pot.py:146-156: float64 machine epsilon)
+
+
+def ss_lin_step_esr(x_tm, coef, jac, target, skip, n_chunks, n_global=None, eps=ESR_EPS, z0=None, want_zT=False, want_gcoef=False,
+                    ws=None, y=None, finish=True):
+    """The MSE + ESR training step of a LINEAR tree in one pass (wdf_ss_lin_step_esr, csrc/wdf_ss_step.h): loss = S/n +
+    sqrt(S / (E + eps) / n) on the rows t >= skip (0 <= skip < T), S = sum (y - target)^2, E = sum y^2, n = n_global (None: this
+    call's own B (T - skip)).  Arguments, shape checks and buffers as ss_lin_step_mse; ws: zeroed wdf_ss_lin_step_esr_ws_bytes()
+    bytes when not given.  finish=True: a single rank -- the kernel's last wave forms g = dloss/d params and loss3 itself;
+    finish=False: one shard of several -- only sums comes back (g and loss3 None): add the shards' sums and call ss_lin_esr_finish().
+    -> dict: y [T,B], sums [2 + 2 n_params] = {S, E, gP, gQ}, g [n_params] | None, loss3 [3] = {mse, esr, mse + esr} | None,
+    gcoef [2 (ns^2 + ns ni + ns + ni)] = {GP, GQ} | None, zT [ns,B] | None, ws."""
+    require_gpu()
+    x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_esr", lib().wdf_ss_lin_step_esr_ws_bytes, x_tm,
+                                                                               coef, jac, target, n_chunks, z0, want_zT, ws, y)
+    skip = int(skip)
+    if not 0 <= skip < T:
+        raise WdfHipError(f"ss_lin_step_esr: skip must be in [0, T) = [0, {T}), got {skip}")
+    n_global = float(B * (T - skip)) if n_global is None else float(n_global)
+    if not n_global > 0.0 or not float(eps) >= 0.0:
+        raise WdfHipError("ss_lin_step_esr: n_global > 0 and eps >= 0")
+    dev = x_tm.device
+    sums = torch.empty((2 + 2 * n_params,), dtype=torch.float32, device=dev)
+    g = torch.empty((n_params,), dtype=torch.float32, device=dev) if finish else None
+    loss3 = torch.empty((3,), dtype=torch.float32, device=dev) if finish else None
+    gcoef = torch.empty((2 * (ns * ns + ns * ni + ns + ni),), dtype=torch.float32, device=dev) if want_gcoef else None
+    _check(lib().wdf_ss_lin_step_esr(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), n_global, float(eps), skip, _ptr(y),
+                                     _ptr(ws), _ptr(sums), _ptr(g), _ptr(loss3), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT),
+                                     _stream()), "wdf_ss_lin_step_esr")
+    return {"y": y, "sums": sums, "g": g, "loss3": loss3, "gcoef": gcoef, "zT": zT, "ws": ws}
+
+
+def ss_lin_esr_finish(sums, n_global, eps=ESR_EPS, g=None, loss3=None):
+    """Several ranks: sums = {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> (g [n_params], loss3 = {mse, esr,
+    mse + esr}), the global loss and its gradient (wdf_ss_lin_esr_finish: the single-rank step's own formulas)."""
+    require_gpu()
+    sums = _f32_dev(sums, "sums")
+    n_params = (sums.numel() - 2) // 2
+    if sums.dim() != 1 or sums.numel() != 2 + 2 * n_params or not 1 <= n_params <= 15:
+        raise WdfHipError("sums must hold {S, E, gP[n_params], gQ[n_params]} with 1..15 parameters")
+    if not float(n_global) > 0.0 or not float(eps) >= 0.0:
+        raise WdfHipError("ss_lin_esr_finish: n_global > 0 and eps >= 0")
+    if g is None:
+        g = torch.empty((n_params,), dtype=torch.float32, device=sums.device)
+    elif _f32_dev(g, "g").numel() != n_params:
+        raise WdfHipError(f"g must hold {n_params} gradients")
+    if loss3 is None:
+        loss3 = torch.empty((3,), dtype=torch.float32, device=sums.device)
+    elif _f32_dev(loss3, "loss3").numel() != 3:
+        raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
+    _check(lib().wdf_ss_lin_esr_finish(_ptr(sums), n_params, float(n_global), float(eps), _ptr(g), _ptr(loss3), _stream()),
+           "wdf_ss_lin_esr_finish")
+    return g, loss3
 
 
 PROBE_MAX_OPS, PROBE_MAX_PARAMS = 384, 15                                            # csrc/wdf_ss_step.h

@@ -34,6 +34,11 @@ N_SIMD = 1024            # MI355X: 256 CUs x 4
 # decided per loss by tools/ss_asym_step_bench.py (the step's slowest sample against the composed path's fastest, at both of its
 # shapes; profiles/r13_ss_asym_step.jsonl).  Circuit._asym_tree_step is the step either way.
 ASYM_TREE_STEP_SERVES = {"mse": False, "mse_esr": False}
+# Whether Circuit.mse_esr() takes the one-pass MSE + ESR step of a resident LINEAR tree (csrc/wdf_ss_step.h: wdf_ss_lin_step_esr;
+# Circuit._mse_esr_lin_step reaches it either way).  The project's standing criterion for a step: True only where the step's slowest
+# sample beats the composed path's fastest at both shapes of tools/ss_lin_esr_step_bench.py (the linear step's section).
+# Measured (profiles/r17_ss_lin_esr_step.jsonl): 0.142 ms against 0.905 ms at 8192 x 4096, 0.079 ms against 0.620 ms at 1340 x 2048.
+LIN_ESR_STEP_SERVES = True
 
 
 def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
@@ -472,8 +477,9 @@ class _LinResident:
             x_tm = xd.permute(1, 2, 0).contiguous()               # [T][ni][B]: once per training set
             tgt = target.as_subclass(torch.Tensor).to(dev).float().reshape(T, B).contiguous()
             per_wave = 128 if B % 2 == 0 else 64                  # (two sequences per lane when the rows pair up)
-            if loss != "mse" and circ.ns * circ.ni > 1:
-                per_wave = 64                                     # (the MSE + ESR step pairs them up on the smallest tree only)
+            if loss != "mse" and circ.root_kind == "DiodePair" and circ.ns * circ.ni > 1:
+                per_wave = 64                                     # (the diode-root MSE + ESR step pairs them up on the smallest tree only;
+                #                                                    the linear one pairs them up on every tree, as its MSE step does)
             L_ = binding.lib()
             y = torch.empty((T, B), dtype=torch.float32, device=dev)
             if circ.root_kind == "DiodePair":
@@ -482,7 +488,8 @@ class _LinResident:
                 ws = self._plan_nl(B, T, k, dev)
             else:
                 k = max(1, min(T // 64, (_LIN_OCC * N_SIMD) // max(1, -(-B // per_wave))))
-                nbytes = L_.wdf_ss_lin_step_ws_bytes(circ.ns, circ.ni, B, T, k)
+                ws_bytes = L_.wdf_ss_lin_step_ws_bytes if loss == "mse" else L_.wdf_ss_lin_step_esr_ws_bytes
+                nbytes = ws_bytes(circ.ns, circ.ni, B, T, k)
                 if nbytes == 0:
                     raise binding.WdfHipError(L_.wdf_last_error().decode() or "wdf_ss_lin_step_ws_bytes: unsupported tree")
                 ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
@@ -490,9 +497,11 @@ class _LinResident:
             # slab of _ROWS; a full slab is replaced by a fresh one and lives on for as long as anything still refers to
             # it): the loss history a script keeps (lpf.py:99 `losses.append(loss)`) and gradients read after the loop stay
             # what they were -- no copy per call, one allocation per _ROWS calls
-            # (a row of the MSE + ESR step: {S, gradients}, then {mse, esr, mse + esr})
+            # (a row of the diode-root MSE + ESR step: {S, gradients}, then {mse, esr, mse + esr}; of the linear one: {0, gradients},
+            #  {mse, esr, mse + esr}, then this call's sums {S, E, gP[n], gQ[n]}: the C ABI hands S back with the sums)
+            width = 2 if loss == "mse" else (4 if circ.root_kind == "DiodePair" else 6 + 2 * self.pb.n)
             ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": y, "ws": ws,
-                                       "ring": torch.zeros((_ROWS, (2 if loss == "mse" else 4) + self.pb.n), dtype=torch.float32, device=dev),
+                                       "ring": torch.zeros((_ROWS, width + self.pb.n), dtype=torch.float32, device=dev),
                                        "turn": 0, "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0,
                                        "loss": loss, "skip": int(skip)},
                                  extra, nbytes=_nbytes(x_tm, tgt, y, ws))
@@ -569,7 +578,8 @@ class _LinResident:
         """probe + one-pass step -> (out = {SSE, d(mean squared error)/d component value}, loss = the mean squared error): views
         of this call's own result row (never written again).  z0 [ns,B] float32 on the device: the capacitor states the call
         starts from (linear trees; None: zero); want_zT: the states it ends in are left in ent["zT"] (a buffer of its own per
-        call parity, never the one z0 may be)."""
+        call parity, never the one z0 may be).  The MSE + ESR step of a LINEAR tree: out = {0, d(mse + esr)/d component value},
+        loss = mse + esr; the call's row stays in ent["row"] = {0, g[n], mse, esr, mse + esr, S, E, gP[n], gQ[n]} (S is row[4 + n])."""
         circ = self.circ
         self.probe()
         B, T, n = ent["B"], ent["T"], self.pb.n
@@ -605,6 +615,21 @@ class _LinResident:
             bufs = ent.setdefault("zT_bufs", [torch.empty((circ.ns, B), dtype=torch.float32, device=ent["y"].device) for _ in range(2)])
             zT = bufs[0] if (z0 is None or z0.data_ptr() != bufs[0].data_ptr()) else bufs[1]
         ent["zT"] = zT
+        if ent.get("loss", "mse") != "mse":
+            # MSE + ESR past skip on a linear tree (wdf_ss_lin_step_esr): the gradients land in out[1:] and {mse, esr, mse + esr} in
+            # the row behind them, then this call's sums {S, E, gP, gQ} (what a data-parallel loop would all-reduce): the C ABI
+            # hands S back with the sums, not in front of g, so out[0] stays 0 and S is row[4 + n] -- per call like the rest of the
+            # row, never written again.  (Addresses inside the row by arithmetic: every view is microseconds of host time.)
+            at = row.data_ptr()
+            rc = binding.lib().wdf_ss_lin_step_esr(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), n, circ.ns,
+                                                   circ.ni, binding._ptr(ent["t"]), float(B * (T - ent["skip"])), ESR_EPS, int(ent["skip"]),
+                                                   binding._ptr(ent["y"]), binding._ptr(ent["ws"]), ctypes.c_void_p(at + 4 * (4 + n)),
+                                                   ctypes.c_void_p(at + 4), ctypes.c_void_p(at + 4 * (1 + n)), None, B, T, ent["k"],
+                                                   None if z0 is None else binding._ptr(z0), None if zT is None else binding._ptr(zT),
+                                                   binding._stream())
+            binding._check(rc, "wdf_ss_lin_step_esr")
+            ent["row"] = row                                      # ({0, g[n], mse, esr, mse + esr, S, E, gP[n], gQ[n]} of this call)
+            return out, row[3 + n]
         rc = binding.lib().wdf_ss_lin_step_mse(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), self.pb.n,
                                                circ.ns, circ.ni, binding._ptr(ent["t"]), 2.0 / float(B * T), binding._ptr(ent["y"]),
                                                binding._ptr(ent["ws"]), binding._ptr(out), binding._ptr(loss), None, B, T, ent["k"],
@@ -995,7 +1020,9 @@ class Circuit:
         (wdf_clipper_step_esr_tp), and so does the clipper under an AsymDiodePair root with a Newton solver
         (wdf_clipper_asym_step_esr: forward, both loss sums and the six gradients in one sweep, with or without z0 /
         carry_state; `circ.last_output` is then the step's own y buffer, valid until the next call of the same shape, and a
-        tensor of its own on stateful calls); anything else composes it from the forward.
+        tensor of its own on stateful calls); a resident LINEAR tree (to_device() of an ideal-source root, at most two capacitors
+        and two sources) likewise (wdf_ss_lin_step_esr, LIN_ESR_STEP_SERVES: z0 / carry_state are the step's own z0 / zT,
+        `circ.last_output` the batch's output buffer); anything else composes it from the forward.
         z0 / carry_state: as in mse() -- the state the call starts from, or the one the previous carry_state call ended in
         (`circ.last_state`); composed from __call__(x, z0, return_state) (the resident one-pass steps start from zero state,
         which is what clipper_pot.py:110-111 does before every forward)."""
@@ -1010,6 +1037,11 @@ class Circuit:
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
             return self._asym_tree_step(x, target, "mse_esr", int(skip), z0, stateful)
+        if LIN_ESR_STEP_SERVES and getattr(self, "_lin", None) is not None and isinstance(x, torch.Tensor) \
+                and isinstance(target, torch.Tensor) and x.dim() >= 2 and 0 <= int(skip) < int(x.shape[1]):
+            if carry_state and z0 is None:
+                z0 = getattr(self, "last_state", None)
+            return self._mse_esr_lin_step(x, target, int(skip), z0, stateful)      # the linear step takes z0 / zT itself
         if stateful:
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
@@ -1092,6 +1124,34 @@ class Circuit:
         loss = loss.as_subclass(tf.Tensor)
         loss._wdf_fused = (out, {id(v): i for i, v in live})
         self.last_output = ent["y"]
+        return loss
+
+    def _mse_esr_lin_step(self, x, target, skip=0, z0=None, stateful=False):
+        """mse_esr(x, target, skip) of a resident LINEAR tree as ONE pass (wdf_ss_lin_step_esr) through the MSE step's autograd
+        function, factor 1.0: the loss carries the gradient the pass produced (`_wdf_fused`), the queued optimizer updates ride in
+        its probe launch, `last_output` is the step's y.  z0 [ns,B] / stateful: the step's own z0 / zT, as in mse(); `last_state`
+        is a clone of zT on stateful calls."""
+        lin = getattr(self, "_lin", None)
+        if lin is None:
+            raise binding.WdfHipError("Circuit._mse_esr_lin_step: a resident linear tree only (to_device() of an ideal-source root, at "
+                                      "most two capacitors and two sources)")
+        if not (isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)) or not 0 <= int(skip) < int(x.shape[1]):
+            raise binding.WdfHipError("Circuit._mse_esr_lin_step: tensors in and 0 <= skip < T")
+        if self.ns == 0:
+            stateful, z0 = False, None                            # (no capacitor: nothing to carry)
+        with torch._C.DisableTorchFunctionSubclass():
+            lin.check()
+            ent = lin.entry(x, target, "mse+esr", int(skip))
+            live = [(i, v) for i, v in sorted(lin.pb.members.items()) if v.requires_grad]
+            z0d = None
+            if z0 is not None:
+                z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["y"].device).float().reshape(self.ns, ent["B"]).contiguous()
+        loss, out = _LinResidentMseFn.apply(lin, ent, 1.0, [i for i, _ in live], z0d, bool(stateful), *[v for _, v in live])
+        loss = loss.as_subclass(tf.Tensor)
+        loss._wdf_fused = (out, {id(v): i for i, v in live})
+        self.last_output = ent["y"]
+        if stateful:
+            self.last_state = ent["zT"].clone()                  # (ent["zT"] is one of two ping-pong buffers: kept by value)
         return loss
 
     def _asym_step_tree(self, x, target, kind="mse", skip=0):

@@ -360,6 +360,28 @@ int wdf_ss_lin_step_mse(const float* x, const float* coef, const double* jac, in
                         const float* target, float gscale, float* y, void* ws, float* out, float* loss_out,
                         float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0, float* zT,
                         void* stream);
+/* The same one-pass step for the scripts' training loss, MSE + ESR on the rows t >= skip (clipper_pot.py:141-177,232,248):
+ *   loss = S / n + sqrt(S / (E + eps_energy) / n),  S = sum (y - target)^2,  E = sum y^2,  n = n_global.
+ * dLoss/dy = ga (y - target) + gb y with ga, gb functions of the GLOBAL S and E, so the pass carries both weighted sums of the
+ * forward tangents (weight y - target, weight y) and its last wave contracts both with jac.  State, tangents and y run over the
+ * rows before skip (0 <= skip < T, anywhere in a chunk) as over any row; they count for nothing in the sums.
+ *   sums       device float [2 + 2 n_params] = {S, E, gP[n_params], gQ[n_params]} of THIS call (gP = d(S/2)/d params,
+ *              gQ = d(E/2)/d params), or NULL: with several ranks all-reduce it and call wdf_ss_lin_esr_finish.
+ *   g          device float [n_params] <- ga gP + gb gQ, the step finished as a single rank (fp64 from the double totals; an
+ *              ESR of 0 contributes 0), or NULL: then only sums is written.  sums and g must not both be NULL.
+ *   loss3      (optional, with g) device float [3] = {mse, esr, mse + esr}.
+ *   gcoef_out  (optional) device float [2 (ns^2 + ns ni + ns + ni)] = the two sums over {A, Bx, cy, dy} before the Jacobian.
+ * x, coef, jac, target, y, n_chunks, z0 / zT as wdf_ss_lin_step_mse; ns 0..2, ni 1..2, n_params 1..15.  ws:
+ * wdf_ss_lin_step_esr_ws_bytes bytes (the MSE step's layout with twice the partial sums), ZERO before the first call; the step
+ * leaves it clean.  wdf_ss_lin_esr_finish: one small launch, the same fp64 formulas on all-reduced sums.  Additions to ABI 6: no
+ * existing signature changed, wdf_ss_lin_step_ws_bytes is what it was. */
+size_t wdf_ss_lin_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+int wdf_ss_lin_step_esr(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni,
+                        const float* target, double n_global, double eps_energy, int64_t skip, float* y, void* ws,
+                        float* sums, float* g, float* loss3, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
+                        const float* z0, float* zT, void* stream);
+int wdf_ss_lin_esr_finish(const float* sums, int n_params, double n_global, double eps_energy, float* g, float* loss3,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The one-pass MSE training step of small trees with a DIODE-PAIR root (csrc/wdf_ss_nl_step.h): the same epoch
