@@ -684,6 +684,21 @@ class MlpTrainStep:
         binding._check(self.lib.wdf_clipper_mlp_step_set(binding._ptr(self.state), 12, 1 if on else 0, binding._stream()),
                        "wdf_clipper_mlp_step_set")
 
+    def set_controller(self, cold16=None, tol=None, repair_at=None):
+        """Controller words of the live state (wdf_clipper_mlp_step_set): cold16 -- the cold call's warm-up in 16-step units;
+        tol -- the chunk verification's tolerance; repair_at -- a re-run chunk has met the old trajectory at repair_at * tol."""
+        words = []
+        if cold16 is not None:
+            words.append((3, int(cold16)))
+        for field, v in ((9, tol), (13, repair_at)):
+            if v is not None:
+                words.append((field, int(_np.float32(v).view(_np.int32))))
+        for field, bits in words:
+            binding._check(self.lib.wdf_clipper_mlp_step_set(binding._ptr(self.state), field, bits, binding._stream()),
+                           "wdf_clipper_mlp_step_set")
+        if tol is not None:
+            self.tol = float(tol)
+
     # -- the step -------------------------------------------------------------------------------------------------
     def _call(self, phase, adam):
         a = adam

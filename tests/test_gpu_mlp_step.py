@@ -51,6 +51,7 @@ def sequential_reference(xd, rd, w, hidden, n_layers, target, skip, C):
 
 
 def mlp_components(hidden, n_layers, stride=4):
+    # (a strided sample of the hidden kernels: tests/test_gpu_mlp_step_edges.py compares every weight's gradient)
     idx, o, n_in = [], 0, 2
     for layer in range(n_layers):
         nk = n_in * hidden
