@@ -938,6 +938,30 @@ def clipper_bwd_mse_tp(x, theta, fs, zstash, zT, target, gscale, n_chunks, r=Non
     return gtheta, sse
 
 
+def _mlp_check_shapes(who, x, theta2, w, hidden, n_tanh, r=None, z0=None, zstash=None, gy=None, sweep=False):
+    """What the wdf_clipper_mlp_* kernels index by (B, T) and by the architecture without the C ABI knowing the arrays' sizes
+    -> (B, T): x [B,T]; theta2 at least the 2 values {R, C}; w wdf_mlp_weight_count(hidden, n_tanh) values; r [B,T]; z0 B values;
+    for a reverse sweep (sweep=True) zstash and gy [T,B]."""
+    if x.dim() != 2:
+        raise WdfHipError(f"{who}: x must be [B,T], got {tuple(x.shape)}")
+    B, T = int(x.shape[0]), int(x.shape[1])
+    if theta2 is None or theta2.numel() < 2:
+        raise WdfHipError(f"{who}: theta2 must hold the 2 values {{R, C}}, got {None if theta2 is None else theta2.numel()}")
+    n = lib().wdf_mlp_weight_count(int(hidden), int(n_tanh))
+    if w is None or w.numel() != n:
+        raise WdfHipError(f"{who}: a {n_tanh - 1}x{hidden} network has {n} weights, got {None if w is None else w.numel()}")
+    if r is not None and tuple(r.shape) != (B, T):
+        raise WdfHipError(f"{who}: r must be [B,T] = [{B},{T}], got {tuple(r.shape)}")
+    if z0 is not None and tuple(z0.shape) != (B,):
+        raise WdfHipError(f"{who}: z0 must be [B] = [{B}], got {tuple(z0.shape)}")
+    if sweep:
+        if zstash is None or tuple(zstash.shape) != (T, B):
+            raise WdfHipError(f"{who}: zstash must be [T,B] = [{T},{B}], got {None if zstash is None else tuple(zstash.shape)}")
+        if gy is None or tuple(gy.shape) != (T, B):
+            raise WdfHipError(f"{who}: gy must be [T,B] = [{T},{B}], got {None if gy is None else tuple(gy.shape)}")
+    return B, T
+
+
 def clipper_mlp_fwd(x, theta2, w, hidden, n_tanh, fs, r=None, want_stash=True, z0=None, want_zT=False):
     """MLP-root clipper forward.  x [B,T], theta2 = {R, C}, w flat weights.  -> y [T,B], zstash, zT."""
     require_gpu()
@@ -946,10 +970,7 @@ def clipper_mlp_fwd(x, theta2, w, hidden, n_tanh, fs, r=None, want_stash=True, z
     theta2 = _f32_dev(theta2, "theta2")
     w = _f32_dev(w, "w")
     z0 = _f32_dev(z0, "z0")
-    n = lib().wdf_mlp_weight_count(int(hidden), int(n_tanh))
-    if w.numel() != n:
-        raise WdfHipError(f"a {n_tanh - 1}x{hidden} network has {n} weights, got {w.numel()}")
-    B, T = x.shape
+    B, T = _mlp_check_shapes("clipper_mlp_fwd", x, theta2, w, hidden, n_tanh, r=r, z0=z0)
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, B), dtype=torch.float32, device=x.device) if want_stash else None
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
@@ -968,7 +989,7 @@ def clipper_mlp_bwd(x, theta2, w, hidden, n_tanh, fs, zstash, gy, r=None):
     w = _f32_dev(w, "w")
     zstash = _f32_dev(zstash, "zstash")
     gy = _f32_dev(gy, "gy")
-    B, T = x.shape
+    B, T = _mlp_check_shapes("clipper_mlp_bwd", x, theta2, w, hidden, n_tanh, r=r, zstash=zstash, gy=gy, sweep=True)
     gb = torch.empty((T, B), dtype=torch.float32, device=x.device)
     ain = torch.empty((T, B), dtype=torch.float32, device=x.device)
     lrin = torch.empty((T, B), dtype=torch.float32, device=x.device) if r is not None else None
@@ -990,6 +1011,7 @@ def clipper_mlp_bwd_w(x, theta2, w, hidden, n_tanh, fs, zstash, gy, r=None):
     nbytes = lib().wdf_clipper_mlp_bwd_w_ws_bytes(int(hidden), int(n_tanh), B)
     if nbytes <= 0:
         raise WdfHipError(f"unsupported MLP root: width {hidden}, {n_tanh} tanh layers")
+    _mlp_check_shapes("clipper_mlp_bwd_w", x, theta2, w, hidden, n_tanh, r=r, zstash=zstash, gy=gy, sweep=True)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
     gth = torch.empty((2,), dtype=torch.float32, device=x.device)
     gw = torch.empty((w.numel(),), dtype=torch.float32, device=x.device)
@@ -1008,9 +1030,7 @@ def clipper_mlp_fwd_tp(x, theta2, w, hidden, n_tanh, fs, n_chunks, warmup, r=Non
     (with want_kappa): the states the chunks start their warm-up from (mlp_tp_starts() names the samples)."""
     require_gpu()
     x, r, theta2, w, z0 = _f32_dev(x, "x"), _f32_dev(r, "r"), _f32_dev(theta2, "theta2"), _f32_dev(w, "w"), _f32_dev(z0, "z0")
-    if w.numel() != lib().wdf_mlp_weight_count(int(hidden), int(n_tanh)):
-        raise WdfHipError(f"a {n_tanh - 1}x{hidden} network has {lib().wdf_mlp_weight_count(int(hidden), int(n_tanh))} weights, got {w.numel()}")
-    B, T = x.shape
+    B, T = _mlp_check_shapes("clipper_mlp_fwd_tp", x, theta2, w, hidden, n_tanh, r=r, z0=z0)
     if warmup_per_wave is not None and not (warmup_per_wave.is_cuda and warmup_per_wave.dtype == torch.int32
                                             and warmup_per_wave.numel() == (B + 3) // 4 and warmup_per_wave.is_contiguous()):
         raise WdfHipError("warmup_per_wave: expected a contiguous int32 device tensor with ceil(B/4) entries")
@@ -1068,6 +1088,7 @@ def clipper_mlp_bwd_w_tp(x, theta2, w, hidden, n_tanh, fs, zstash, gy, n_chunks,
     nbytes = lib().wdf_clipper_mlp_bwd_w_tp_ws_bytes(int(hidden), int(n_tanh), B, T, int(n_chunks))
     if nbytes <= 0:
         raise WdfHipError(f"unsupported MLP root: width {hidden}, {n_tanh} tanh layers")
+    _mlp_check_shapes("clipper_mlp_bwd_w_tp", x, theta2, w, hidden, n_tanh, r=r, zstash=zstash, gy=gy, sweep=True)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
     gth = torch.empty((2,), dtype=torch.float32, device=x.device)
@@ -1095,7 +1116,11 @@ def mlp_eval(ain, lrin, w, hidden, n_tanh):
     w = _f32_dev(w, "w")
     if lrin.numel() != ain.numel():
         raise WdfHipError("mlp_eval: ain and lrin must have the same number of samples")
-    out = torch.empty((ain.numel(),), dtype=torch.float32, device=ain.device)
+    n = lib().wdf_mlp_weight_count(int(hidden), int(n_tanh))
+    # (a network no kernel is built for is the library's to refuse; one that has kernels must come with all its weights)
+    if lib().wdf_clipper_mlp_bwd_w_ws_bytes(int(hidden), int(n_tanh), 1) > 0 and w.numel() != n:
+        raise WdfHipError(f"mlp_eval: a {n_tanh - 1}x{hidden} network has {n} weights, got {w.numel()}")
+    out =torch.empty((ain.numel(),), dtype=torch.float32, device=ain.device)
     rc = lib().wdf_mlp_eval(_ptr(ain), _ptr(lrin), _ptr(w), int(hidden), int(n_tanh), _ptr(out), ain.numel(), _stream())
     _check(rc, "wdf_mlp_eval")
     return out

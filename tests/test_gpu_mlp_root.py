@@ -161,7 +161,7 @@ def test_segmented_time_parallel_matches_sequential(golden):
     assert miss > 1e-6 and float((y_bad - y_seq).abs().max()) <= 2e-6
 
 
-@pytest.mark.parametrize("hidden,n_tanh", [(4, 3), (8, 3), (16, 3), (8, 4), (4, 5), (8, 5)])
+@pytest.mark.parametrize("hidden,n_tanh", [(4, 3), (8, 3), (16, 3), (4, 4), (8, 4), (4, 5), (8, 5)])
 @pytest.mark.parametrize("dyn", [False, True])
 @pytest.mark.parametrize("S", [64 * 700 + 37, 1, 17, 16 * 8 * 4 * 3 + 1])   # ragged: the tail lanes must contribute nothing; one sample;
 def test_wgrad_kernel_matches_dense_autograd(hidden, n_tanh, dyn, S):       # one partial block; one sample past a workgroup's share
@@ -190,7 +190,7 @@ def test_wgrad_kernel_matches_dense_autograd(hidden, n_tanh, dyn, S):       # on
     assert err <= 2e-5 * float(want.abs().max()), (err, float(want.abs().max()))
 
 
-@pytest.mark.parametrize("hidden,n_tanh", [(4, 3), (8, 3), (16, 3), (8, 4), (4, 5), (8, 5)])
+@pytest.mark.parametrize("hidden,n_tanh", [(4, 3), (8, 3), (16, 3), (4, 4), (8, 4), (4, 5), (8, 5)])
 @pytest.mark.parametrize("B,T,dyn", [(1, 16, False), (5, 100, True), (7, 257, False), (130, 515, True)])
 def test_row_kernels_equal_lane_kernels(hidden, n_tanh, B, T, dyn):
     """The 16-lane-row kernels (default) against the one-lane-per-sequence kernels, random weights,
@@ -272,7 +272,7 @@ def test_mlp_forward_on_matrix_cores_equals_the_row_kernel_at_a_large_batch(monk
 
 
 # ---- in-kernel time-parallel MLP-root kernels (csrc/wdf_mlp_tp.h) ----------------------------------------
-@pytest.mark.parametrize("hidden,n_tanh", [(8, 3), (16, 3), (4, 5), (8, 5)])
+@pytest.mark.parametrize("hidden,n_tanh", [(8, 3), (16, 3), (4, 4), (4, 5), (8, 5)])
 @pytest.mark.parametrize("B,T,K,dyn", [(5, 100, 3, True), (7, 257, 2, False), (130, 515, 4, True), (96, 2048, 8, True)])
 def test_mlp_time_parallel_kernels_equal_sequential(hidden, n_tanh, B, T, K, dyn, wgrad_kernel, monkeypatch):
     """Forward: chunks warmed up per wave (pot-dependent), verified on the device -> the sequential kernel's y,
@@ -328,7 +328,7 @@ def test_mlp_time_parallel_forward_repairs_a_short_warmup(forward_kernel):
     assert float((zT2 - zT).abs().max()) <= tol
 
 
-@pytest.mark.parametrize("hidden,n_tanh", [(8, 3), (16, 3), (8, 5)])
+@pytest.mark.parametrize("hidden,n_tanh", [(8, 3), (16, 3), (4, 4), (8, 5)])
 @pytest.mark.parametrize("B,T,K,dyn,warm", [(5, 100, 3, True, 448), (7, 257, 2, False, 448), (130, 515, 4, True, 448),
                                             (96, 2048, 8, True, 448), (40, 1024, 4, True, 32)])
 def test_mlp_forward_stored_kappa_equals_the_recomputed_one(hidden, n_tanh, B, T, K, dyn, warm, wgrad_kernel):
