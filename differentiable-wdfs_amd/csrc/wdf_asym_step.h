@@ -42,6 +42,7 @@
 
 #include "wdf_asym.h"
 #include "wdf_optim.h"
+#include "wdf_esr.h"
 
 namespace wdf {
 
@@ -300,9 +301,8 @@ __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const doub
         if (threadIdx.x == 0) { esr.sums14[0] = (float)t[0]; esr.sums14[1] = (float)t[1]; }
         if (threadIdx.x < 6) { esr.sums14[2 + threadIdx.x] = (float)gi; esr.sums14[8 + threadIdx.x] = (float)qi; }
         if (esr.gtheta6 == nullptr) return;
-        const double n = esr.n_global, S = t[0], E = t[1] + esr.eps;
-        const double mse = S / n, er = sqrt(S / E / n);
-        const double ga = 2.0 / n + (er > 0.0 ? 1.0 / (er * E * n) : 0.0), gb = -er / E;
+        const EsrTerms lt = esr_terms(t[0], t[1] + esr.eps, esr.n_global);
+        const double mse = lt.mse, er = lt.esr, ga = lt.ga, gb = lt.gb;
         g = (float)(ga * gi + gb * qi);
         if (threadIdx.x < 6) esr.gtheta6[threadIdx.x] = g;
         if (threadIdx.x == 0 && esr.loss3) { esr.loss3[0] = (float)mse; esr.loss3[1] = (float)er; esr.loss3[2] = (float)(mse + er); }
@@ -324,15 +324,6 @@ __global__ __launch_bounds__(64) void clipper_asym_step_finish_kernel(const doub
     theta6[i] = th;
 }
 
-// Several ranks: sums14 summed over the ranks -> the global loss and gradient (the single-rank finish's formulas, on the floats)
-static __global__ void asym_esr_finish_kernel(const float* __restrict__ sums14, double n, double eps, float* __restrict__ gtheta6,
-                                              float* __restrict__ loss3)
-{
-    const double S = sums14[0], E = (double)sums14[1] + eps;
-    const double mse = S / n, esr = sqrt(S / E / n);
-    const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0), gb = -esr / E;
-    for (int k = 0; k < 6; ++k) gtheta6[k] = (float)(ga * (double)sums14[2 + k] + gb * (double)sums14[8 + k]);
-    if (loss3) { loss3[0] = (float)mse; loss3[1] = (float)esr; loss3[2] = (float)(mse + esr); }
-}
+// (several ranks: sums14 summed over the ranks -> the global loss and gradient: esr_finish_kernel, wdf_esr.h, six entries)
 
 }  // namespace wdf

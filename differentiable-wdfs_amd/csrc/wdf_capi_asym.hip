@@ -323,7 +323,7 @@ int wdf_asym_esr_finish(const float* sums14, double n_global, double eps_energy,
 {
     if (!sums14 || !gtheta6 || !(n_global > 0.0) || !(eps_energy >= 0.0))
         return fail(WDF_EINVAL, "wdf_asym_esr_finish: null sums14/gtheta6, n_global <= 0 or eps_energy < 0");
-    hipLaunchKernelGGL(wdf::asym_esr_finish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sums14, n_global, eps_energy, gtheta6, loss3);
+    hipLaunchKernelGGL(wdf::esr_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums14, 6, n_global, eps_energy, gtheta6, loss3);
     return check_launch("wdf_asym_esr_finish");
 }
 

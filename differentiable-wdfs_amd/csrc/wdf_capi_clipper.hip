@@ -276,17 +276,6 @@ wdf::AdamTail adam_tail(float* theta, float* m, float* v, int32_t* step, const f
     return wdf::AdamTail{m ? theta : nullptr, m, v, step, lr, beta1, beta2, eps, lo, hi};
 }
 
-// the finish of the MSE + ESR step after the ranks' sums10 have been all-reduced (esr_tile_partial_and_finish's last lines)
-__global__ void esr_finish_kernel(const float* __restrict__ sums10, double n, double eps, float* __restrict__ gtheta,
-                                  float* __restrict__ loss3)
-{
-    const double S = sums10[0], E = (double)sums10[1] + eps;
-    const double mse = S / n, esr = sqrt(S / E / n);
-    const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0), gb = -esr / E;
-    for (int k = 0; k < 4; ++k) gtheta[k] = (float)(ga * (double)sums10[2 + k] + gb * (double)sums10[6 + k]);
-    if (loss3) { loss3[0] = (float)mse; loss3[1] = (float)esr; loss3[2] = (float)(mse + esr); }
-}
-
 }  // namespace
 
 extern "C" {
@@ -600,7 +589,8 @@ int wdf_clipper_step_esr_tp(const float* x, const float* r, float* theta, float 
 int wdf_esr_finish(const float* sums10, double n_global, double eps_energy, float* gtheta, float* loss3, void* stream)
 {
     if (!sums10 || !gtheta || !(n_global > 0.0)) return fail(WDF_EINVAL, "wdf_esr_finish: null sums10/gtheta or n_global <= 0");
-    hipLaunchKernelGGL(esr_finish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sums10, n_global, eps_energy, gtheta, loss3);
+    // (the finish of the MSE + ESR step after the ranks' sums10 have been all-reduced: wdf_esr.h, four entries)
+    hipLaunchKernelGGL(wdf::esr_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums10, 4, n_global, eps_energy, gtheta, loss3);
     return check_launch("wdf_esr_finish");
 }
 

@@ -306,19 +306,61 @@ int wdf_ss_probe_adam(const wdf_adam_job* jobs, int n_jobs, const int32_t* tape,
     return probe_launch(jobs, n_jobs, tape, n_ops, consts, params, n_params, outs, n_out, coef, coef64, jac, stream, "wdf_ss_probe_adam");
 }
 
-static bool lin_step_ok(int ns, int ni) { return ns >= 0 && ns <= 2 && ni >= 1 && ni <= 2; }
-static int lin_step_d(int ns, int ni) { return ns * (1 + ns * ns + ns * ni); }
-static int lin_step_g(int ns, int ni) { return ns * ns + ns * ni + ns + ni; }
+}  // extern "C"
+
+// ---- the one-pass step of linear trees, MSE and MSE + ESR (wdf_ss_step.h) -----------------------------------------------
+namespace {
+
+bool lin_step_ok(int ns, int ni) { return ns >= 0 && ns <= 2 && ni >= 1 && ni <= 2; }
+int lin_step_d(int ns, int ni) { return ns * (1 + ns * ns + ns * ni); }
+int lin_step_g(int ns, int ni) { return ns * ns + ns * ni + ns + ni; }
 constexpr int kLinStepUnit = 32;
 
-size_t wdf_ss_lin_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks)
+// the ticket's line, the chunks' zero-state ends, a line of slack for the alignment, the waves' partial sums: `families` rows
+// of {gradient entries, sum of squares} per wave (1: MSE, 2: MSE + ESR)
+size_t lin_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks, int families)
 {
     if (!lin_step_ok(ns, ni) || B <= 0 || T <= 0 || n_chunks < 1) return 0;
     const int K = chunk_geom(T, n_chunks, kLinStepUnit).K;
     const size_t waves = waves64(B) * (size_t)K;
     return 256 + (size_t)K * (size_t)lin_step_d(ns, ni) * (size_t)B * sizeof(float) + 256 +
-           waves * (size_t)(lin_step_g(ns, ni) + 1) * sizeof(double);
+           waves * (size_t)(families * (lin_step_g(ns, ni) + 1)) * sizeof(double);
 }
+
+// Both losses' launches, arguments already checked: pass 1 where there is a state to carry across a chunk boundary, then pass 2
+// (the bracketed one) with the loss's own scalars and outputs in `a`.
+template <int LOSS>
+int lin_step_launch(const char* what, const float* x, const float* coef, const double* jac, int n_params, int ns, int ni,
+                    const float* target, float* y, void* ws, float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0,
+                    float* zT, const typename wdf::LinLoss<LOSS>::type& a, hipStream_t s)
+{
+    const ChunkGeom g = chunk_geom(T, n_chunks, kLinStepUnit);
+    const int K = g.K;
+    const int64_t L = g.L;
+    // the ticket, the chunks' zero-state ends and the waves' partial sums, each on a 256-byte line of its own (by ADDRESS)
+    unsigned* ticket = (unsigned*)ws;
+    float* uend0 = (float*)((char*)ws + 256);
+    double* part = (double*)round_up((uintptr_t)(uend0 + (size_t)K * (size_t)lin_step_d(ns, ni) * (size_t)B), 256);
+    // two sequences per lane (8-byte loads and stores) when the rows of x, target, y and the workspace allow it, on every tree
+    // and for both losses (no instantiation needs scratch for it: DESIGN.md's table)
+    const bool pair = (B % 2 == 0) && ((((uintptr_t)x | (uintptr_t)target | (uintptr_t)y | (uintptr_t)ws | (uintptr_t)z0 | (uintptr_t)zT) & 7u) == 0);
+    const int64_t per_wave = pair ? 128 : 64;
+    const dim3 grid((unsigned)((B + per_wave - 1) / per_wave), (unsigned)K);
+    const bool ok = dispatch([&](auto NS, auto NI, auto PAIR) {
+        using V = std::conditional_t<PAIR(), wdf::v2f, float>;
+        if (NS() > 0 && K > 1) hipLaunchKernelGGL((wdf::ss_lin_step_zero_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, uend0, B, T, L);
+        EventBracket bracket(s);
+        hipLaunchKernelGGL((wdf::ss_lin_step_kernel<NS(), NI(), V, LOSS>), grid, dim3(64), 0, s, x, coef, (const float*)uend0, target, y,
+                           part, ticket, jac, n_params, gcoef_out, B, T, L, z0, zT, a);
+    }, Values<int, 0, 1, 2>{ns}, SsInputs{ni}, Bools{pair});
+    return ok ? check_launch(what) : no_kernel(what);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t wdf_ss_lin_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks) { return lin_step_ws_bytes(ns, ni, B, T, n_chunks, 1); }
 
 // x: [T][ni][B] time-major (the resident training set); coef / jac: wdf_ss_probe's outputs; target, y: [T][B].
 // ws: wdf_ss_lin_step_ws_bytes() bytes, ZERO before the first call (the step leaves it clean).
@@ -336,38 +378,12 @@ int wdf_ss_lin_step_mse(const float* x, const float* coef, const double* jac, in
     if (!x || !coef || !jac || !target || !y || !ws || !out) return fail(WDF_EINVAL, "null argument");
     if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "wdf_ss_lin_step_mse: ns in 0..2, ni in 1..2 (got %d, %d)", ns, ni);
     if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams) return fail(WDF_EINVAL, "B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
-    const ChunkGeom g = chunk_geom(T, n_chunks, kLinStepUnit);
-    const int K = g.K;
-    const int64_t L = g.L;
-    const int D = lin_step_d(ns, ni);
-    // the ticket, the chunks' zero-state ends and the waves' partial sums, each on a 256-byte line of its own (by ADDRESS)
-    unsigned* ticket = (unsigned*)ws;
-    float* uend0 = (float*)((char*)ws + 256);
-    double* part = (double*)round_up((uintptr_t)(uend0 + (size_t)K * (size_t)D * (size_t)B), 256);
-    // two sequences per lane (8-byte loads and stores) when the rows of x, target, y and the workspace allow it
-    const bool pair = (B % 2 == 0) && ((((uintptr_t)x | (uintptr_t)target | (uintptr_t)y | (uintptr_t)ws | (uintptr_t)z0 | (uintptr_t)zT) & 7u) == 0);
-    const int64_t per_wave = pair ? 128 : 64;
-    const dim3 grid((unsigned)((B + per_wave - 1) / per_wave), (unsigned)K);
-    hipStream_t s = (hipStream_t)stream;
-    const bool ok = dispatch([&](auto NS, auto NI, auto PAIR) {
-        using V = std::conditional_t<PAIR(), wdf::v2f, float>;
-        if (NS() > 0 && K > 1) hipLaunchKernelGGL((wdf::ss_lin_step_zero_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, uend0, B, T, L);
-        EventBracket bracket(s);
-        hipLaunchKernelGGL((wdf::ss_lin_step_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, (const float*)uend0, target, gscale, y,
-                           part, ticket, jac, n_params, out, loss_out, gcoef_out, B, T, L, z0, zT);
-    }, Values<int, 0, 1, 2>{ns}, SsInputs{ni}, Bools{pair});
-    return ok ? check_launch("wdf_ss_lin_step_mse") : no_kernel("wdf_ss_lin_step_mse");
+    return lin_step_launch<0>("wdf_ss_lin_step_mse", x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
+                              wdf::LinMse{gscale, out, loss_out}, (hipStream_t)stream);
 }
 
 // The MSE + ESR step: the MSE step's layout with twice the partial sums per wave ({GP, S} and {GQ, E}).
-size_t wdf_ss_lin_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks)
-{
-    if (!lin_step_ok(ns, ni) || B <= 0 || T <= 0 || n_chunks < 1) return 0;
-    const int K = chunk_geom(T, n_chunks, kLinStepUnit).K;
-    const size_t waves = waves64(B) * (size_t)K;
-    return 256 + (size_t)K * (size_t)lin_step_d(ns, ni) * (size_t)B * sizeof(float) + 256 +
-           waves * (size_t)(2 * (lin_step_g(ns, ni) + 1)) * sizeof(double);
-}
+size_t wdf_ss_lin_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks) { return lin_step_ws_bytes(ns, ni, B, T, n_chunks, 2); }
 
 // x, coef, jac, target, y, z0 / zT, chunks as wdf_ss_lin_step_mse.  ws: wdf_ss_lin_step_esr_ws_bytes() bytes, ZERO before the first
 // call (the step leaves it clean).  Loss on the rows t >= skip: S/n + sqrt(S / (E + eps_energy) / n), n = n_global.
@@ -385,26 +401,8 @@ int wdf_ss_lin_step_esr(const float* x, const float* coef, const double* jac, in
         return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
     if (skip < 0 || skip >= T) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: skip must be in [0, T) (got %lld, T = %lld)", (long long)skip, (long long)T);
     if (!(n_global > 0.0) || !(eps_energy >= 0.0)) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: n_global > 0 and eps_energy >= 0");
-    const ChunkGeom cg = chunk_geom(T, n_chunks, kLinStepUnit);
-    const int K = cg.K;
-    const int64_t L = cg.L;
-    const int D = lin_step_d(ns, ni);
-    unsigned* ticket = (unsigned*)ws;
-    float* uend0 = (float*)((char*)ws + 256);
-    double* part = (double*)round_up((uintptr_t)(uend0 + (size_t)K * (size_t)D * (size_t)B), 256);
-    // two sequences per lane: the MSE step's rule, on every tree (no instantiation needs scratch for it: DESIGN.md's table)
-    const bool pair = (B % 2 == 0) && ((((uintptr_t)x | (uintptr_t)target | (uintptr_t)y | (uintptr_t)ws | (uintptr_t)z0 | (uintptr_t)zT) & 7u) == 0);
-    const int64_t per_wave = pair ? 128 : 64;
-    const dim3 grid((unsigned)((B + per_wave - 1) / per_wave), (unsigned)K);
-    hipStream_t s = (hipStream_t)stream;
-    const bool ok = dispatch([&](auto NS, auto NI, auto PAIR) {
-        using V = std::conditional_t<PAIR(), wdf::v2f, float>;
-        if (NS() > 0 && K > 1) hipLaunchKernelGGL((wdf::ss_lin_step_zero_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, uend0, B, T, L);
-        EventBracket bracket(s);
-        hipLaunchKernelGGL((wdf::ss_lin_step_esr_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, (const float*)uend0, target, skip,
-                           n_global, eps_energy, y, part, ticket, jac, n_params, sums, g, loss3, gcoef_out, B, T, L, z0, zT);
-    }, Values<int, 0, 1, 2>{ns}, SsInputs{ni}, Bools{pair});
-    return ok ? check_launch("wdf_ss_lin_step_esr") : no_kernel("wdf_ss_lin_step_esr");
+    return lin_step_launch<1>("wdf_ss_lin_step_esr", x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
+                              wdf::LinEsr{skip, n_global, eps_energy, sums, g, loss3}, (hipStream_t)stream);
 }
 
 // sums: {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> g [n_params] and (optional) loss3, one small launch.
@@ -413,7 +411,7 @@ int wdf_ss_lin_esr_finish(const float* sums, int n_params, double n_global, doub
     if (!sums || !g) return fail(WDF_EINVAL, "wdf_ss_lin_esr_finish: null sums/g");
     if (n_params < 1 || n_params > wdf::kProbeMaxParams) return fail(WDF_EINVAL, "wdf_ss_lin_esr_finish: 1..%d parameters", wdf::kProbeMaxParams);
     if (!(n_global > 0.0) || !(eps_energy >= 0.0)) return fail(WDF_EINVAL, "wdf_ss_lin_esr_finish: n_global > 0 and eps_energy >= 0");
-    hipLaunchKernelGGL(wdf::ss_lin_esr_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, n_params, n_global, eps_energy, g, loss3);
+    hipLaunchKernelGGL(wdf::esr_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, n_params, n_global, eps_energy, g, loss3);
     return check_launch("wdf_ss_lin_esr_finish");
 }
 

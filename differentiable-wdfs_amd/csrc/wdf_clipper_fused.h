@@ -35,6 +35,7 @@
 #pragma once
 
 #include "wdf_clipper.h"
+#include "wdf_esr.h"
 
 namespace wdf {
 
@@ -902,9 +903,8 @@ __device__ __forceinline__ void esr_tile_partial_and_finish(const double (&v)[8]
     if (threadIdx.x < 4) { out.sums10[2 + threadIdx.x] = (float)gPc; out.sums10[6 + threadIdx.x] = (float)gQc; }
     float gi = 0.0f;
     if (out.gtheta != nullptr) {
-        const double n = out.n_global, S = t[3], E = t[7] + out.eps;
-        const double mse = S / n, esr = sqrt(S / E / n);
-        const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0), gb = -esr / E;
+        const EsrTerms lt = esr_terms(t[3], t[7] + out.eps, out.n_global);
+        const double mse = lt.mse, esr = lt.esr, ga = lt.ga, gb = lt.gb;
         gi = (out.accumulate ? out.gtheta[c] : 0.0f) + (float)(ga * gPc + gb * gQc);
         if (threadIdx.x < 4) out.gtheta[threadIdx.x] = gi;
         if (threadIdx.x == 0 && out.loss3) { out.loss3[0] = (float)mse; out.loss3[1] = (float)esr; out.loss3[2] = (float)(mse + esr); }

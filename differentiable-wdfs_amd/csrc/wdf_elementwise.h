@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "wdf_omega.h"
+#include "wdf_esr.h"
 
 namespace wdf {
 
@@ -49,16 +50,15 @@ static __global__ __launch_bounds__(256) void loss_sums_finish_kernel(const doub
     if (threadIdx.x == 0) { sums[0] = sh[0][0]; sums[1] = sh[0][1]; }
 }
 
-// From the (global) sums: loss = S/n + sqrt(S / (E + eps) / n) and its derivative w.r.t. y,
-//   dL/dy_i = ga (y_i - t_i) + gb y_i ,  ga = 2/n + 1/(esr (E+eps) n) ,  gb = -esr / (E+eps).
+// From the (global) sums: the loss and the coefficients of its derivative w.r.t. y, dL/dy_i = ga (y_i - t_i) + gb y_i
+// (esr_terms, wdf_esr.h).
 static __global__ void esr_coef_kernel(const double* __restrict__ sums, double n, double eps, float* __restrict__ gcoef,
                                 float* __restrict__ loss)
 {
-    const double S = sums[0], E = sums[1] + eps;
-    const double mse = S / n, esr = sqrt(S / E / n);
-    gcoef[0] = (float)(2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0));
-    gcoef[1] = (float)(-esr / E);
-    loss[0] = (float)mse; loss[1] = (float)esr; loss[2] = (float)(mse + esr);
+    const EsrTerms lt = esr_terms(sums[0], sums[1] + eps, n);
+    gcoef[0] = (float)lt.ga;
+    gcoef[1] = (float)lt.gb;
+    loss[0] = (float)lt.mse; loss[1] = (float)lt.esr; loss[2] = (float)(lt.mse + lt.esr);
 }
 
 // dL/dy [T][B] of that loss for a reverse sweep that takes an upstream gradient (the MLP-root sweep): zero before

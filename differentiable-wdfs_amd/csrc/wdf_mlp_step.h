@@ -700,7 +700,8 @@ __global__ __launch_bounds__(256) void mlp_step_wgrad_kernel(const MlpStepArgs A
     const bool live = b_raw < B;
     const int64_t b = live ? b_raw : B - 1;
     const int64_t t0 = (int64_t)chunk * Lw, t1 = !active ? t0 : ((t0 + Lw < T) ? t0 + Lw : T);
-    // ---- the loss coefficients: dLoss/dy = ga (y - t) + gb y past skip (clipper_pot.py:146-156,177; wdf_elementwise.h)
+    // ---- the loss coefficients: dLoss/dy = ga (y - t) + gb y past skip (clipper_pot.py:146-156,177; esr_terms' expressions,
+    // wdf_esr.h, by hand here and in mlp_step_reduce_adam_kernel: calling it reorders these tuned kernels' instructions)
     double S, E;
     if (sums) { S = sums[0]; E = sums[1]; }
     else {

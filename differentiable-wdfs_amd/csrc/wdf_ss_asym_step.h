@@ -437,6 +437,7 @@ __global__ __launch_bounds__(64) void ss_asym_step_finish_kernel(const float* __
         if (i == 0) { o.sums[0] = (float)Ssum; o.sums[1] = (float)Esum; }
         if (i < D::nG) { o.sums[2 + i] = (float)t; o.sums[2 + D::nG + i] = (float)q; }
         if (o.g == nullptr) return;
+        // (esr_terms' expressions, wdf_esr.h, by hand: calling it reorders this kernel's instructions)
         const double n = o.n_global, En = Esum + o.eps;
         const double mse = Ssum / n, er = sqrt(Ssum / En / n);
         const double ga = 2.0 / n + (er > 0.0 ? 1.0 / (er * En * n) : 0.0), gb = -er / En;

@@ -808,6 +808,7 @@ __global__ __launch_bounds__((64 * WD * NlTile<NS, WD, LOSS>::n)) void ss_nl_ste
     mm = wave_max_dpp(mm);
     // LOSS = 1: the loss and its coefficients from the global sums (esr_coef_kernel's formulas, wdf_elementwise.h), then
     // ga P + gb Q per coefficient -- from here on sum[0 .. nG) is dLoss/d coefficient as in the MSE step
+    // (esr_terms' expressions, wdf_esr.h, by hand: calling it reorders this tuned kernel's instructions)
     double mse = 0.0, esr = 0.0;
     if constexpr (LOSS != 0) {
         const double Ssum = sum[D::nG], En = sum[D::oQ + D::nG] + a.eps, n = (double)a.B * (double)(a.T - a.skip);

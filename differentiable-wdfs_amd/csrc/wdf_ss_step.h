@@ -28,6 +28,7 @@
 #include "wdf_clipper.h"      // wave_sum_dpp
 #include "wdf_vec.h"
 #include "wdf_optim.h"
+#include "wdf_esr.h"
 
 namespace wdf {
 
@@ -234,14 +235,14 @@ __device__ __forceinline__ void lin_u_step(const SSCoef<NS, NI>& c, const V (&x)
     for (int s = 0; s < NS; ++s) u.z[s] = zn[s];
 }
 
-constexpr int kLinBlk = 8;                                         // steps whose loads are issued together
+constexpr int kLinBlk = 8;                                         // pass 1: steps whose loads are issued together
 
-// x: [T][NI][B] (time-major: the engine's resident training set); loads kLinBlk steps of lane b
-template <int NI, typename V>
-__device__ __forceinline__ void lin_load_x(const float* __restrict__ x, int64_t B, int64_t b, int64_t t, int n, V (&xs)[kLinBlk][NI])
+// x: [T][NI][B] (time-major: the engine's resident training set); loads N steps of lane b (N: the caller's block, pass 1's or pass 2's)
+template <int NI, typename V, int N>
+__device__ __forceinline__ void lin_load_x(const float* __restrict__ x, int64_t B, int64_t b, int64_t t, int n, V (&xs)[N][NI])
 {
 #pragma unroll
-    for (int k = 0; k < kLinBlk; ++k)
+    for (int k = 0; k < N; ++k)
 #pragma unroll
         for (int i = 0; i < NI; ++i) xs[k][i] = (k < n) ? lin_ld<V>(x + ((t + k) * NI + i) * B + b) : vsplat<V>(0.0f);
 }
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(64) void ss_lin_step_zero_kernel(const float* __res
     for (int64_t tb = t0; tb < t1; tb += kLinBlk) {
         const int n = t1 - tb < kLinBlk ? (int)(t1 - tb) : kLinBlk;
         V xs[kLinBlk][NI];
-        lin_load_x<NI, V>(x, B, b, tb, n, xs);
+        lin_load_x(x, B, b, tb, n, xs);
 #pragma unroll
         for (int i = 0; i < kLinBlk; ++i)
             if (i < n) lin_u_step<NS, NI, V>(c, xs[i], u);
@@ -334,35 +335,60 @@ __device__ __forceinline__ void lin_walk_to(const SSCoef<NS, NI>& c, const float
     }
 }
 
-// ---- pass 2: every chunk from its exact start: y, the squared error, the coefficient gradient; the last wave finishes ------
+// ---- pass 2: every chunk from its exact start: y, the loss sums, the coefficient gradient; the last wave finishes -----------
 // The chunk's exact start is made by the wave itself: Phi = {A^L, G_c} from L homogeneous steps, then the walk over the chunks
 // before it (their zero-state ends: pass 1) -- no separate walk launch.
-// part: double [waves][kG + 1] = {gA.., gBx.., gcy.., gdy.., SSE}; ticket: one word, left 0.
-// jac: double [ncoef (+1)][n_params] of ss_probe_kernel (rows in SSCoef order).  out: float [1 + n_params] = {SSE, dLoss/dparam}.
+// jac: double [ncoef (+1)][n_params] of ss_probe_kernel (rows in SSCoef order).  ticket: one word, left 0.
+//
+// LOSS = 0, the MSE: ONE family of weighted tangent sums, weight g = gscale (y - target).
+//   part: double [waves][kG + 1] = {gA.., gBx.., gcy.., gdy.., SSE}.  out: float [1 + n_params] = {SSE, dLoss/dparam};
+//   loss_out: (or NULL) <- gscale/2 x SSE; gcoef_out: (or NULL) float [kG] before the Jacobian.
+// LOSS = 1, the scripts' training loss, MSE + ESR on the rows t >= skip (clipper_pot.py:141-177,232,248; wdf_esr.h):
+//   ga and gb are functions of the GLOBAL S and E, so the pass carries TWO families -- P with weight e = y - target (unscaled:
+//   the MSE sums at gscale = 1), Q with weight y -- and the last wave combines them.  State, tangents and y advance on every
+//   row; rows before skip carry weight 0 through a wave-uniform select (a chunk wholly before skip contributes zeros), dead
+//   lanes carry weight 0.
+//   part: double [waves][2 (kG + 1)] = {GP[kG], S, GQ[kG], E}.
+//   sums: (or NULL) float [2 + 2 n_params] = {S, E, gP[n_params], gQ[n_params]} of THIS call, gP = GP . jac, gQ = GQ . jac: what
+//   several ranks all-reduce.  g_out: (or NULL) float [n_params] <- ga gP + gb gQ, the step finished as a single rank with
+//   esr_terms in fp64 from the double totals; loss3: (or NULL; with g_out) {mse, esr, mse + esr}.  gcoef_out: (or NULL) float
+//   [2 kG] = {GP, GQ} before the Jacobian.
+// The streamed pointers stay plain __restrict__ parameters (the prefetch needs its loads to move past the non-temporal y
+// stores); only what the tail touches travels in the loss's struct.
 #ifndef WDF_LIN_BLK
 #define WDF_LIN_BLK 8
 #endif
 constexpr int kLinBlk2 = WDF_LIN_BLK;                            // pass 2's block (steps whose loads are issued together)
+
+struct LinMse { float gscale; float* out; float* loss_out; };
+struct LinEsr { int64_t skip; double n_global, eps; float* sums; float* g_out; float* loss3; };
+template <int LOSS> struct LinLoss { using type = LinMse; };
+template <> struct LinLoss<1> { using type = LinEsr; };
+
+// the next block's x and target into xn / tn
 template <int NI, typename V>
-__device__ __forceinline__ void lin_load_x2(const float* __restrict__ x, int64_t B, int64_t b, int64_t t, int n, V (&xs)[kLinBlk2][NI])
+__device__ __forceinline__ void lin_load_blk(const float* __restrict__ x, const float* __restrict__ target, int64_t B, int64_t b,
+                                             int64_t ts, int64_t t1, V (&xn)[kLinBlk2][NI], V (&tn)[kLinBlk2])
 {
+    const int n = t1 - ts < kLinBlk2 ? (int)(t1 - ts) : kLinBlk2;
+    lin_load_x(x, B, b, ts, n, xn);
 #pragma unroll
-    for (int k = 0; k < kLinBlk2; ++k)
-#pragma unroll
-        for (int i = 0; i < NI; ++i) xs[k][i] = (k < n) ? lin_ld<V>(x + ((t + k) * NI + i) * B + b) : vsplat<V>(0.0f);
+    for (int i = 0; i < kLinBlk2; ++i) tn[i] = (i < n) ? lin_ld<V>(target + (ts + i) * B + b) : vsplat<V>(0.0f);
 }
 
-template <int NS, int NI, typename V>
+template <int NS, int NI, typename V, int LOSS>
 __global__ __launch_bounds__(64) void ss_lin_step_kernel(const float* __restrict__ x, const float* __restrict__ coef,
                                                          const float* __restrict__ uend0, const float* __restrict__ target,
-                                                         float gscale, float* __restrict__ y, double* __restrict__ part,
+                                                         float* __restrict__ y, double* __restrict__ part,
                                                          unsigned* __restrict__ ticket, const double* __restrict__ jac, int n_params,
-                                                         float* __restrict__ out, float* __restrict__ loss_out, float* __restrict__ gcoef_out, int64_t B, int64_t T,
-                                                         int64_t L, const float* __restrict__ z0, float* __restrict__ zT)
+                                                         float* __restrict__ gcoef_out, int64_t B, int64_t T, int64_t L,
+                                                         const float* __restrict__ z0, float* __restrict__ zT,
+                                                         const typename LinLoss<LOSS>::type a)
 {
     using U = LinU<NS, NI, V>;
     using C = SSCoef<NS, NI>;
     constexpr int W = LinWidth<V>::w;
+    constexpr int kG = U::kG, NF = LOSS ? 2 : 1, oQ = kG + 1, kP = NF * oQ;   // accumulators: {GP[kG], S} (then {GQ[kG], E})
     const V zero = vsplat<V>(0.0f);
     const int64_t b_raw = ((int64_t)blockIdx.x * 64 + threadIdx.x) * W;
     const bool live = b_raw < B;
@@ -379,175 +405,16 @@ __global__ __launch_bounds__(64) void ss_lin_step_kernel(const float* __restrict
         for (int s = 0; s < NS; ++s) u.z[s] = lin_ld<V>(z0 + s * B + b);
     }
     if (NS > 0 && k > 0) lin_walk_to<NS, NI, V>(c, uend0, B, b, k, L, u);
-    const float gs = live ? gscale : 0.0f, lv = live ? 1.0f : 0.0f;
-    double acc[U::kG + 1];
-#pragma unroll
-    for (int i = 0; i <= U::kG; ++i) acc[i] = 0.0;
-    // 8-step blocks, the next one's loads in flight under this one's arithmetic (a wave that loads, waits, computes keeps
-    // half as many bytes on their way)
-    V xn[kLinBlk2][NI], tn[kLinBlk2];
-    auto load_blk = [&](int64_t ts) {
-        const int n = t1 - ts < kLinBlk2 ? (int)(t1 - ts) : kLinBlk2;
-        lin_load_x2<NI, V>(x, B, b, ts, n, xn);
-#pragma unroll
-        for (int i = 0; i < kLinBlk2; ++i) tn[i] = (i < n) ? lin_ld<V>(target + (ts + i) * B + b) : zero;
-    };
-    load_blk(t0);
-    for (int64_t tb = t0; tb < t1; tb += 32) {                     // fp32 sums within 32 steps, fp64 across
-        V f[U::kG + 1];
-#pragma unroll
-        for (int i = 0; i <= U::kG; ++i) f[i] = zero;
-#pragma unroll 1
-        for (int64_t ts = tb; ts < tb + 32 && ts < t1; ts += kLinBlk2) {
-            const int n = t1 - ts < kLinBlk2 ? (int)(t1 - ts) : kLinBlk2;
-            V xs[kLinBlk2][NI], tg[kLinBlk2];
-#pragma unroll
-            for (int i = 0; i < kLinBlk2; ++i) {
-                tg[i] = tn[i];
-#pragma unroll
-                for (int j = 0; j < NI; ++j) xs[i][j] = xn[i][j];
-            }
-            if (ts + kLinBlk2 < t1) load_blk(ts + kLinBlk2);
-#pragma unroll
-            for (int i = 0; i < kLinBlk2; ++i) {
-                if (i >= n) break;
-                V yv = zero;
-#pragma unroll
-                for (int j = 0; j < NI; ++j) yv = vfma(c.v[C::oDy + j], xs[i][j], yv);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) yv = vfma(c.v[C::oCy + s], u.z[s], yv);
-                const V e = yv - tg[i];
-                const V g = e * gs;
-                if (live) lin_st_nt<V>(y + (ts + i) * B + b, yv);
-                f[U::kG] = vfma(e * lv, e, f[U::kG]);
-#pragma unroll
-                for (int cc = 0; cc < U::nA; ++cc) {
-                    V d = zero;
-#pragma unroll
-                    for (int s = 0; s < NS; ++s) d = vfma(c.v[C::oCy + s], u.SA[cc][s], d);
-                    f[cc] = vfma(g, d, f[cc]);
-                }
-#pragma unroll
-                for (int cc = 0; cc < U::nB; ++cc) {
-                    V d = zero;
-#pragma unroll
-                    for (int s = 0; s < NS; ++s) d = vfma(c.v[C::oCy + s], u.SB[cc][s], d);
-                    f[U::nA + cc] = vfma(g, d, f[U::nA + cc]);
-                }
-#pragma unroll
-                for (int s = 0; s < NS; ++s) f[U::nA + U::nB + s] = vfma(g, u.z[s], f[U::nA + U::nB + s]);
-#pragma unroll
-                for (int j = 0; j < NI; ++j) f[U::nA + U::nB + NS + j] = vfma(g, xs[i][j], f[U::nA + U::nB + NS + j]);
-                lin_u_step<NS, NI, V>(c, xs[i], u);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i <= U::kG; ++i) acc[i] += lin_hsum(f[i]);
-    }
-    if (NS > 0 && zT && t1 == T && live) {                          // the states the call ends in [NS][B] (never the z0 buffer)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) lin_st<V>(zT + s * B + b, u.z[s]);
-    }
-    // ---- this wave's partial; the last wave of the launch adds them up in a fixed order and applies the chain rule
-    const int64_t wave = (int64_t)blockIdx.y * gridDim.x + blockIdx.x, nwaves = (int64_t)gridDim.x * gridDim.y;
-#pragma unroll
-    for (int i = 0; i <= U::kG; ++i) {
-        const double s = wave_sum_dpp(acc[i]);
-        if (threadIdx.x == 0) __hip_atomic_store(part + wave * (U::kG + 1) + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned old = 0;
-    if (threadIdx.x == 0) old = atomicAdd(ticket, 1u);
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (old != (unsigned)(nwaves - 1)) return;
-    if (threadIdx.x == 0) *ticket = 0u;
-    double tot[U::kG + 1];
-#pragma unroll
-    for (int i = 0; i <= U::kG; ++i) {
-        double s = 0.0;
-        for (int64_t w = threadIdx.x; w < nwaves; w += 64)
-            s += __hip_atomic_load(part + w * (U::kG + 1) + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tot[i] = wave_sum_dpp(s);
-    }
-    // coefficient index (SSCoef order) of gradient entry i
-    const int p = threadIdx.x;
-    if (p < n_params) {
-        double gp = 0.0;
-#pragma unroll
-        for (int i = 0; i < U::kG; ++i) {
-            const int row = i < U::nA ? C::oA + i : (i < U::nA + U::nB ? C::oB + (i - U::nA)
-                                                     : (i < U::nA + U::nB + NS ? C::oCy + (i - U::nA - U::nB) : C::oDy + (i - U::nA - U::nB - NS)));
-            gp += tot[i] * jac[row * n_params + p];
-        }
-        out[1 + p] = (float)gp;
-    }
-    if (p == 0) {
-        out[0] = (float)tot[U::kG];
-        if (loss_out) *loss_out = (float)(0.5 * (double)gscale * tot[U::kG]);   // the mean squared error when gscale = 2 / (B T)
-        if (gcoef_out) {
-#pragma unroll
-            for (int i = 0; i < U::kG; ++i) gcoef_out[i] = (float)tot[i];
-        }
-    }
-}
-
-// the next block's x and target into xn / tn (what ss_lin_step_kernel's load_blk closure does, as a function)
-template <int NI, typename V>
-__device__ __forceinline__ void lin_load_blk2(const float* __restrict__ x, const float* __restrict__ target, int64_t B, int64_t b,
-                                              int64_t ts, int64_t t1, V (&xn)[kLinBlk2][NI], V (&tn)[kLinBlk2])
-{
-    const int n = t1 - ts < kLinBlk2 ? (int)(t1 - ts) : kLinBlk2;
-    lin_load_x2<NI, V>(x, B, b, ts, n, xn);
-#pragma unroll
-    for (int i = 0; i < kLinBlk2; ++i) tn[i] = (i < n) ? lin_ld<V>(target + (ts + i) * B + b) : vsplat<V>(0.0f);
-}
-
-// ---- pass 2 for the scripts' training loss: MSE + ESR on the rows t >= skip (clipper_pot.py:141-177,232,248) ------------------
-//     loss = S/n + sqrt(S / (E + eps) / n) ,  S = sum (y - target)^2 ,  E = sum y^2 ,  dLoss/dy = ga (y - target) + gb y
-// ga and gb are functions of the GLOBAL S and E, so the pass carries BOTH weighted sums of the tangents -- the P family with
-// weight e = y - target (unscaled: ss_lin_step_kernel's sums at gscale = 1), the Q family with weight y -- and the last wave
-// combines them.  A sibling of ss_lin_step_kernel, not a flag on it: the MSE kernels keep their code byte for byte.  Pass 1
-// (ss_lin_step_zero_kernel) and lin_walk_to are shared; state, tangents and y advance on every row as there.  Rows before skip
-// carry weight 0 through a wave-uniform select (a chunk wholly before skip contributes zeros), dead lanes carry weight 0.
-// part: double [waves][2 (kG + 1)] = {GP[kG], S, GQ[kG], E}; ticket: one word, left 0.
-// sums: (or NULL) float [2 + 2 n_params] = {S, E, gP[n_params], gQ[n_params]} of THIS call, gP = GP . jac, gQ = GQ . jac: what
-// several ranks all-reduce.  g: (or NULL) float [n_params] <- ga gP + gb gQ, the step finished as a single rank with
-// esr_coef_kernel's formulas in fp64 from the double totals (an ESR of 0 contributes 0); loss3: (or NULL; with g) {mse, esr,
-// mse + esr}.  gcoef_out: (or NULL) float [2 kG] = {GP, GQ} before the Jacobian.
-template <int NS, int NI, typename V>
-__global__ __launch_bounds__(64) void ss_lin_step_esr_kernel(const float* __restrict__ x, const float* __restrict__ coef,
-                                                             const float* __restrict__ uend0, const float* __restrict__ target,
-                                                             int64_t skip, double n_global, double eps, float* __restrict__ y,
-                                                             double* __restrict__ part, unsigned* __restrict__ ticket,
-                                                             const double* __restrict__ jac, int n_params, float* __restrict__ sums,
-                                                             float* __restrict__ g_out, float* __restrict__ loss3,
-                                                             float* __restrict__ gcoef_out, int64_t B, int64_t T, int64_t L,
-                                                             const float* __restrict__ z0, float* __restrict__ zT)
-{
-    using U = LinU<NS, NI, V>;
-    using C = SSCoef<NS, NI>;
-    constexpr int W = LinWidth<V>::w;
-    constexpr int kG = U::kG, kP = 2 * (kG + 1), oQ = kG + 1;     // accumulators: {GP[kG], S} then {GQ[kG], E}
-    const V zero = vsplat<V>(0.0f);
-    const int64_t b_raw = ((int64_t)blockIdx.x * 64 + threadIdx.x) * W;
-    const bool live = b_raw < B;
-    const int64_t b = live ? b_raw : B - W;
-    const int64_t k = blockIdx.y, t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
-    SSCoef<NS, NI> c;
-    c.load(coef);
-    U u;
-    u.zero();
-    if (NS > 0 && z0) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) u.z[s] = lin_ld<V>(z0 + s * B + b);
-    }
-    if (NS > 0 && k > 0) lin_walk_to<NS, NI, V>(c, uend0, B, b, k, L, u);
     const float lv = live ? 1.0f : 0.0f;
+    float gs = 0.0f;
+    if constexpr (LOSS == 0) gs = live ? a.gscale : 0.0f;
     double acc[kP];
 #pragma unroll
     for (int i = 0; i < kP; ++i) acc[i] = 0.0;
+    // 8-step blocks, the next one's loads in flight under this one's arithmetic (a wave that loads, waits, computes keeps
+    // half as many bytes on their way)
     V xn[kLinBlk2][NI], tn[kLinBlk2];
-    lin_load_blk2<NI, V>(x, target, B, b, t0, t1, xn, tn);
+    lin_load_blk<NI, V>(x, target, B, b, t0, t1, xn, tn);
     for (int64_t tb = t0; tb < t1; tb += 32) {                     // fp32 sums within 32 steps, fp64 across
         V f[kP];
 #pragma unroll
@@ -562,7 +429,7 @@ __global__ __launch_bounds__(64) void ss_lin_step_esr_kernel(const float* __rest
 #pragma unroll
                 for (int j = 0; j < NI; ++j) xs[i][j] = xn[i][j];
             }
-            if (ts + kLinBlk2 < t1) lin_load_blk2<NI, V>(x, target, B, b, ts + kLinBlk2, t1, xn, tn);
+            if (ts + kLinBlk2 < t1) lin_load_blk<NI, V>(x, target, B, b, ts + kLinBlk2, t1, xn, tn);
 #pragma unroll
             for (int i = 0; i < kLinBlk2; ++i) {
                 if (i >= n) break;
@@ -573,39 +440,46 @@ __global__ __launch_bounds__(64) void ss_lin_step_esr_kernel(const float* __rest
                 for (int s = 0; s < NS; ++s) yv = vfma(c.v[C::oCy + s], u.z[s], yv);
                 const V e = yv - tg[i];
                 if (live) lin_st_nt<V>(y + (ts + i) * B + b, yv);
-                // rows before skip: the weights themselves are 0, by a select (ts, i, skip are the same in every lane) -- not
-                // 0 x e, which would let a NaN or Inf in a skipped row of target (padding) into every sum
-                const bool on = ts + i >= skip;
-                const V es = on ? e : zero;
-                const V ge = es * lv, gy = on ? yv * lv : zero;
-                f[kG] = vfma(ge, es, f[kG]);
-                f[oQ + kG] = vfma(gy, yv, f[oQ + kG]);
+                V w[NF];                                          // the families' weights on this row's tangents
+                if constexpr (LOSS == 0) {
+                    w[0] = e * gs;
+                    f[kG] = vfma(e * lv, e, f[kG]);
+                } else {
+                    // rows before skip: the weights themselves are 0, by a select (ts, i, skip are the same in every lane) -- not
+                    // 0 x e, which would let a NaN or Inf in a skipped row of target (padding) into every sum
+                    const bool on = ts + i >= a.skip;
+                    const V es = on ? e : zero;
+                    w[0] = es * lv;
+                    w[1] = on ? yv * lv : zero;
+                    f[kG] = vfma(w[0], es, f[kG]);
+                    f[oQ + kG] = vfma(w[1], yv, f[oQ + kG]);
+                }
+                // entry r of every family += weight x (dy/d coefficient r), each inner product formed once
 #pragma unroll
                 for (int cc = 0; cc < U::nA; ++cc) {
                     V d = zero;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) d = vfma(c.v[C::oCy + s], u.SA[cc][s], d);
-                    f[cc] = vfma(ge, d, f[cc]);
-                    f[oQ + cc] = vfma(gy, d, f[oQ + cc]);
+#pragma unroll
+                    for (int q = 0; q < NF; ++q) f[q * oQ + cc] = vfma(w[q], d, f[q * oQ + cc]);
                 }
 #pragma unroll
                 for (int cc = 0; cc < U::nB; ++cc) {
                     V d = zero;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) d = vfma(c.v[C::oCy + s], u.SB[cc][s], d);
-                    f[U::nA + cc] = vfma(ge, d, f[U::nA + cc]);
-                    f[oQ + U::nA + cc] = vfma(gy, d, f[oQ + U::nA + cc]);
+#pragma unroll
+                    for (int q = 0; q < NF; ++q) f[q * oQ + U::nA + cc] = vfma(w[q], d, f[q * oQ + U::nA + cc]);
                 }
 #pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    f[U::nA + U::nB + s] = vfma(ge, u.z[s], f[U::nA + U::nB + s]);
-                    f[oQ + U::nA + U::nB + s] = vfma(gy, u.z[s], f[oQ + U::nA + U::nB + s]);
-                }
+                for (int s = 0; s < NS; ++s)
 #pragma unroll
-                for (int j = 0; j < NI; ++j) {
-                    f[U::nA + U::nB + NS + j] = vfma(ge, xs[i][j], f[U::nA + U::nB + NS + j]);
-                    f[oQ + U::nA + U::nB + NS + j] = vfma(gy, xs[i][j], f[oQ + U::nA + U::nB + NS + j]);
-                }
+                    for (int q = 0; q < NF; ++q) f[q * oQ + U::nA + U::nB + s] = vfma(w[q], u.z[s], f[q * oQ + U::nA + U::nB + s]);
+#pragma unroll
+                for (int j = 0; j < NI; ++j)
+#pragma unroll
+                    for (int q = 0; q < NF; ++q)
+                        f[q * oQ + U::nA + U::nB + NS + j] = vfma(w[q], xs[i][j], f[q * oQ + U::nA + U::nB + NS + j]);
                 lin_u_step<NS, NI, V>(c, xs[i], u);
             }
         }
@@ -616,8 +490,8 @@ __global__ __launch_bounds__(64) void ss_lin_step_esr_kernel(const float* __rest
 #pragma unroll
         for (int s = 0; s < NS; ++s) lin_st<V>(zT + s * B + b, u.z[s]);
     }
-    // ---- this wave's partial; the last wave of the launch (the counted ticket of ss_lin_step_kernel: no wait on anything) adds
-    // them up in wave order, so the results repeat bit for bit, and finishes the step
+    // ---- this wave's partial; the last wave of the launch (a counted ticket: no wait on anything) adds them up in wave order,
+    // so the results repeat bit for bit, and finishes the step
     const int64_t wave = (int64_t)blockIdx.y * gridDim.x + blockIdx.x, nwaves = (int64_t)gridDim.x * gridDim.y;
 #pragma unroll
     for (int i = 0; i < kP; ++i) {
@@ -641,60 +515,56 @@ __global__ __launch_bounds__(64) void ss_lin_step_esr_kernel(const float* __rest
     }
 #pragma unroll
     for (int i = 0; i < kP; ++i) tot[i] = wave_sum_dpp(tot[i]);
-    const double S = tot[kG], E = tot[oQ + kG];
+    // the chain rule: lane p contracts every family with column p of the Jacobian (entry i is row `row` in SSCoef order)
     const int p = threadIdx.x;
+    double gp[NF];
+#pragma unroll
+    for (int q = 0; q < NF; ++q) gp[q] = 0.0;
     if (p < n_params) {
-        double gP = 0.0, gQ = 0.0;
 #pragma unroll
         for (int i = 0; i < kG; ++i) {
             const int row = i < U::nA ? C::oA + i : (i < U::nA + U::nB ? C::oB + (i - U::nA)
                                                      : (i < U::nA + U::nB + NS ? C::oCy + (i - U::nA - U::nB) : C::oDy + (i - U::nA - U::nB - NS)));
             const double j = jac[row * n_params + p];
-            gP += tot[i] * j;
-            gQ += tot[oQ + i] * j;
-        }
-        if (sums) {
-            sums[2 + p] = (float)gP;
-            sums[2 + n_params + p] = (float)gQ;
-        }
-        if (g_out) {
-            const double Ee = E + eps, esr = sqrt(S / Ee / n_global);
-            const double ga = 2.0 / n_global + (esr > 0.0 ? 1.0 / (esr * Ee * n_global) : 0.0), gb = -esr / Ee;
-            g_out[p] = (float)(ga * gP + gb * gQ);
+#pragma unroll
+            for (int q = 0; q < NF; ++q) gp[q] += tot[q * oQ + i] * j;
         }
     }
-    if (p == 0) {
-        if (sums) {
-            sums[0] = (float)S;
-            sums[1] = (float)E;
+    if constexpr (LOSS == 0) {
+        if (p < n_params) a.out[1 + p] = (float)gp[0];
+        if (p == 0) {
+            a.out[0] = (float)tot[kG];
+            if (a.loss_out) *a.loss_out = (float)(0.5 * (double)a.gscale * tot[kG]);   // the mean squared error when gscale = 2 / (B T)
         }
-        if (g_out && loss3) {
-            const double mse = S / n_global, esr = sqrt(S / (E + eps) / n_global);
-            loss3[0] = (float)mse;
-            loss3[1] = (float)esr;
-            loss3[2] = (float)(mse + esr);
+    } else {
+        const double S = tot[kG], E = tot[oQ + kG];
+        if (a.sums) {
+            if (p < n_params) {
+                a.sums[2 + p] = (float)gp[0];
+                a.sums[2 + n_params + p] = (float)gp[1];
+            }
+            if (p == 0) {
+                a.sums[0] = (float)S;
+                a.sums[1] = (float)E;
+            }
         }
-        if (gcoef_out) {
-#pragma unroll
-            for (int i = 0; i < kG; ++i) {
-                gcoef_out[i] = (float)tot[i];
-                gcoef_out[kG + i] = (float)tot[oQ + i];
+        if (a.g_out) {
+            const EsrTerms lt = esr_terms(S, E + a.eps, a.n_global);
+            const double ga = lt.ga, gb = lt.gb, gP = gp[0], gQ = gp[1];
+            if (p < n_params) a.g_out[p] = (float)(ga * gP + gb * gQ);
+            if (p == 0 && a.loss3) {
+                a.loss3[0] = (float)lt.mse;
+                a.loss3[1] = (float)lt.esr;
+                a.loss3[2] = (float)(lt.mse + lt.esr);
             }
         }
     }
-}
-
-// Several ranks: sums = {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> the global loss and its gradient (the
-// single-rank finish's formulas, on the floats).  One wave, lane p owns parameter p.
-static __global__ __launch_bounds__(64) void ss_lin_esr_finish_kernel(const float* __restrict__ sums, int n_params, double n, double eps,
-                                                                      float* __restrict__ g, float* __restrict__ loss3)
-{
-    const double S = sums[0], E = (double)sums[1] + eps;
-    const double mse = S / n, esr = sqrt(S / E / n);
-    const double ga = 2.0 / n + (esr > 0.0 ? 1.0 / (esr * E * n) : 0.0), gb = -esr / E;
-    const int p = threadIdx.x;
-    if (p < n_params) g[p] = (float)(ga * (double)sums[2 + p] + gb * (double)sums[2 + n_params + p]);
-    if (p == 0 && loss3) { loss3[0] = (float)mse; loss3[1] = (float)esr; loss3[2] = (float)(mse + esr); }
+    if (p == 0 && gcoef_out) {
+#pragma unroll
+        for (int q = 0; q < NF; ++q)
+#pragma unroll
+            for (int i = 0; i < kG; ++i) gcoef_out[q * kG + i] = (float)tot[q * oQ + i];
+    }
 }
 
 }  // namespace wdf

@@ -78,7 +78,7 @@ def barrier():
 
 
 def esr_coefficients(S, E, n, eps):
-    """Host mirror of esr_coef_kernel (csrc/wdf_clipper.h): from the GLOBAL sums S = sum (y-t)^2,
+    """Host mirror of esr_terms (csrc/wdf_esr.h): from the GLOBAL sums S = sum (y-t)^2,
     E = sum y^2 over n samples -> (ga, gb, mse, esr) with dL/dy = ga (y - t) + gb y for
     L = S/n + sqrt(S / (E + eps) / n)   (clipper_pot.py:146-156,177)."""
     E = E + eps

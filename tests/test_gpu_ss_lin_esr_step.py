@@ -9,7 +9,8 @@ tests/test_ss_lin_esr_ref_cpu.py, which also asserts the caps and the absence of
   C  chunk geometry (T, k) in {(33, 2), (65, 3), (1000, 5), (2048, 64)} on (2,1), both lane widths;
   D  z0 / zT handed across two calls on (2,2), against the references of the halves and one call of double length;
   E  the finish: 1 and 15 parameters, an n_global larger than the call's own n, esr = 0, g == NULL, two half-batch calls + finish,
-     the same bits on a reused workspace and the ticket left 0, the MSE step's SSE and gcoef at skip = 0, the wrapper's refusals.
+     the same bits on a reused workspace and the ticket left 0, the MSE step's SSE and gcoef at skip = 0, the wrapper's refusals,
+     the three families' finish exports giving the same bits on the same sums (one kernel) within one fp32 ulp of dist.py.
 
 Bounds (none relative to a gradient entry, none taken from what the kernel gives):
   y, zT        3e-6 max(1, max |ref|)            tests/test_gpu_ss_lin_step_kernel.py's row for this arithmetic
@@ -26,7 +27,9 @@ Every check prints `FIG <section> | <case> | ...` with each error divided by its
 
 Also in E: NaN and Inf in the rows of target before skip leave every output bit for bit what a clean target gives.
 
-Measured on an MI355X (worst figure of each section, error / bound; 70 tests, all passing, 3.2 s in all):
+Measured on an MI355X (worst figure of each section, error / bound; 74 tests, all passing, 3.1 s in all; the figures below are
+the same on the build with two pass-2 kernels and on the one with ss_lin_step_kernel<NS, NI, V, LOSS> alone: the outputs are the
+same bytes; the three finish exports against dist.py, of one fp32 ulp: g 0.41, loss3 0.46):
   A  y 0.049  S 0.012  E 0.011  GP 0.109  GQ 0.136 (B = 1, T = 40)  gP 0.015  gQ 0.016  g 0.009  g_own 0.428  loss3 0.010  zT 0.025
   B  y 0.049  S 0.006  E 0.005  GP 0.017  GQ 0.020  g 0.006  g_own 0.522 ((2,2) B = 65 skip = 1)  loss3 0.006  zT 0.025
   C  y 0.043  S 0.009  E 0.005  GP 0.051  GQ 0.047  gP 0.031  g 0.016  g_own 0.398  loss3 0.009
@@ -281,6 +284,35 @@ def test_e_two_half_batches_and_the_finish_launch():
     print(f"FIG E | halves + finish | g={fg:.3f} loss3={fl:.3f}")
     assert fg <= 1.0 and fl <= 1.0
     assert np.abs(tt[:2] - whole["sums"].cpu().numpy()[:2].astype(np.float64)).max() <= 3 * u * tt[:2].max()
+
+
+FINISH_GP = [0.5, -1.25, 2.0, 0.03125, -3.0, 0.75]
+FINISH_GQ = [1.5, -0.75, 0.25, 0.5, 0.125, -2.5]
+
+
+@pytest.mark.parametrize("S", [3.5, 0.0], ids=["S3.5", "S0"])
+@pytest.mark.parametrize("P", [4, 6], ids=["clipper-4", "asym-6"])
+def test_e_the_three_finish_exports_are_one_kernel(P, S):
+    """{S, E, gP[P], gQ[P]} through the family's own finish export (wdf_esr_finish: 4 entries, wdf_asym_esr_finish: 6) and through
+    wdf_ss_lin_esr_finish with n_params = P: g and loss3 BIT FOR BIT (one kernel, csrc/wdf_esr.h), and both within one fp32 ulp of
+    dist.esr_coefficients in float64 (the device rounds an fp64 result once; no term of g cancels here: |gb gQ| < |ga gP| / 3).
+    S = 0: esr = 0 contributes 0 to ga -- g = 2/n gP exactly, loss3 = 0, nothing NaN."""
+    from wdf_hip import binding as wb, dist
+    n, eps = 1000.0, wb.ESR_EPS
+    sums = np.array([S, 120.25] + FINISH_GP[:P] + FINISH_GQ[:P], dtype=np.float32)
+    own = wb.esr_finish if P == 4 else wb.asym_esr_finish
+    g1, l1 = own(cuda(sums), n, eps)
+    g2, l2 = wb.ss_lin_esr_finish(cuda(sums), n, eps)
+    assert torch.equal(g1.view(torch.int32), g2.view(torch.int32)) and torch.equal(l1.view(torch.int32), l2.view(torch.int32))
+    s64 = sums.astype(np.float64)
+    ga, gb, mse, esr = dist.esr_coefficients(s64[0], s64[1], n, eps)
+    g_ref, l_ref = ga * s64[2:2 + P] + gb * s64[2 + P:], np.array([mse, esr, mse + esr])
+    g, l3 = g2.cpu().numpy().astype(np.float64), l2.cpu().numpy().astype(np.float64)
+    fg, fl = ratio(np.abs(g - g_ref), ulp32(g_ref)), ratio(np.abs(l3 - l_ref), ulp32(l_ref))
+    print(f"FIG E | one finish kernel P={P} S={S} | g={fg:.3f} loss3={fl:.3f}")
+    assert np.all(np.isfinite(g)) and np.all(np.isfinite(l3)) and fg <= 1.0 and fl <= 1.0
+    if S == 0.0:
+        assert np.all(l3 == 0) and np.array_equal(g2.cpu().numpy(), (2.0 / n * s64[2:2 + P]).astype(np.float32))
 
 
 @pytest.mark.parametrize("B,T,k", E.SHAPES_B, ids=["one-B65", "two-B130"])

@@ -121,8 +121,58 @@ def work(shape):
     return 0
 
 
+def kernels(shape):
+    """--kernel: pass 2 alone (ss_lin_step_kernel, between the events the C call brackets it with) through binding.ss_lin_step_mse /
+    ss_lin_step_esr on the two-capacitor instantiations no circuit of this tool reaches: (2,2) at one and two sequences per lane,
+    (2,1) at two; one per lane is chosen by a y buffer at 4 mod 8 bytes.  One JSON row per (tree, width, loss), nothing written."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(_R, "differentiable-wdfs_amd", "lib"))
+    from wdf_hip import binding as wb
+
+    B, T = (int(v) for v in shape.split("x"))
+    wb.require_gpu()
+    rng = np.random.default_rng(11)
+    target = torch.as_tensor(rng.standard_normal((T, B)).astype(np.float32), device="cuda")
+    for ns, ni, width in ((2, 2, 1), (2, 2, 2), (2, 1, 2)):
+        q = np.array([[1.0, 0.4], [-0.3, 1.0]])
+        A = q @ np.diag([0.98, 0.6]) @ np.linalg.inv(q)
+        n_coef = wb.lib().wdf_ss_ncoef(ns, ni)
+        coef = np.zeros(n_coef + 1)                              # SSCoef order: A, Bx, E, ca, da, cy, dy, fy (+ the port resistance)
+        coef[:ns * ns] = A.reshape(-1)
+        coef[ns * ns:ns * ns + ns * ni] = 0.02 * rng.uniform(-1.0, 1.0, ns * ni)
+        o_cy = ns * ns + ns * ni + 2 * ns + ni
+        coef[o_cy:o_cy + ns + ni] = rng.uniform(-1.0, 1.0, ns + ni)
+        coef_d = torch.as_tensor(coef.astype(np.float32), device="cuda")
+        jac = torch.as_tensor(rng.uniform(-1.0, 1.0, (n_coef + 1, 3)), device="cuda")
+        x = torch.as_tensor(rng.standard_normal((T, ni, B)).astype(np.float32), device="cuda")
+        y = torch.empty((T * B + 2,), dtype=torch.float32, device="cuda")[(2 if width == 2 else 1):][:T * B].view(T, B)
+        assert y.data_ptr() % 8 == (0 if width == 2 else 4)
+        n_chunks = max(1, min(T // 32, (4 * 256 * 64 * width) // B))
+        steps = {"mse": lambda ws: wb.ss_lin_step_mse(x, coef_d, jac, target, 2.0 / (B * T), n_chunks, ws=ws, y=y),
+                 "mse+esr": lambda ws: wb.ss_lin_step_esr(x, coef_d, jac, target, SKIP, n_chunks, ws=ws, y=y)}
+        for loss, fn in steps.items():
+            ws = fn(None)["ws"]
+            for _ in range(WARMUP):
+                fn(ws)
+            ms = []
+            for _ in range(REPS):
+                e0, e1 = wb.Event(), wb.Event()
+                wb.Event.bracket_next(e0, e1)
+                fn(ws)
+                torch.cuda.synchronize()
+                ms.append(e0.elapsed_ms(e1))
+            print(json.dumps({"kernel": f"ss_lin_step_kernel<{ns},{ni},{'v2f' if width == 2 else 'float'}>", "loss": loss, "B": B, "T": T,
+                              "n_chunks": n_chunks, "ms": float(np.median(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms)),
+                              "reps": len(ms)}), flush=True)
+    return 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--shape", choices=SHAPES, help="worker: time this shape's three rows in this process")
+    ap.add_argument("--kernel", action="store_true", help="with --shape: time pass 2 alone on the two-capacitor instantiations instead")
     a = ap.parse_args()
-    sys.exit(work(a.shape) if a.shape else drive())
+    if a.kernel and not a.shape:
+        ap.error("--kernel needs --shape")
+    sys.exit((kernels(a.shape) if a.kernel else work(a.shape)) if a.shape else drive())
