@@ -50,6 +50,160 @@ class WdfHipError(RuntimeError):
 _lib = None
 
 
+# ---- the C ABI, once: name -> (restype, argtypes) of every declaration in include/wdf_hip.h (tests/test_cabi_cpu.py compares
+# the two, parameter by parameter) ------------------------------------------------------------------------------------------
+_p, _i64, _ci, _cf, _cd, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_size_t
+_ip, _dp, _i64p, _f32p = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+_ADAM = [_p, _p, _p, _p, _cf, _cf, _cf, _p, _p]                        # m, v, step, lr, beta1, beta2, eps, lo, hi
+_CLIP = [_p, _p, _p, _cf, _ci, _ci]                                    # x, r, theta, fs, n_up, n_down
+_ASYM = [_p, _p, _cf, _ci, _cd, _ci]                                   # x, theta6, fs, mode, tol, max_iter
+_MLP = [_p, _p, _p, _p, _ci, _ci, _cf]                                 # x, r, theta2, w, hidden, n_tanh_layers, fs
+_SS = [_p, _p, _p, _ci, _ci, _ci, _ci, _ci]                            # x, coef, rootp, ns, ni, root, n_up, n_down
+_DYN = [_p, _p, _ci, _ci, _ci, _ci, _p, _p, _ci, _ci, _ci, _ci]        # x, rows, per_sample, ns, ni, root, rootp, w, hidden, n_tanh_layers, n_up, n_down
+_STEP_WS = [_ci, _ci, _i64, _i64, _ci]                                 # ns, ni, B, T, n_chunks
+_PROBE = [_p, _ci, _p, _p, _ci, _p, _ci, _p, _p, _p, _p]               # tape, n_ops, consts, params, n_params, outs, n_out, coef, coef64, jac, stream
+_ROWS = [_ip, _ci, _dp, _ci, _ip, _ci, _p, _ci, _ci, _p]               # ops, n_ops, consts, n_consts, outs, n_out, params, n_params, chan, r
+
+SIGNATURES = {
+    "wdf_abi_version": (_ci, []),
+    "wdf_last_error": (C.c_char_p, []),
+    "wdf_device_info": (_ci, [_ci, C.c_char_p, _ci]),
+    "wdf_clipper_fwd": (_ci, _CLIP + [_p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_clipper_bwd": (_ci, _CLIP + [_p, _p, _p, _p, _p, _p, _ci, _i64, _i64, _ci, _p]),
+    "wdf_clipper_bwd_ws_bytes": (_sz, [_i64]),
+    "wdf_clipper_tp_chunks": (_ci, [_i64, _ci]),
+    "wdf_clipper_tp_warm_unit": (_ci, []),
+    "wdf_clipper_fwd_tp_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_fwd_tp": (_ci, _CLIP + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _ci, _p]),
+    "wdf_clipper_fwd_tp_state_bytes": (_sz, [_i64, _ci, _ci]),
+    "wdf_clipper_fwd_tp_state_reset": (_ci, [_p, _i64, _ci, _p]),
+    "wdf_clipper_fwd_tp_warm": (_ci, _CLIP + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _ci, _ci, _p]),
+    "wdf_clipper_bwd_tp_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_bwd_tp_ws_init": (_ci, [_p, _i64, _ci, _p]),
+    "wdf_clipper_bwd_tp": (_ci, _CLIP + [_p, _p, _p, _p, _p, _ci, _i64, _i64, _ci, _ci, _p]),
+    "wdf_clipper_bwd_mse_tp": (_ci, _CLIP + [_p, _p, _p, _cf, _p, _p, _p, _p, _ci, _i64, _i64, _ci, _ci, _p]),
+    "wdf_clipper_bwd_mse_tp_adam": (_ci, _CLIP + [_p, _p, _p, _cf, _p, _p, _p, _i64, _i64, _ci, _ci] + _ADAM + [_p]),
+    "wdf_clipper_step_mse_tp_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_step_mse_tp_ws_init": (_ci, [_p, _i64, _ci, _p]),
+    "wdf_clipper_step_mse_tp": (_ci, _CLIP + [_p, _cf, _i64, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _ci, _p, _p, _ci]
+                                + _ADAM + [_ci, _p]),
+    "wdf_clipper_step_esr_tp": (_ci, _CLIP + [_p, _cd, _cd, _i64, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _ci, _p, _p, _p]
+                                + _ADAM + [_ci, _p]),
+    "wdf_esr_finish": (_ci, [_p, _cd, _cd, _p, _p, _p]),
+    "wdf_loss_sums_ws_bytes": (_i64, []),
+    "wdf_loss_sums": (_ci, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "wdf_esr_coef": (_ci, [_p, _cd, _cd, _p, _p, _p]),
+    "wdf_loss_esr_grad": (_ci, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "wdf_loss_terms_ws_bytes": (_i64, []),
+    "wdf_loss_terms_sums": (_ci, [_p, _p, _i64, _i64, _i64, _cd, _p, _p, _p]),
+    "wdf_loss_terms_coef": (_ci, [_p, _cd, _cd, _dp, _cd, _p, _p, _p]),
+    "wdf_loss_terms_grad": (_ci, [_p, _p, _p, _cd, _i64, _i64, _i64, _p, _p]),
+    "wdf_clipper_bwd_esr_tp": (_ci, _CLIP + [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _ci, _i64, _i64, _ci, _ci, _p]),
+    "wdf_clipper_asym_fwd": (_ci, _ASYM + [_p, _p, _p, _p, _p, _i64, _i64, _p]),
+    "wdf_clipper_asym_fwd_tp_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_asym_fwd_tp": (_ci, _ASYM + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p]),
+    "wdf_clipper_asym_bwd_ws_bytes": (_sz, [_i64]),
+    "wdf_clipper_asym_bwd": (_ci, [_p, _p, _cf, _cd, _ci, _p, _p, _p, _p, _i64, _i64, _p]),
+    "wdf_clipper_asym_bwd_tp_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_asym_bwd_tp": (_ci, [_p, _p, _cf, _ci, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_asym_root": (_ci, _ASYM + [_p, _i64, _p]),
+    "wdf_clipper_asym_step_mse_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_asym_step_mse": (_ci, _ASYM + [_p, _cf, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p] + _ADAM + [_p]),
+    "wdf_clipper_asym_step_esr_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_asym_step_esr": (_ci, _ASYM + [_p, _cd, _cd, _i64, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p, _p]
+                                  + _ADAM + [_p]),
+    "wdf_asym_esr_finish": (_ci, [_p, _cd, _cd, _p, _p, _p]),
+    "wdf_ss_dyn_row_len": (_ci, [_ci, _ci]),
+    "wdf_ss_dyn_fwd": (_ci, _DYN + [_p, _p, _p, _p, _i64, _i64, _p]),
+    "wdf_ss_dyn_bwd_ws_bytes": (_sz, [_i64]),
+    "wdf_ss_dyn_bwd_root_ws_bytes": (_sz, [_ci, _i64]),
+    "wdf_ss_dyn_bwd_tp_root_ws_bytes": (_sz, [_ci, _ci, _i64, _i64, _ci]),
+    "wdf_ss_dyn_bwd": (_ci, _DYN + [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),
+    "wdf_ss_dyn_fwd_tp_ws_bytes": (_sz, [_ci, _i64, _ci]),
+    "wdf_ss_dyn_fwd_tp": (_ci, _DYN + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p]),
+    "wdf_ss_dyn_bwd_tp_ws_bytes": (_sz, [_ci, _i64, _i64, _ci]),
+    "wdf_ss_dyn_bwd_tp": (_ci, _DYN + [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_dyn_rows": (_ci, _ROWS + [_p, _i64, _i64, _p]),
+    "wdf_ss_dyn_rows_bwd_ws_bytes": (_sz, [_ci, _i64, _i64]),
+    "wdf_ss_dyn_rows_bwd": (_ci, _ROWS + [_p, _p, _p, _i64, _i64, _p]),
+    "wdf_clipper_mlp_wgrad_matrix_core_chunks": (_ci, [_i64, _i64]),
+    "wdf_mlp_weight_count": (_ci, [_ci, _ci]),
+    "wdf_clipper_mlp_fwd": (_ci, _MLP + [_p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_clipper_mlp_bwd_w_ws_bytes": (_i64, [_ci, _ci, _i64]),
+    "wdf_clipper_mlp_bwd_w": (_ci, _MLP + [_p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_clipper_mlp_tp_chunks": (_ci, [_i64, _ci]),
+    "wdf_clipper_mlp_fwd_tp_ws_bytes": (_sz, [_i64, _ci]),
+    "wdf_clipper_mlp_fwd_tp": (_ci, _MLP + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _p, _cf, _p, _p, _p]),
+    "wdf_clipper_mlp_bwd_w_tp_ws_bytes": (_i64, [_ci, _ci, _i64, _i64, _ci]),
+    "wdf_clipper_mlp_bwd_w_tp": (_ci, _MLP + [_p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_clipper_mlp_fwd_tp_kappa": (_ci, _MLP + [_p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _ci, _p, _cf, _p, _p, _p]),
+    "wdf_clipper_mlp_tp_starts": (_ci, [_i64, _ci, _ci, _i64p]),
+    "wdf_clipper_mlp_bwd_w_tp_kappa": (_ci, _MLP + [_p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_clipper_mlp_bwd_ws_bytes": (_sz, [_i64]),
+    "wdf_clipper_mlp_bwd": (_ci, _MLP + [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_mlp_eval": (_ci, [_p, _p, _p, _ci, _ci, _p, _i64, _p]),
+    "wdf_mlp_fit_epoch": (_ci, [_p, _p, _p, _i64, _ci, _p, _p, _p, _p, _cf, _cf, _cf, _cf, _cf, _cf, _p, _ci, _ci, _p]),
+    "wdf_clipper_mlp_wgrad_ws_bytes": (_i64, [_ci, _ci, _i64]),
+    "wdf_clipper_mlp_wgrad": (_ci, [_p, _p, _p, _p, _p, _ci, _ci, _cf, _p, _p, _i64, _p]),
+    "wdf_clipper_mlp_step_state_bytes": (_sz, [_ci, _ci, _i64, _i64, _ci, _ci]),
+    "wdf_clipper_mlp_step_plan": (_ci, [_p, _ci, _ci, _i64, _i64, _ci, _ci, _ip, _ci, _ci, _ci, _ci, _ci, _cf, _p]),
+    "wdf_clipper_mlp_step_read": (_ci, [_p, _ci, _ci, _i64, _i64, _ci, _ci, _ip, _ip, _ip, _ip, _f32p, _p]),
+    "wdf_clipper_mlp_step_set": (_ci, [_p, _ci, C.c_int32, _p]),
+    "wdf_clipper_mlp_step_set_wcol": (_ci, [_p, _ci, _ci, _i64, _i64, _ci, _ci, _ip, _p]),
+    "wdf_clipper_mlp_step_prepare": (_ci, [_p, _p, _cf, _i64, _i64, _p, _p, _p]),
+    "wdf_clipper_mlp_step": (_ci, [_p, _p, _p, _p, _p, _ci, _ci, _ci, _cf, _p, _i64, _cd, _cd, _p, _p, _p, _p, _i64, _i64, _ci, _ci, _ci,
+                                   _p, _p, _p, _p, _p, _p, _p, _p, _cf, _cf, _cf, _p]),
+    "wdf_ss_probe": (_ci, _PROBE),
+    "wdf_ss_probe_adam": (_ci, [_p, _ci] + _PROBE),
+    "wdf_ss_lin_step_ws_bytes": (_sz, _STEP_WS),
+    "wdf_ss_lin_step_mse": (_ci, [_p, _p, _p, _ci, _ci, _ci, _p, _cf, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p, _p, _p]),
+    "wdf_ss_lin_step_esr_ws_bytes": (_sz, _STEP_WS),
+    "wdf_ss_lin_step_esr": (_ci, [_p, _p, _p, _ci, _ci, _ci, _p, _cd, _cd, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p, _p, _p]),
+    "wdf_ss_lin_esr_finish": (_ci, [_p, _ci, _cd, _cd, _p, _p, _p]),
+    "wdf_ss_nl_step_ws_bytes": (_sz, _STEP_WS),
+    "wdf_ss_nl_step_chunk_len": (_ci, [_i64, _ci]),
+    "wdf_ss_nl_step_plan": (_ci, [_p, _ci, _ci, _i64, _i64, _ci, _ci, _ci, _ci, _ci, _cf, _p]),
+    "wdf_ss_nl_step_set": (_ci, [_p, _ci, _cd, _p]),
+    "wdf_ss_nl_step_read": (_ci, [_p, _p, _p]),
+    "wdf_ss_nl_step_mse": (_ci, [_p, _p, _p, _p, _ci, _ci, _ci, _ci, _ci, _p, _cf, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_nl_step_esr_ws_bytes": (_sz, _STEP_WS),
+    "wdf_ss_nl_step_esr": (_ci, [_p, _p, _p, _p, _ci, _ci, _ci, _ci, _ci, _p, _i64, _cd, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_ncoef": (_ci, [_ci, _ci]),
+    "wdf_ss_fwd": (_ci, _SS + [_p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_fwd_lin_tp_ws_bytes": (_sz, [_ci, _i64, _ci]),
+    "wdf_ss_fwd_lin_tp": (_ci, [_p, _p, _ci, _ci, _p, _p, _p, _p, _i64, _i64, _ci, _p, _p]),
+    "wdf_ss_bwd": (_ci, _SS + [_p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_bwd_ws_bytes": (_sz, [_ci, _ci, _i64]),
+    "wdf_ss_tp_chunks": (_ci, [_i64, _ci]),
+    "wdf_ss_tp_starts": (_ci, [_i64, _ci, _ci, _i64p]),
+    "wdf_ss_fwd_tp_ws_bytes": (_sz, [_ci, _i64, _ci]),
+    "wdf_ss_fwd_tp": (_ci, [_p, _p, _p, _ci, _ci, _ci, _ci, _p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p]),
+    "wdf_ss_fwd_tp_root": (_ci, _SS + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p]),
+    "wdf_ss_bwd_tp_ws_bytes": (_sz, [_ci, _ci, _i64, _ci]),
+    "wdf_ss_bwd_tp": (_ci, _SS + [_p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_asym_step_ws_bytes": (_sz, _STEP_WS),
+    "wdf_ss_asym_step_esr_ws_bytes": (_sz, _STEP_WS),
+    "wdf_ss_asym_step_mse": (_ci, [_p, _p, _p, _ci, _ci, _p, _cf, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p]),
+    "wdf_ss_asym_step_esr": (_ci, [_p, _p, _p, _ci, _ci, _p, _cd, _cd, _i64, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p, _p, _p]),
+    "wdf_omega_f32": (_ci, [_p, _p, _p, _i64, _p]),
+    "wdf_omega_f64": (_ci, [_p, _p, _p, _i64, _p]),
+    "wdf_diode_pair_f32": (_ci, [_p, _p, _cf, _cf, _ci, _ci, _p, _i64, _p]),
+    "wdf_adam_step": (_ci, [_p, _p] + _ADAM + [_ci, _p]),
+    "wdf_adam_step_multi": (_ci, [_p, _ci, _p]),
+    "wdf_event_create": (_p, []),
+    "wdf_event_record": (_ci, [_p, _p]),
+    "wdf_event_elapsed_ms": (_ci, [_p, _p, _f32p]),
+    "wdf_event_destroy": (None, [_p]),
+    "wdf_event_bracket_next": (None, [_p, _p]),
+    "wdf_clock_stamp": (_ci, [_p, _p]),
+}
+# one pot resistance per sequence: the static twins' argument lists with rseq behind x
+for _twin in ("wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_tp", "wdf_clipper_asym_step_mse",
+              "wdf_clipper_asym_step_esr"):
+    SIGNATURES[_twin + "_rseq"] = (_ci, SIGNATURES[_twin][1][:1] + [_p] + SIGNATURES[_twin][1][1:])
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+
+
 def lib():
     """Load libwdf_hip.so (once).  Raises WdfHipError if it has not been built."""
     global _lib
@@ -60,319 +214,15 @@ def lib():
             f"{LIB_PATH} not found: build it with `make -C differentiable-wdfs_amd/csrc` "
             "(or __graft_entry__.build()). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, fp, i64, ci, cf = C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float
-    L.wdf_abi_version.restype = ci
+    L.wdf_abi_version.restype = _ci
     if L.wdf_abi_version() != ABI_VERSION:
         raise WdfHipError(f"{LIB_PATH} has ABI version {L.wdf_abi_version()}, this host layer needs {ABI_VERSION}: "
                           "rebuild it (make -C differentiable-wdfs_amd/csrc)")
-    L.wdf_last_error.restype = C.c_char_p
-    L.wdf_device_info.restype = ci
-    L.wdf_device_info.argtypes = [ci, C.c_char_p, ci]
-    L.wdf_clipper_fwd.restype = ci
-    L.wdf_clipper_fwd.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, fp, i64, i64, ci, vp]
-    L.wdf_clipper_bwd.restype = ci
-    L.wdf_clipper_bwd.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, vp, fp, fp, fp, ci, i64, i64, ci, vp]
-    L.wdf_clipper_bwd_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_bwd_ws_bytes.argtypes = [i64]
-    L.wdf_clipper_tp_chunks.restype = ci
-    L.wdf_clipper_tp_chunks.argtypes = [i64, ci]
-    L.wdf_clipper_tp_warm_unit.restype = ci
-    L.wdf_clipper_tp_warm_unit.argtypes = []
-    L.wdf_clipper_fwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_fwd_tp_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_fwd_tp.restype = ci
-    L.wdf_clipper_fwd_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, ci, vp]
-    L.wdf_clipper_fwd_tp_state_bytes.restype = C.c_size_t
-    L.wdf_clipper_fwd_tp_state_bytes.argtypes = [i64, ci, ci]
-    L.wdf_clipper_fwd_tp_state_reset.restype = ci
-    L.wdf_clipper_fwd_tp_state_reset.argtypes = [vp, i64, ci, vp]
-    L.wdf_clipper_fwd_tp_warm.restype = ci
-    L.wdf_clipper_fwd_tp_warm.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, vp, ci, ci, vp]
-    L.wdf_clipper_bwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_bwd_tp_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_bwd_tp_ws_init.restype = ci
-    L.wdf_clipper_bwd_tp_ws_init.argtypes = [vp, i64, ci, vp]
-    L.wdf_clipper_bwd_tp.restype = ci
-    L.wdf_clipper_bwd_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, vp, fp, fp, ci, i64, i64, ci, ci, vp]
-    L.wdf_clipper_bwd_mse_tp.restype = ci
-    L.wdf_clipper_bwd_mse_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, cf, vp, fp, fp, fp, ci, i64, i64, ci,
-                                         ci, vp]
-    L.wdf_clipper_bwd_mse_tp_adam.restype = ci
-    L.wdf_clipper_bwd_mse_tp_adam.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, cf, vp, fp, fp, i64, i64, ci, ci,
-                                              fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
-    L.wdf_clipper_step_mse_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_step_mse_tp_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_step_mse_tp_ws_init.restype = ci
-    L.wdf_clipper_step_mse_tp_ws_init.argtypes = [vp, i64, ci, vp]
-    L.wdf_clipper_step_mse_tp.restype = ci
-    L.wdf_clipper_step_mse_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, cf, i64, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, vp,
-                                          ci, fp, fp, ci, fp, fp, vp, fp, cf, cf, cf, fp, fp, ci, vp]
-    L.wdf_clipper_step_esr_tp.restype = ci
-    L.wdf_clipper_step_esr_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, C.c_double, C.c_double, i64, fp, fp, fp, i64, i64, ci, ci, cf,
-                                          vp, vp, vp, ci, fp, fp, fp, fp, fp, vp, fp, cf, cf, cf, fp, fp, ci, vp]
-    L.wdf_esr_finish.restype = ci
-    L.wdf_esr_finish.argtypes = [fp, C.c_double, C.c_double, fp, fp, vp]
-    L.wdf_loss_sums_ws_bytes.restype = i64
-    L.wdf_loss_sums.restype = ci
-    L.wdf_loss_sums.argtypes = [fp, fp, i64, i64, i64, vp, vp, vp]
-    L.wdf_esr_coef.restype = ci
-    L.wdf_esr_coef.argtypes = [vp, C.c_double, C.c_double, fp, fp, vp]
-    L.wdf_loss_esr_grad.restype = ci
-    L.wdf_loss_esr_grad.argtypes = [fp, fp, fp, i64, i64, i64, fp, vp]
-    L.wdf_loss_terms_ws_bytes.restype = i64
-    L.wdf_loss_terms_ws_bytes.argtypes = []
-    L.wdf_loss_terms_sums.restype = ci
-    L.wdf_loss_terms_sums.argtypes = [fp, fp, i64, i64, i64, C.c_double, vp, vp, vp]
-    L.wdf_loss_terms_coef.restype = ci
-    L.wdf_loss_terms_coef.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_double, fp, fp, vp]
-    L.wdf_loss_terms_grad.restype = ci
-    L.wdf_loss_terms_grad.argtypes = [fp, fp, fp, C.c_double, i64, i64, i64, fp, vp]
-    L.wdf_clipper_bwd_esr_tp.restype = ci
-    L.wdf_clipper_bwd_esr_tp.argtypes = [fp, fp, fp, cf, ci, ci, fp, fp, fp, fp, i64, vp, fp, fp, fp, ci, i64, i64, ci,
-                                         ci, vp]
-    L.wdf_clipper_asym_fwd.restype = ci
-    L.wdf_clipper_asym_fwd.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, fp, fp, fp, vp, i64, i64, vp]
-    L.wdf_clipper_asym_fwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_asym_fwd_tp_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_asym_fwd_tp.restype = ci
-    L.wdf_clipper_asym_fwd_tp.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, vp]
-    L.wdf_clipper_asym_bwd_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_asym_bwd_ws_bytes.argtypes = [i64]
-    L.wdf_clipper_asym_bwd.restype = ci
-    L.wdf_clipper_asym_bwd.argtypes = [fp, fp, cf, C.c_double, ci, fp, fp, vp, fp, i64, i64, vp]
-    L.wdf_clipper_asym_bwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_asym_bwd_tp_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_asym_bwd_tp.restype = ci
-    L.wdf_clipper_asym_bwd_tp.argtypes = [fp, fp, cf, ci, fp, fp, fp, fp, vp, fp, fp, i64, i64, ci, vp]
-    L.wdf_ss_dyn_row_len.restype = ci
-    L.wdf_ss_dyn_row_len.argtypes = [ci, ci]
-    L.wdf_ss_dyn_fwd.restype = ci
-    L.wdf_ss_dyn_fwd.argtypes = [fp, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, vp]
-    L.wdf_ss_dyn_bwd_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_dyn_bwd_ws_bytes.argtypes = [i64]
-    L.wdf_ss_dyn_bwd_root_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_dyn_bwd_root_ws_bytes.argtypes = [ci, i64]
-    L.wdf_ss_dyn_bwd_tp_root_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_dyn_bwd_tp_root_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_dyn_bwd.restype = ci
-    L.wdf_ss_dyn_bwd.argtypes = [fp, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, vp, fp, fp, fp, fp, i64, i64, vp]
-    L.wdf_ss_dyn_fwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_dyn_fwd_tp_ws_bytes.argtypes = [ci, i64, ci]
-    L.wdf_ss_dyn_fwd_tp.restype = ci
-    L.wdf_ss_dyn_fwd_tp.argtypes = [fp, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, fp, vp, vp, vp]
-    L.wdf_ss_dyn_bwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_dyn_bwd_tp_ws_bytes.argtypes = [ci, i64, i64, ci]
-    L.wdf_ss_dyn_bwd_tp.restype = ci
-    L.wdf_ss_dyn_bwd_tp.argtypes = [fp, fp, ci, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, vp, fp, fp, fp, fp, i64, i64, ci, vp]
-    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-    L.wdf_ss_dyn_rows.restype = ci
-    L.wdf_ss_dyn_rows.argtypes = [ip, ci, dp, ci, ip, ci, vp, ci, ci, fp, fp, i64, i64, vp]
-    L.wdf_ss_dyn_rows_bwd_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_dyn_rows_bwd_ws_bytes.argtypes = [ci, i64, i64]
-    L.wdf_ss_dyn_rows_bwd.restype = ci
-    L.wdf_ss_dyn_rows_bwd.argtypes = [ip, ci, dp, ci, ip, ci, vp, ci, ci, fp, fp, vp, vp, i64, i64, vp]
-    L.wdf_clipper_mlp_wgrad_matrix_core_chunks.restype = ci
-    L.wdf_clipper_mlp_wgrad_matrix_core_chunks.argtypes = [i64, i64]
-    L.wdf_clipper_asym_step_mse_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_asym_step_mse_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_asym_step_mse.restype = ci
-    L.wdf_clipper_asym_step_mse.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, cf, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, fp,
-                                            fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
-    L.wdf_clipper_asym_step_esr_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_asym_step_esr_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_asym_step_esr.restype = ci
-    L.wdf_clipper_asym_step_esr.argtypes = [fp, fp, cf, ci, C.c_double, ci, fp, C.c_double, C.c_double, i64, fp, fp, fp, i64, i64, ci, ci,
-                                            cf, vp, vp, fp, fp, fp, fp, fp, vp, fp, cf, cf, cf, fp, fp, vp]
-    L.wdf_asym_esr_finish.restype = ci
-    L.wdf_asym_esr_finish.argtypes = [fp, C.c_double, C.c_double, fp, fp, vp]
-    # one pot resistance per sequence: the static twins' argument lists with rseq behind x
-    for twin in ("wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_tp", "wdf_clipper_asym_step_mse",
-                 "wdf_clipper_asym_step_esr"):
-        fn, st = getattr(L, twin + "_rseq"), getattr(L, twin)
-        fn.restype = ci
-        fn.argtypes = [st.argtypes[0], fp] + list(st.argtypes[1:])
-    L.wdf_asym_root.restype = ci
-    L.wdf_asym_root.argtypes = [fp, fp, cf, ci, C.c_double, ci, vp, i64, vp]
-    L.wdf_mlp_weight_count.restype = ci
-    L.wdf_mlp_weight_count.argtypes = [ci, ci]
-    L.wdf_clipper_mlp_fwd.restype = ci
-    L.wdf_clipper_mlp_fwd.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, fp, fp, i64, i64, ci, vp]
-    L.wdf_clipper_mlp_bwd_w_ws_bytes.restype = i64
-    L.wdf_clipper_mlp_bwd_w_ws_bytes.argtypes = [ci, ci, i64]
-    L.wdf_clipper_mlp_bwd_w.restype = ci
-    L.wdf_clipper_mlp_bwd_w.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, vp, fp, fp, i64, i64, ci, vp]
-    L.wdf_clipper_mlp_tp_chunks.restype = ci
-    L.wdf_clipper_mlp_tp_chunks.argtypes = [i64, ci]
-    L.wdf_clipper_mlp_fwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_mlp_fwd_tp_ws_bytes.argtypes = [i64, ci]
-    L.wdf_clipper_mlp_fwd_tp.restype = ci
-    L.wdf_clipper_mlp_fwd_tp.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, fp, fp, i64, i64, ci, ci, vp, cf, vp, vp, vp]
-    L.wdf_clipper_mlp_bwd_w_tp_ws_bytes.restype = i64
-    L.wdf_clipper_mlp_bwd_w_tp_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_clipper_mlp_bwd_w_tp.restype = ci
-    L.wdf_clipper_mlp_bwd_w_tp.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, vp, fp, fp, i64, i64, ci, vp]
-    L.wdf_clipper_mlp_fwd_tp_kappa.restype = ci
-    L.wdf_clipper_mlp_fwd_tp_kappa.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, fp, fp, fp, fp, i64, i64, ci, ci, vp, cf, vp, vp, vp]
-    L.wdf_clipper_mlp_tp_starts.restype = ci
-    L.wdf_clipper_mlp_tp_starts.argtypes = [i64, ci, ci, C.POINTER(C.c_int64)]
-    L.wdf_clipper_mlp_bwd_w_tp_kappa.restype = ci
-    L.wdf_clipper_mlp_bwd_w_tp_kappa.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, fp, vp, fp, fp, i64, i64, ci, vp]
-    L.wdf_clipper_mlp_bwd_ws_bytes.restype = C.c_size_t
-    L.wdf_clipper_mlp_bwd_ws_bytes.argtypes = [i64]
-    L.wdf_clipper_mlp_bwd.restype = ci
-    L.wdf_clipper_mlp_bwd.argtypes = [fp, fp, fp, fp, ci, ci, cf, fp, fp, fp, fp, fp, vp, fp, i64, i64, ci, vp]
-    L.wdf_mlp_eval.restype = ci
-    L.wdf_mlp_eval.argtypes = [fp, fp, fp, ci, ci, fp, i64, vp]
-    L.wdf_mlp_fit_epoch.restype = ci
-    L.wdf_mlp_fit_epoch.argtypes = [fp, fp, fp, i64, ci, fp, fp, fp, vp, cf, cf, cf, cf, cf, cf, vp, ci, ci, vp]
-    L.wdf_clipper_mlp_wgrad_ws_bytes.restype = i64
-    L.wdf_clipper_mlp_wgrad_ws_bytes.argtypes = [ci, ci, i64]
-    L.wdf_clipper_mlp_wgrad.restype = ci
-    L.wdf_clipper_mlp_wgrad.argtypes = [fp, fp, fp, fp, fp, ci, ci, cf, vp, fp, i64, vp]
-    i32p = C.POINTER(C.c_int32)
-    L.wdf_clipper_mlp_step_state_bytes.restype = C.c_size_t
-    L.wdf_clipper_mlp_step_state_bytes.argtypes = [ci, ci, i64, i64, ci, ci]
-    L.wdf_clipper_mlp_step_plan.restype = ci
-    L.wdf_clipper_mlp_step_plan.argtypes = [vp, ci, ci, i64, i64, ci, ci, i32p, ci, ci, ci, ci, ci, cf, vp]
-    L.wdf_clipper_mlp_step_read.restype = ci
-    L.wdf_clipper_mlp_step_read.argtypes = [vp, ci, ci, i64, i64, ci, ci, i32p, i32p, i32p, i32p, C.POINTER(C.c_float), vp]
-    L.wdf_clipper_mlp_step_set.restype = ci
-    L.wdf_clipper_mlp_step_set.argtypes = [vp, ci, C.c_int32, vp]
-    L.wdf_clipper_mlp_step_set_wcol.restype = ci
-    L.wdf_clipper_mlp_step_set_wcol.argtypes = [vp, ci, ci, i64, i64, ci, ci, i32p, vp]
-    L.wdf_clipper_mlp_step_prepare.restype = ci
-    L.wdf_clipper_mlp_step_prepare.argtypes = [fp, fp, cf, i64, i64, fp, fp, vp]
-    L.wdf_clipper_mlp_step.restype = ci
-    L.wdf_clipper_mlp_step.argtypes = [fp, fp, fp, fp, fp, ci, ci, ci, cf, fp, i64, C.c_double, C.c_double, fp, fp, fp, vp, i64, i64,
-                                       ci, ci, ci, vp, fp, fp, fp, fp, fp, vp, fp, cf, cf, cf, vp]
-    L.wdf_ss_probe.restype = ci
-    L.wdf_ss_probe.argtypes = [vp, ci, vp, fp, ci, vp, ci, fp, vp, vp, vp]
-    L.wdf_ss_probe_adam.restype = ci
-    L.wdf_ss_probe_adam.argtypes = [vp, ci, vp, ci, vp, fp, ci, vp, ci, fp, vp, vp, vp]
-    L.wdf_ss_lin_step_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_lin_step_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_lin_step_mse.restype = ci
-    L.wdf_ss_lin_step_mse.argtypes = [fp, fp, vp, ci, ci, ci, fp, cf, fp, vp, fp, fp, fp, i64, i64, ci, fp, fp, vp]
-    L.wdf_ss_lin_step_esr_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_lin_step_esr_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_lin_step_esr.restype = ci
-    L.wdf_ss_lin_step_esr.argtypes = [fp, fp, vp, ci, ci, ci, fp, C.c_double, C.c_double, i64, fp, vp, fp, fp, fp, fp, i64, i64, ci, fp, fp, vp]
-    L.wdf_ss_lin_esr_finish.restype = ci
-    L.wdf_ss_lin_esr_finish.argtypes = [fp, ci, C.c_double, C.c_double, fp, fp, vp]
-    L.wdf_ss_nl_step_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_nl_step_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_nl_step_chunk_len.restype = ci
-    L.wdf_ss_nl_step_chunk_len.argtypes = [i64, ci]
-    L.wdf_ss_nl_step_plan.restype = ci
-    L.wdf_ss_nl_step_plan.argtypes = [vp, ci, ci, i64, i64, ci, ci, ci, ci, ci, cf, vp]
-    L.wdf_ss_nl_step_set.restype = ci
-    L.wdf_ss_nl_step_set.argtypes = [vp, ci, C.c_double, vp]
-    L.wdf_ss_nl_step_read.restype = ci
-    L.wdf_ss_nl_step_read.argtypes = [vp, vp, vp]
-    L.wdf_ss_nl_step_mse.restype = ci
-    L.wdf_ss_nl_step_mse.argtypes = [fp, fp, fp, vp, ci, ci, ci, ci, ci, fp, cf, fp, vp, fp, fp, i64, i64, ci, vp]
-    L.wdf_ss_nl_step_esr_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_nl_step_esr_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_nl_step_esr.restype = ci
-    L.wdf_ss_nl_step_esr.argtypes = [fp, fp, fp, vp, ci, ci, ci, ci, ci, fp, i64, C.c_double, fp, vp, fp, fp, i64, i64, ci, vp]
-    L.wdf_ss_ncoef.restype = ci
-    L.wdf_ss_ncoef.argtypes = [ci, ci]
-    L.wdf_ss_fwd.restype = ci
-    L.wdf_ss_fwd.argtypes = [fp, fp, fp, ci, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, ci, vp]
-    L.wdf_ss_fwd_lin_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_fwd_lin_tp_ws_bytes.argtypes = [ci, i64, ci]
-    L.wdf_ss_fwd_lin_tp.restype = ci
-    L.wdf_ss_fwd_lin_tp.argtypes = [fp, fp, ci, ci, fp, fp, fp, fp, i64, i64, ci, vp, vp]
-    L.wdf_ss_bwd.restype = ci
-    L.wdf_ss_bwd.argtypes = [fp, fp, fp, ci, ci, ci, ci, ci, fp, fp, vp, fp, fp, fp, i64, i64, ci, vp]
-    L.wdf_ss_tp_chunks.restype = ci
-    L.wdf_ss_tp_chunks.argtypes = [i64, ci]
-    L.wdf_ss_fwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_fwd_tp_ws_bytes.argtypes = [ci, i64, ci]
-    L.wdf_ss_fwd_tp.restype = ci
-    L.wdf_ss_fwd_tp.argtypes = [fp, fp, fp, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, fp, vp, vp, vp]
-    L.wdf_ss_fwd_tp_root.restype = ci
-    L.wdf_ss_fwd_tp_root.argtypes = [fp, fp, fp, ci, ci, ci, ci, ci, fp, fp, fp, fp, i64, i64, ci, ci, cf, fp, vp, vp, vp]
-    L.wdf_ss_tp_starts.restype = ci
-    L.wdf_ss_tp_starts.argtypes = [i64, ci, ci, C.POINTER(C.c_int64)]
-    L.wdf_ss_bwd_tp_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_bwd_tp_ws_bytes.argtypes = [ci, ci, i64, ci]
-    L.wdf_ss_bwd_tp.restype = ci
-    L.wdf_ss_bwd_tp.argtypes = [fp, fp, fp, ci, ci, ci, ci, ci, fp, fp, vp, fp, fp, fp, i64, i64, ci, vp]
-    L.wdf_ss_bwd_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_bwd_ws_bytes.argtypes = [ci, ci, i64]
-    L.wdf_ss_asym_step_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_asym_step_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_asym_step_esr_ws_bytes.restype = C.c_size_t
-    L.wdf_ss_asym_step_esr_ws_bytes.argtypes = [ci, ci, i64, i64, ci]
-    L.wdf_ss_asym_step_mse.restype = ci
-    L.wdf_ss_asym_step_mse.argtypes = [fp, fp, fp, ci, ci, fp, cf, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp, fp, vp]
-    L.wdf_ss_asym_step_esr.restype = ci
-    L.wdf_ss_asym_step_esr.argtypes = [fp, fp, fp, ci, ci, fp, C.c_double, C.c_double, i64, fp, fp, fp, i64, i64, ci, ci, cf, vp, vp,
-                                       fp, fp, fp, vp]
-    L.wdf_omega_f32.restype = ci
-    L.wdf_omega_f32.argtypes = [fp, fp, vp, i64, vp]
-    L.wdf_omega_f64.restype = ci
-    L.wdf_omega_f64.argtypes = [vp, vp, vp, i64, vp]
-    L.wdf_diode_pair_f32.restype = ci
-    L.wdf_diode_pair_f32.argtypes = [fp, fp, cf, cf, ci, ci, fp, i64, vp]
-    L.wdf_adam_step.restype = ci
-    L.wdf_adam_step.argtypes = [fp, fp, fp, fp, vp, fp, cf, cf, cf, fp, fp, ci, vp]
-    L.wdf_adam_step_multi.restype = ci
-    L.wdf_adam_step_multi.argtypes = [vp, ci, vp]
-    L.wdf_event_create.restype = vp
-    L.wdf_event_record.restype = ci
-    L.wdf_event_record.argtypes = [vp, vp]
-    L.wdf_event_elapsed_ms.restype = ci
-    L.wdf_event_elapsed_ms.argtypes = [vp, vp, C.POINTER(C.c_float)]
-    L.wdf_event_destroy.restype = None
-    L.wdf_event_destroy.argtypes = [vp]
-    L.wdf_clock_stamp.restype = ci
-    L.wdf_clock_stamp.argtypes = [vp, vp]
-    L.wdf_event_bracket_next.restype = None
-    L.wdf_event_bracket_next.argtypes = [vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = (
-    "wdf_abi_version", "wdf_last_error", "wdf_device_info",
-    "wdf_clipper_fwd", "wdf_clipper_bwd", "wdf_clipper_bwd_ws_bytes",
-    "wdf_clipper_tp_chunks", "wdf_clipper_tp_warm_unit", "wdf_clipper_fwd_tp_ws_bytes", "wdf_clipper_fwd_tp",
-    "wdf_clipper_fwd_tp_state_bytes", "wdf_clipper_fwd_tp_state_reset", "wdf_clipper_fwd_tp_warm",
-    "wdf_clipper_bwd_tp_ws_bytes", "wdf_clipper_bwd_tp_ws_init", "wdf_clipper_bwd_tp", "wdf_clipper_bwd_mse_tp",
-    "wdf_clipper_bwd_mse_tp_adam", "wdf_clipper_step_mse_tp_ws_bytes", "wdf_clipper_step_mse_tp_ws_init",
-    "wdf_clipper_step_mse_tp", "wdf_clipper_step_esr_tp", "wdf_esr_finish", "wdf_loss_sums_ws_bytes", "wdf_loss_sums", "wdf_esr_coef", "wdf_loss_esr_grad", "wdf_clipper_bwd_esr_tp",
-    "wdf_loss_terms_ws_bytes", "wdf_loss_terms_sums", "wdf_loss_terms_coef", "wdf_loss_terms_grad",
-    "wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp_ws_bytes", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_ws_bytes", "wdf_clipper_asym_bwd",
-    "wdf_clipper_asym_bwd_tp_ws_bytes", "wdf_clipper_asym_bwd_tp", "wdf_asym_root",
-    "wdf_clipper_asym_step_mse_ws_bytes", "wdf_clipper_asym_step_mse",
-    "wdf_clipper_asym_step_esr_ws_bytes", "wdf_clipper_asym_step_esr", "wdf_asym_esr_finish",
-    "wdf_clipper_asym_fwd_rseq", "wdf_clipper_asym_fwd_tp_rseq", "wdf_clipper_asym_bwd_tp_rseq",
-    "wdf_clipper_asym_step_mse_rseq", "wdf_clipper_asym_step_esr_rseq",
-    "wdf_ss_dyn_row_len", "wdf_ss_dyn_fwd", "wdf_ss_dyn_bwd_ws_bytes", "wdf_ss_dyn_bwd", "wdf_clipper_mlp_wgrad_matrix_core_chunks",
-    "wdf_ss_dyn_fwd_tp_ws_bytes", "wdf_ss_dyn_fwd_tp", "wdf_ss_dyn_bwd_tp_ws_bytes", "wdf_ss_dyn_bwd_tp",
-    "wdf_ss_dyn_bwd_root_ws_bytes", "wdf_ss_dyn_bwd_tp_root_ws_bytes",
-    "wdf_ss_dyn_rows", "wdf_ss_dyn_rows_bwd_ws_bytes", "wdf_ss_dyn_rows_bwd",
-    "wdf_mlp_weight_count", "wdf_clipper_mlp_fwd", "wdf_clipper_mlp_bwd", "wdf_clipper_mlp_bwd_ws_bytes",
-    "wdf_clipper_mlp_bwd_w_ws_bytes", "wdf_clipper_mlp_bwd_w",
-    "wdf_clipper_mlp_tp_chunks", "wdf_clipper_mlp_fwd_tp_ws_bytes", "wdf_clipper_mlp_fwd_tp",
-    "wdf_clipper_mlp_bwd_w_tp_ws_bytes", "wdf_clipper_mlp_bwd_w_tp",
-    "wdf_clipper_mlp_fwd_tp_kappa", "wdf_clipper_mlp_bwd_w_tp_kappa", "wdf_clipper_mlp_tp_starts",
-    "wdf_clipper_mlp_wgrad_ws_bytes", "wdf_clipper_mlp_wgrad", "wdf_mlp_eval", "wdf_mlp_fit_epoch",
-    "wdf_clipper_mlp_step_state_bytes", "wdf_clipper_mlp_step_plan", "wdf_clipper_mlp_step_read", "wdf_clipper_mlp_step_set",
-    "wdf_clipper_mlp_step_set_wcol", "wdf_clipper_mlp_step_prepare", "wdf_clipper_mlp_step",
-    "wdf_ss_probe", "wdf_ss_probe_adam", "wdf_ss_lin_step_ws_bytes", "wdf_ss_lin_step_mse",
-    "wdf_ss_lin_step_esr_ws_bytes", "wdf_ss_lin_step_esr", "wdf_ss_lin_esr_finish",
-    "wdf_ss_nl_step_ws_bytes", "wdf_ss_nl_step_chunk_len", "wdf_ss_nl_step_plan", "wdf_ss_nl_step_set", "wdf_ss_nl_step_read",
-    "wdf_ss_nl_step_mse", "wdf_ss_nl_step_esr_ws_bytes", "wdf_ss_nl_step_esr",
-    "wdf_ss_ncoef", "wdf_ss_fwd", "wdf_ss_bwd", "wdf_ss_bwd_ws_bytes", "wdf_ss_fwd_lin_tp_ws_bytes", "wdf_ss_fwd_lin_tp",
-    "wdf_ss_tp_chunks", "wdf_ss_tp_starts", "wdf_ss_fwd_tp_ws_bytes", "wdf_ss_fwd_tp", "wdf_ss_fwd_tp_root", "wdf_ss_bwd_tp_ws_bytes", "wdf_ss_bwd_tp",
-    "wdf_ss_asym_step_ws_bytes", "wdf_ss_asym_step_esr_ws_bytes", "wdf_ss_asym_step_mse", "wdf_ss_asym_step_esr",
-    "wdf_omega_f32", "wdf_omega_f64", "wdf_diode_pair_f32", "wdf_adam_step", "wdf_adam_step_multi",
-    "wdf_event_create", "wdf_event_record", "wdf_event_elapsed_ms", "wdf_event_destroy", "wdf_event_bracket_next",
-    "wdf_clock_stamp",
-)
 
 
 def _check(rc, what):
@@ -398,9 +248,96 @@ def _f32_dev(t, name):
     return t
 
 
+_GPU_SEEN = False
+
+
 def require_gpu():
-    if not torch.cuda.is_available():
-        raise WdfHipError("no HIP device visible: the WDF engine runs on MI355X only (no CPU fallback)")
+    """(A device once seen stays visible for the life of the process: torch is asked until it says yes, not at every launch.)"""
+    global _GPU_SEEN
+    if not _GPU_SEEN:
+        if not torch.cuda.is_available():
+            raise WdfHipError("no HIP device visible: the WDF engine runs on MI355X only (no CPU fallback)")
+        _GPU_SEEN = True
+
+
+# ---- what the one-pass step wrappers share: a buffer handed in is checked and handed back as it is, a missing one allocated on
+# the device of `like` (an input of the call: its device is looked up only where something is allocated) -----------------------------
+def _out(t, n, name, holds, like):
+    """The float32 output `name` of n elements (`holds` says which, for the refusal)."""
+    if t is None:
+        return torch.empty((n,), dtype=torch.float32, device=like.device)
+    if isinstance(t, torch.Tensor) and t.numel() == n and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous():
+        return t                                    # (what _f32_dev asks for, without the call: this runs per buffer and launch)
+    _f32_dev(t, name)
+    raise WdfHipError(f"{name} must hold {holds} ({n} floats)")
+
+
+def _y_zT(y, want_zT, T, B, like, ns=None):
+    """y [T,B], and zT ([B]; [ns,B] for a tree) where the final state is wanted."""
+    if y is None:
+        y = torch.empty((T, B), dtype=torch.float32, device=like.device)
+    elif tuple(_f32_dev(y, "y").shape) != (T, B):
+        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    zT = torch.empty((B,) if ns is None else (ns, B), dtype=torch.float32, device=like.device) if want_zT else None
+    return y, zT
+
+
+def _ws(ws, need, like, zeroed=False):
+    """The workspace of `need` bytes (what the step's *_ws_bytes export reports)."""
+    if ws is None:
+        return (torch.zeros if zeroed else torch.empty)((need,), dtype=torch.uint8, device=like.device)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.is_contiguous()):
+        raise WdfHipError("ws must be a contiguous tensor on the GPU")
+    if ws.numel() * ws.element_size() < need:
+        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
+    return ws
+
+
+def _esr_outs(finish, g, n, gname, loss3, like):
+    """(g [n], loss3 [3]) of an MSE + ESR step that finishes itself; (None, None) where the caller all-reduces the sums first."""
+    if not finish:
+        return None, None
+    return _out(g, n, gname, "one gradient per parameter", like), _out(loss3, 3, "loss3", "{mse, esr, mse + esr}", like)
+
+
+_NO_ADAM = (None, None, None, None, 0.0, 0.0, 0.0, None, None)
+
+
+def _adam_args(opt):
+    """The nine Adam arguments {m, v, step, lr, beta1, beta2, eps, lo, hi} of an export that applies `opt`."""
+    return _ptr(opt.m), _ptr(opt.v), _ptr(opt.step), _ptr(opt.lr), opt.b1, opt.b2, opt.eps, _ptr(opt.lo), _ptr(opt.hi)
+
+
+def _adam_tail(opt, n, who, holds, finish=True):
+    """The Adam arguments of a step that updates its n parameters in its own last launch; nulls without an optimizer.  A step
+    that does not finish (one shard of several) forms no gradient to apply."""
+    if opt is None:
+        return _NO_ADAM
+    if opt.n != n:
+        raise WdfHipError(f"{who}: the optimizer holds {holds}")
+    if not finish:
+        raise WdfHipError(f"{who}: the optimizer needs finish=True")
+    return _adam_args(opt)
+
+
+def _clipper_flags(time_major, fp64=False):
+    return (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag() | (WDF_PREC_F64 if fp64 else 0)
+
+
+def _clipper_step_flags(r, time_major):
+    return (_clipper_flags(time_major) | (WDF_ONE_SEQUENCE_PER_LANE if ONE_SEQUENCE_PER_LANE else 0) |
+            (WDF_R_PER_SEQUENCE if r_is_per_sequence(r, time_major) else 0))
+
+
+def _esr_finish(export, sums, sname, n, lead, n_global, eps, g, gname, loss3):
+    """The body of esr_finish, asym_esr_finish and ss_lin_esr_finish (export: lib().wdf_*_esr_finish; lead: what it takes between
+    sums and n_global): sums = {S, E, gP[n], gQ[n]} -> (g [n], loss3)."""
+    require_gpu()
+    if _f32_dev(sums, sname).numel() != 2 + 2 * n:
+        raise WdfHipError(f"{sname} must hold {{S, E, gP[{n}], gQ[{n}]}}")
+    g, loss3 = _esr_outs(True, g, n, gname, loss3, sums)
+    _check(export(_ptr(sums), *lead, float(n_global), float(eps), _ptr(g), _ptr(loss3), _stream()), export.__name__)
+    return g, loss3
 
 
 def omega64(x, want_iters=False):
@@ -431,7 +368,7 @@ def clipper_fwd(x, theta, fs, r=None, n_up=1, n_down=1, want_stash=True, z0=None
     y = torch.empty((T, B), dtype=torch.float32, device=x.device)
     zs = torch.empty((T, B), dtype=torch.float32, device=x.device) if want_stash else None
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
-    flags = (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag() | (WDF_PREC_F64 if fp64 else 0)
+    flags = _clipper_flags(time_major, fp64)
     rc = lib().wdf_clipper_fwd(_ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down),
                                _ptr(y), _ptr(zs), _ptr(z0), _ptr(zT), B, T, flags, _stream())
     _check(rc, "wdf_clipper_fwd")
@@ -458,7 +395,7 @@ def clipper_bwd(x, theta, fs, zstash, gy, r=None, n_up=1, n_down=1, want_gz0=Fal
         gtheta = torch.empty((4,), dtype=torch.float32, device=x.device)
         accumulate = False
     gz0 = torch.empty((B,), dtype=torch.float32, device=x.device) if want_gz0 else None
-    flags = (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag() | (WDF_PREC_F64 if fp64 else 0)
+    flags = _clipper_flags(time_major, fp64)
     rc = lib().wdf_clipper_bwd(_ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down),
                                _ptr(zstash), _ptr(gy), _ptr(ws), _ptr(gtheta), _ptr(gz0), _ptr(_f32_dev(gzT, "gzT")),
                                1 if accumulate else 0, B, T, flags, _stream())
@@ -534,7 +471,7 @@ def clipper_fwd_tp(x, theta, fs, n_chunks, warmup, tol=1e-6, r=None, n_up=1, n_d
         ws = torch.empty((lib().wdf_clipper_fwd_tp_ws_bytes(B, int(n_chunks)),), dtype=torch.uint8, device=x.device)
     if status is None:
         status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    flags = (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag()
+    flags = _clipper_flags(time_major)
     if state is not None:
         if (state.B, state.T, state.n_chunks) != (B, T, int(n_chunks)) or state.buf.device != x.device:
             raise WdfHipError("warm-start state was made for another batch shape / chunking / device")
@@ -558,7 +495,7 @@ def clipper_bwd_mse_tp_adam(x, theta, fs, zstash, zT, target, gscale, n_chunks, 
     x, r, theta = _f32_dev(x, "x"), _f32_dev(r, "r"), _f32_dev(theta, "theta")
     zstash, zT, target = _f32_dev(zstash, "zstash"), _f32_dev(zT, "zT"), _f32_dev(target, "target")
     B, T = (x.shape[1], x.shape[0]) if time_major else x.shape
-    if opt.n != 4 or theta.numel() != 4:
+    if opt is None or opt.n != 4 or theta.numel() != 4:
         raise WdfHipError("clipper_bwd_mse_tp_adam: theta and the optimizer hold {Is, nVt, R, C}")
     if ws is None:
         ws = bwd_tp_workspace(B, int(n_chunks), x.device)
@@ -568,9 +505,7 @@ def clipper_bwd_mse_tp_adam(x, theta, fs, zstash, zT, target, gscale, n_chunks, 
         sse = torch.empty((1,), dtype=torch.float32, device=x.device)
     rc = lib().wdf_clipper_bwd_mse_tp_adam(_ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down), _ptr(zstash),
                                            _ptr(zT), _ptr(target), float(gscale), _ptr(ws), _ptr(gtheta), _ptr(sse), B, T,
-                                           int(n_chunks), (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag(),
-                                           _ptr(opt.m), _ptr(opt.v), _ptr(opt.step), _ptr(opt.lr), opt.b1, opt.b2, opt.eps,
-                                           _ptr(opt.lo), _ptr(opt.hi), _stream())
+                                           int(n_chunks), _clipper_flags(time_major), *_adam_args(opt), _stream())
     _check(rc, "wdf_clipper_bwd_mse_tp_adam")
     return gtheta, sse
 
@@ -605,14 +540,9 @@ def step_mse_workspace(B, n_chunks, device):
     return ws
 
 
-def clipper_step_mse_tp(x, theta, fs, target, gscale, n_chunks, warmup, tol=1e-6, r=None, n_up=1, n_down=1, skip=0, y=None,
-                        z0=None, want_zT=False, ws=None, status=None, state=None, gtheta=None, sse=None, accumulate=False,
-                        opt=None, time_major=False):
-    """The whole MSE training step in one pass over the data (include/wdf_hip.h, wdf_clipper_step_mse_tp):
-    forward, loss and d(gscale/2 sum (y - target)^2)/d{Is, nVt, R, C}, x and target read once, y written once, no
-    state stash.  n_chunks: time chunks asked for (rounded like wdf_clipper_tp_chunks does); state: a TpWarmState
-    made for (B, T, n_chunks); opt: a binding.Adam(4, ...) to update theta in the same launch.
-    -> y [T,B], zT [B] | None, gtheta[4], sse[1], status (device int32[4], read with tp_status())."""
+def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish=True):
+    """The checks and buffers the two one-pass clipper steps share
+    -> x, r, theta, target, z0, B, T, K, y, zT, ws, status, (state buffer, max_warm_tiles), Adam tail, flags."""
     require_gpu()
     x, r, theta = _f32_dev(x, "x"), _f32_dev(r, "r"), _f32_dev(theta, "theta")
     target, z0 = _f32_dev(target, "target"), _f32_dev(z0, "z0")
@@ -623,34 +553,38 @@ def clipper_step_mse_tp(x, theta, fs, target, gscale, n_chunks, warmup, tol=1e-6
         raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
     if r is not None and r.shape != x.shape:
         raise WdfHipError("r must have the shape of x")
+    if z0 is not None and z0.numel() != B:
+        raise WdfHipError(f"z0 must hold one state per sequence ({B})")
     K = lib().wdf_clipper_tp_chunks(T, int(n_chunks))
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
-    zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
-    if ws is None:
-        ws = step_mse_workspace(B, K, x.device)
-    if status is None:
-        status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    if gtheta is None:
-        gtheta = torch.empty((4,), dtype=torch.float32, device=x.device)
-        accumulate = False
-    if sse is None:
-        sse = torch.empty((1,), dtype=torch.float32, device=x.device)
+    y, zT = _y_zT(y, want_zT, T, B, x)
+    ws = step_mse_workspace(B, K, x.device) if ws is None else _ws(ws, lib().wdf_clipper_step_mse_tp_ws_bytes(B, K), x)
     if state is not None and ((state.B, state.T, state.K) != (B, T, K) or state.buf.device != x.device):
         raise WdfHipError("warm-start state was made for another batch shape / chunking / device")
-    if opt is not None and opt.n != 4:
-        raise WdfHipError("clipper_step_mse_tp: the optimizer holds {Is, nVt, R, C}")
-    o = opt
+    warm = (None, 0) if state is None else (_ptr(state.buf), state.max_warm_tiles)
+    if status is None:
+        status = torch.empty((4,), dtype=torch.int32, device=x.device)
+    return (x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm,
+            _adam_tail(opt, 4, who, "{Is, nVt, R, C}", finish), _clipper_step_flags(r, time_major))
+
+
+def clipper_step_mse_tp(x, theta, fs, target, gscale, n_chunks, warmup, tol=1e-6, r=None, n_up=1, n_down=1, skip=0, y=None,
+                        z0=None, want_zT=False, ws=None, status=None, state=None, gtheta=None, sse=None, accumulate=False,
+                        opt=None, time_major=False):
+    """The whole MSE training step in one pass over the data (include/wdf_hip.h, wdf_clipper_step_mse_tp):
+    forward, loss and d(gscale/2 sum (y - target)^2)/d{Is, nVt, R, C}, x and target read once, y written once, no
+    state stash.  n_chunks: time chunks asked for (rounded like wdf_clipper_tp_chunks does); state: a TpWarmState
+    made for (B, T, n_chunks); opt: a binding.Adam(4, ...) to update theta in the same launch.
+    -> y [T,B], zT [B] | None, gtheta[4], sse[1], status (device int32[4], read with tp_status())."""
+    x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm, adam, flags = _clipper_step_args(
+        "clipper_step_mse_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major)
+    if gtheta is None:
+        accumulate = False
+    gtheta = _out(gtheta, 4, "gtheta", "four gradients", x)
+    sse = _out(sse, 1, "sse", "one sum", x)
     rc = lib().wdf_clipper_step_mse_tp(
         _ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down), _ptr(target), float(gscale), int(skip), _ptr(y),
-        _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status),
-        None if state is None else _ptr(state.buf), 0 if state is None else state.max_warm_tiles, _ptr(gtheta), _ptr(sse),
-        1 if accumulate else 0, *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
-        0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
-        None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi),
-        (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag() | (WDF_ONE_SEQUENCE_PER_LANE if ONE_SEQUENCE_PER_LANE else 0) |
-        (WDF_R_PER_SEQUENCE if r_is_per_sequence(r, time_major) else 0),
-        _stream())
+        _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status), *warm, _ptr(gtheta), _ptr(sse),
+        1 if accumulate else 0, *adam, flags, _stream())
     _check(rc, "wdf_clipper_step_mse_tp")
     return y, zT, gtheta, sse, status
 
@@ -662,61 +596,21 @@ def clipper_step_esr_tp(x, theta, fs, target, n_global, eps_energy, skip, n_chun
     finish=True: the kernel finishes the step as a single rank -> gtheta[4], loss3 = {mse, esr, mse + esr} (and the Adam
     update of theta with `opt`).  finish=False: only sums10 = {S, E, gP[4], gQ[4]} of this batch comes back -- all-reduce it
     and call esr_finish.  -> y [T,B], zT | None, sums10, gtheta | None, loss3 | None, status."""
-    require_gpu()
-    x, r, theta = _f32_dev(x, "x"), _f32_dev(r, "r"), _f32_dev(theta, "theta")
-    target, z0 = _f32_dev(target, "target"), _f32_dev(z0, "z0")
-    B, T = (x.shape[1], x.shape[0]) if time_major else x.shape
-    if theta.numel() != 4:
-        raise WdfHipError("theta must hold {Is, nVt, R, C}")
-    if tuple(target.shape) != (T, B):
-        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
-    if r is not None and r.shape != x.shape:
-        raise WdfHipError("r must have the shape of x")
-    K = lib().wdf_clipper_tp_chunks(T, int(n_chunks))
-    dev = x.device
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=dev)
-    zT = torch.empty((B,), dtype=torch.float32, device=dev) if want_zT else None
-    if ws is None:
-        ws = step_mse_workspace(B, K, dev)
-    if status is None:
-        status = torch.empty((4,), dtype=torch.int32, device=dev)
-    if sums10 is None:
-        sums10 = torch.empty((10,), dtype=torch.float32, device=dev)
-    if finish:
-        gtheta = torch.empty((4,), dtype=torch.float32, device=dev) if gtheta is None else gtheta
-        loss3 = torch.empty((3,), dtype=torch.float32, device=dev) if loss3 is None else loss3
-    else:
-        gtheta = loss3 = opt = None
-    if state is not None and ((state.B, state.T, state.K) != (B, T, K) or state.buf.device != dev):
-        raise WdfHipError("warm-start state was made for another batch shape / chunking / device")
-    o = opt
-    if o is not None and o.n != 4:
-        raise WdfHipError("clipper_step_esr_tp: the optimizer holds {Is, nVt, R, C}")
+    x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm, adam, flags = _clipper_step_args(
+        "clipper_step_esr_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish)
+    sums10 = _out(sums10, 10, "sums10", "{S, E, gP[4], gQ[4]}", x)
+    gtheta, loss3 = _esr_outs(finish, gtheta, 4, "gtheta", loss3, x)
     rc = lib().wdf_clipper_step_esr_tp(
         _ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down), _ptr(target), float(n_global), float(eps_energy),
-        int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status),
-        None if state is None else _ptr(state.buf), 0 if state is None else state.max_warm_tiles, _ptr(sums10), _ptr(gtheta),
-        _ptr(loss3), *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
-        0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
-        None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi),
-        (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag() | (WDF_ONE_SEQUENCE_PER_LANE if ONE_SEQUENCE_PER_LANE else 0) |
-        (WDF_R_PER_SEQUENCE if r_is_per_sequence(r, time_major) else 0),
-        _stream())
+        int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status), *warm, _ptr(sums10),
+        _ptr(gtheta), _ptr(loss3), *adam, flags, _stream())
     _check(rc, "wdf_clipper_step_esr_tp")
     return y, zT, sums10, gtheta, loss3, status
 
 
 def esr_finish(sums10, n_global, eps_energy, gtheta=None, loss3=None):
     """(gtheta[4], loss3 = {mse, esr, mse + esr}) from the all-reduced sums10 of clipper_step_esr_tp(finish=False)."""
-    require_gpu()
-    sums10 = _f32_dev(sums10, "sums10")
-    if gtheta is None:
-        gtheta = torch.empty((4,), dtype=torch.float32, device=sums10.device)
-    if loss3 is None:
-        loss3 = torch.empty((3,), dtype=torch.float32, device=sums10.device)
-    _check(lib().wdf_esr_finish(_ptr(sums10), float(n_global), float(eps_energy), _ptr(gtheta), _ptr(loss3), _stream()), "wdf_esr_finish")
-    return gtheta, loss3
+    return _esr_finish(lib().wdf_esr_finish, sums10, "sums10", 4, (), n_global, eps_energy, gtheta, "gtheta", loss3)
 
 
 def loss_sums(y, target, skip, sums=None, ws=None):
@@ -859,7 +753,7 @@ def clipper_bwd_esr_tp(x, theta, fs, zstash, zT, target, gcoef, skip, n_chunks, 
         sse = torch.empty((1,), dtype=torch.float32, device=x.device)
     rc = lib().wdf_clipper_bwd_esr_tp(_ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down), _ptr(zstash),
                                       _ptr(zT), _ptr(target), _ptr(gcoef), int(skip), _ptr(ws), _ptr(gtheta), _ptr(sse),
-                                      None, 0, B, T, int(n_chunks), (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag(),
+                                      None, 0, B, T, int(n_chunks), _clipper_flags(time_major),
                                       _stream())
     _check(rc, "wdf_clipper_bwd_esr_tp")
     return gtheta, sse
@@ -899,7 +793,7 @@ def clipper_bwd_tp(x, theta, fs, zstash, gy, n_chunks, r=None, n_up=1, n_down=1,
     rc = lib().wdf_clipper_bwd_tp(_ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down), _ptr(zstash),
                                   _ptr(gy), _ptr(ws), _ptr(gtheta), _ptr(gz0), 1 if accumulate else 0, B, T,
                                   int(n_chunks),
-                                  (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag(), _stream())
+                                  _clipper_flags(time_major), _stream())
     _check(rc, "wdf_clipper_bwd_tp")
     return gtheta, gz0
 
@@ -932,7 +826,7 @@ def clipper_bwd_mse_tp(x, theta, fs, zstash, zT, target, gscale, n_chunks, r=Non
     rc = lib().wdf_clipper_bwd_mse_tp(_ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down),
                                       _ptr(zstash), _ptr(zT), _ptr(target), float(gscale), _ptr(ws), _ptr(gtheta),
                                       _ptr(sse), None, 1 if accumulate else 0, B, T, int(n_chunks),
-                                      (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag(),
+                                      _clipper_flags(time_major),
                                       _stream())
     _check(rc, "wdf_clipper_bwd_mse_tp")
     return gtheta, sse
@@ -1177,7 +1071,10 @@ def _asym_call(name, rseq, x, *rest):
 
 
 def _rseq_arg(rseq, x, mode, who):
-    """What every *_rseq wrapper checks before anything is launched: one resistance per sequence, a Newton mode."""
+    """The rseq= keyword of the two-different-diode wrappers, checked before anything is launched: None (the pot is theta6[4]), or
+    one float32 resistance per sequence and then a Newton mode."""
+    if rseq is None:
+        return None
     B = int(x.shape[0])
     if not isinstance(rseq, torch.Tensor) or rseq.dtype != torch.float32 or rseq.dim() != 1 or rseq.numel() != B:
         raise WdfHipError(f"{who}: rseq must be a float32 tensor [B] = [{B}] (one resistance per sequence), got "
@@ -1185,6 +1082,13 @@ def _rseq_arg(rseq, x, mode, who):
     if int(mode) == ASYM_OMEGA_F32:
         raise WdfHipError(f"{who}: mode 0 (the closed form, a model approximation kept for comparison) has no per-sequence pot: "
                           "use ASYM_NEWTON_F32 or ASYM_NEWTON_F64")
+    return rseq
+
+
+def _required(rseq, who):
+    """The *_rseq wrappers take their pot positionally and need one; what it must be, the wrapper they forward to checks."""
+    if rseq is None:
+        raise WdfHipError(f"{who}: rseq is required (one resistance per sequence, a float32 tensor [B])")
     return rseq
 
 
@@ -1208,40 +1112,42 @@ def r_per_sequence(r):
 
 def clipper_asym_fwd_rseq(x, rseq, theta6, fs, mode, **kw):
     """clipper_asym_fwd with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_fwd_rseq): theta6[4] is ignored."""
-    return clipper_asym_fwd(x, theta6, fs, mode, _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_fwd_rseq"), **kw)
+    return clipper_asym_fwd(x, theta6, fs, mode, rseq=_required(rseq, "clipper_asym_fwd_rseq"), **kw)
 
 
 def clipper_asym_fwd_tp_rseq(x, rseq, theta6, fs, mode, n_chunks, warmup, **kw):
     """clipper_asym_fwd_tp with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_fwd_tp_rseq): theta6[4] is ignored;
     the warm-up has to outlast the LARGEST pot's memory."""
-    return clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_fwd_tp_rseq"), **kw)
+    return clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, rseq=_required(rseq, "clipper_asym_fwd_tp_rseq"), **kw)
 
 
 def clipper_asym_bwd_tp_rseq(x, rseq, theta6, fs, mode, zstash, zT, gy, n_chunks, **kw):
     """clipper_asym_bwd_tp with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_bwd_tp_rseq): component 4 of the
     gradient is exactly 0 (the pot is data), component 5 is dL/dC with the chain rule applied per sequence."""
     return clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks,
-                               _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_bwd_tp_rseq"), **kw)
+                               rseq=_required(rseq, "clipper_asym_bwd_tp_rseq"), **kw)
 
 
 def clipper_asym_step_mse_rseq(x, rseq, theta6, fs, mode, target, gscale, n_chunks, warmup, **kw):
     """clipper_asym_step_mse with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_step_mse_rseq): out7[5] (dR) is
     exactly 0 and opt never writes theta6[4]."""
     return clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup,
-                                 _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_step_mse_rseq"), **kw)
+                                 rseq=_required(rseq, "clipper_asym_step_mse_rseq"), **kw)
 
 
 def clipper_asym_step_esr_rseq(x, rseq, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup, **kw):
     """clipper_asym_step_esr with one pot resistance per sequence, rseq [B] (wdf_clipper_asym_step_esr_rseq): component 4 of
     gP, gQ and gtheta6 is exactly 0 and opt never writes theta6[4]."""
     return clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup,
-                                 _rseq=_rseq_arg(rseq, x, mode, "clipper_asym_step_esr_rseq"), **kw)
+                                 rseq=_required(rseq, "clipper_asym_step_esr_rseq"), **kw)
 
 
 def clipper_asym_fwd(x, theta6, fs, mode, tol=1e-12, max_iter=50, z0=None, want_zT=False, want_iters=False, want_stash=False,
-                     _rseq=None):
+                     rseq=None):
     """Two-different-diode clipper forward.  Returns y [T,B], zT | None, iters (int64 per wave) | None
-    (and the state stash [T,B] as a fourth value when want_stash)."""
+    (and the state stash [T,B] as a fourth value when want_stash).  rseq [B]: one pot resistance per sequence in place of
+    theta6[4] (wdf_clipper_asym_fwd_rseq; Newton modes)."""
+    rseq = _rseq_arg(rseq, x, mode, "clipper_asym_fwd")
     require_gpu()
     x = _f32_dev(x, "x")
     theta6 = _f32_dev(theta6, "theta6")
@@ -1253,16 +1159,18 @@ def clipper_asym_fwd(x, theta6, fs, mode, tol=1e-12, max_iter=50, z0=None, want_
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
     it = torch.zeros(((B + 63) // 64,), dtype=torch.int64, device=x.device) if want_iters else None
     zs = torch.empty((T, B), dtype=torch.float32, device=x.device) if want_stash else None
-    rc, name = _asym_call("wdf_clipper_asym_fwd", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
+    rc, name = _asym_call("wdf_clipper_asym_fwd", rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
                           _ptr(zs), _ptr(z0), _ptr(zT), _ptr(it), B, T, _stream())
     _check(rc, name)
     return (y, zT, it, zs) if want_stash else (y, zT, it)
 
 
 def clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, z0=None, want_zT=False,
-                        want_stash=False, _rseq=None):
+                        want_stash=False, rseq=None):
     """Time-parallel two-different-diode clipper forward (wdf_clipper_asym_fwd_tp).  n_chunks is rounded to a count that
-    tiles T in 8-step units.  -> y [T,B], zT | None, zstash | None, status (int32[4]; read with mlp_tp_status())."""
+    tiles T in 8-step units.  rseq [B]: one pot resistance per sequence in place of theta6[4] (wdf_clipper_asym_fwd_tp_rseq).
+    -> y [T,B], zT | None, zstash | None, status (int32[4]; read with mlp_tp_status())."""
+    rseq = _rseq_arg(rseq, x, mode, "clipper_asym_fwd_tp")
     require_gpu()
     x, theta6, z0 = _f32_dev(x, "x"), _f32_dev(theta6, "theta6"), _f32_dev(z0, "z0")
     if theta6.numel() != 6:
@@ -1274,7 +1182,7 @@ def clipper_asym_fwd_tp(x, theta6, fs, mode, n_chunks, warmup, tol=1e-12, max_it
     zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
     ws = torch.empty((lib().wdf_clipper_asym_fwd_tp_ws_bytes(B, K),), dtype=torch.uint8, device=x.device)
     status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    rc, name = _asym_call("wdf_clipper_asym_fwd_tp", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
+    rc, name = _asym_call("wdf_clipper_asym_fwd_tp", rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(y),
                           _ptr(zs), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _stream())
     _check(rc, name)
     return y, zT, zs, status
@@ -1295,10 +1203,12 @@ def clipper_asym_bwd(x, theta6, fs, zstash, gy, tol=1e-12, max_iter=50):
     return g
 
 
-def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None, want_gz0=False, ws=None, _rseq=None):
+def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None, want_gz0=False, ws=None, rseq=None):
     """Time-parallel reverse sweep of the two-different-diode clipper, any mode (wdf_clipper_asym_bwd_tp): no root
-    re-solve (consecutive stash entries give b), chunks composed exactly.  zT [B]: the forward's final state.
+    re-solve (consecutive stash entries give b), chunks composed exactly.  zT [B]: the forward's final state.  rseq [B]: the
+    forward's pot resistance per sequence (wdf_clipper_asym_bwd_tp_rseq).
     -> gtheta6 (and dL/dz0 [B] when want_gz0)."""
+    rseq = _rseq_arg(rseq, x, mode, "clipper_asym_bwd_tp")
     require_gpu()
     x, theta6, zstash, gy = _f32_dev(x, "x"), _f32_dev(theta6, "theta6"), _f32_dev(zstash, "zstash"), _f32_dev(gy, "gy")
     zT, gzT = _f32_dev(zT, "zT"), _f32_dev(gzT, "gzT")
@@ -1311,7 +1221,7 @@ def clipper_asym_bwd_tp(x, theta6, fs, mode, zstash, zT, gy, n_chunks, gzT=None,
         ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
     g = torch.empty((6,), dtype=torch.float32, device=x.device)
     gz0 = torch.empty((B,), dtype=torch.float32, device=x.device) if want_gz0 else None
-    rc, name = _asym_call("wdf_clipper_asym_bwd_tp", _rseq, x, _ptr(theta6), float(fs), int(mode), _ptr(zstash), _ptr(zT), _ptr(gy),
+    rc, name = _asym_call("wdf_clipper_asym_bwd_tp", rseq, x, _ptr(theta6), float(fs), int(mode), _ptr(zstash), _ptr(zT), _ptr(gy),
                           _ptr(gzT), _ptr(ws), _ptr(g), _ptr(gz0), B, T, K, _stream())
     _check(rc, name)
     return (g, gz0) if want_gz0 else g
@@ -1322,13 +1232,10 @@ def asym_chunks(T, n_chunks):
     return chunk_geom(T, n_chunks, 8)[1]
 
 
-def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, y=None,
-                          z0=None, want_zT=False, ws=None, status=None, out7=None, opt=None, _rseq=None):
-    """The MSE training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_mse): forward,
-    loss and d(gscale/2 sum (y - target)^2)/d{Is_up, nVt_up, Is_down, nVt_down, R, C}, x [B,T] and target [T,B] read once, y
-    written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is rounded like asym_chunks(); y, ws, status,
-    out7 can be preallocated; opt: a binding.Adam(6, ...) to update theta6 in the step's last launch.
-    -> y [T,B], zT [B] | None, out7 = {sse, gtheta6}, status (int32[4]; read with mlp_tp_status())."""
+def _asym_step_args(who, ws_bytes, x, theta6, mode, target, n_chunks, y, z0, want_zT, ws, status, opt, rseq, finish=True):
+    """The checks and buffers the two one-pass steps of the two-different-diode clipper share
+    -> x, theta6, target, z0, rseq, B, T, K, y, zT, ws, status, Adam tail."""
+    rseq = _rseq_arg(rseq, x, mode, who)
     require_gpu()
     x, theta6, target, z0 = _f32_dev(x, "x"), _f32_dev(theta6, "theta6"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
     if theta6.numel() != 6:
@@ -1338,39 +1245,38 @@ def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup,
         raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
     if z0 is not None and z0.numel() != B:
         raise WdfHipError(f"z0 must hold one state per sequence ({B})")
-    if opt is not None and opt.n != 6:
-        raise WdfHipError("clipper_asym_step_mse: the optimizer holds {Is_up, nVt_up, Is_down, nVt_down, R, C}")
+    adam = _adam_tail(opt, 6, who, "{Is_up, nVt_up, Is_down, nVt_down, R, C}", finish)
     K = asym_chunks(T, n_chunks)
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
-    elif tuple(_f32_dev(y, "y").shape) != (T, B):
-        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
-    zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
-    need = lib().wdf_clipper_asym_step_mse_ws_bytes(B, K)
-    if ws is None:
-        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
-    elif ws.numel() * ws.element_size() < need:
-        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
+    y, zT = _y_zT(y, want_zT, T, B, x)
+    ws = _ws(ws, ws_bytes(B, K), x)
     if status is None:
         status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    if out7 is None:
-        out7 = torch.empty((7,), dtype=torch.float32, device=x.device)
-    elif _f32_dev(out7, "out7").numel() != 7:
-        raise WdfHipError("out7 must hold {sse, gtheta6}")
-    o = opt
+    return x, theta6, target, z0, rseq, B, T, K, y, zT, ws, status, adam
+
+
+def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, y=None,
+                          z0=None, want_zT=False, ws=None, status=None, out7=None, opt=None, rseq=None):
+    """The MSE training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_mse): forward,
+    loss and d(gscale/2 sum (y - target)^2)/d{Is_up, nVt_up, Is_down, nVt_down, R, C}, x [B,T] and target [T,B] read once, y
+    written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is rounded like asym_chunks(); y, ws, status,
+    out7 can be preallocated; opt: a binding.Adam(6, ...) to update theta6 in the step's last launch.  rseq [B]: one pot
+    resistance per sequence (wdf_clipper_asym_step_mse_rseq): theta6[4] is ignored, out7[5] (dR) is exactly 0 and opt never
+    writes theta6[4].
+    -> y [T,B], zT [B] | None, out7 = {sse, gtheta6}, status (int32[4]; read with mlp_tp_status())."""
+    x, theta6, target, z0, rseq, B, T, K, y, zT, ws, status, adam = _asym_step_args(
+        "clipper_asym_step_mse", lib().wdf_clipper_asym_step_mse_ws_bytes, x, theta6, mode, target, n_chunks, y, z0, want_zT, ws,
+        status, opt, rseq)
+    out7 = _out(out7, 7, "out7", "{sse, gtheta6}", x)
     rc, name = _asym_call(
-        "wdf_clipper_asym_step_mse", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(gscale), _ptr(y), _ptr(z0),
-        _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(out7),
-        *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
-        0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
-        None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
+        "wdf_clipper_asym_step_mse", rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(gscale),
+        _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(out7), *adam, _stream())
     _check(rc, name)
     return y, zT, out7, status
 
 
 def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup, tol=1e-12, max_iter=50,
                           verify_tol=1e-6, y=None, z0=None, want_zT=False, ws=None, status=None, sums14=None, gtheta6=None, loss3=None,
-                          finish=True, opt=None, _rseq=None):
+                          finish=True, opt=None, rseq=None):
     """The MSE + ESR training step of the two-different-diode clipper in one pass over the data (wdf_clipper_asym_step_esr):
     loss = S/n + sqrt(S / (E + eps_energy) / n) on the rows past `skip`, S = sum (y - target)^2, E = sum y^2, n = n_global.
     x [B,T] and target [T,B] read once, y written once, no stash.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is
@@ -1378,54 +1284,18 @@ def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, ski
     kernel forms gtheta6 = dloss/d{Is_up, nVt_up, Is_down, nVt_down, R, C} and loss3 = {mse, esr, mse + esr} itself, and
     opt (a binding.Adam(6, ...)) updates theta6 in the same last launch.  finish=False: one shard of several -- only sums14 =
     {S, E, gP[6], gQ[6]} of this call comes back (gtheta6 and loss3 are None): all-reduce it and call asym_esr_finish().
+    rseq [B]: one pot resistance per sequence (wdf_clipper_asym_step_esr_rseq): theta6[4] is ignored, component 4 of gP, gQ and
+    gtheta6 is exactly 0 and opt never writes theta6[4].
     -> y [T,B], zT [B] | None, sums14, gtheta6, loss3, status (int32[4]; read with mlp_tp_status())."""
-    require_gpu()
-    x, theta6, target, z0 = _f32_dev(x, "x"), _f32_dev(theta6, "theta6"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
-    if theta6.numel() != 6:
-        raise WdfHipError("theta6 must hold {Is_up, nVt_up, Is_down, nVt_down, R, C}")
-    B, T = x.shape
-    if tuple(target.shape) != (T, B):
-        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
-    if z0 is not None and z0.numel() != B:
-        raise WdfHipError(f"z0 must hold one state per sequence ({B})")
-    if opt is not None and (opt.n != 6 or not finish):
-        raise WdfHipError("clipper_asym_step_esr: the optimizer holds {Is_up, nVt_up, Is_down, nVt_down, R, C} and needs finish=True")
-    K = asym_chunks(T, n_chunks)
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
-    elif tuple(_f32_dev(y, "y").shape) != (T, B):
-        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
-    zT = torch.empty((B,), dtype=torch.float32, device=x.device) if want_zT else None
-    need = lib().wdf_clipper_asym_step_esr_ws_bytes(B, K)
-    if ws is None:
-        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
-    elif ws.numel() * ws.element_size() < need:
-        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
-    if status is None:
-        status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    if sums14 is None:
-        sums14 = torch.empty((14,), dtype=torch.float32, device=x.device)
-    elif _f32_dev(sums14, "sums14").numel() != 14:
-        raise WdfHipError("sums14 must hold {S, E, gP[6], gQ[6]}")
-    if not finish:
-        gtheta6 = loss3 = None
-    else:
-        if gtheta6 is None:
-            gtheta6 = torch.empty((6,), dtype=torch.float32, device=x.device)
-        elif _f32_dev(gtheta6, "gtheta6").numel() != 6:
-            raise WdfHipError("gtheta6 must hold six gradients")
-        if loss3 is None:
-            loss3 = torch.empty((3,), dtype=torch.float32, device=x.device)
-        elif _f32_dev(loss3, "loss3").numel() != 3:
-            raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
-    o = opt
+    x, theta6, target, z0, rseq, B, T, K, y, zT, ws, status, adam = _asym_step_args(
+        "clipper_asym_step_esr", lib().wdf_clipper_asym_step_esr_ws_bytes, x, theta6, mode, target, n_chunks, y, z0, want_zT, ws,
+        status, opt, rseq, finish)
+    sums14 = _out(sums14, 14, "sums14", "{S, E, gP[6], gQ[6]}", x)
+    gtheta6, loss3 = _esr_outs(finish, gtheta6, 6, "gtheta6", loss3, x)
     rc, name = _asym_call(
-        "wdf_clipper_asym_step_esr", _rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(n_global), float(eps_energy),
-        int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(sums14),
-        _ptr(gtheta6), _ptr(loss3),
-        *((None,) * 4 if o is None else (_ptr(o.m), _ptr(o.v), _ptr(o.step), _ptr(o.lr))),
-        0.0 if o is None else o.b1, 0.0 if o is None else o.b2, 0.0 if o is None else o.eps,
-        None if o is None else _ptr(o.lo), None if o is None else _ptr(o.hi), _stream())
+        "wdf_clipper_asym_step_esr", rseq, x, _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target), float(n_global),
+        float(eps_energy), int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status),
+        _ptr(sums14), _ptr(gtheta6), _ptr(loss3), *adam, _stream())
     _check(rc, name)
     return y, zT, sums14, gtheta6, loss3, status
 
@@ -1433,17 +1303,7 @@ def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, ski
 def asym_esr_finish(sums14, n_global, eps_energy, gtheta6=None, loss3=None):
     """Several ranks: sums14 = {S, E, gP[6], gQ[6]} summed over the ranks -> (gtheta6, loss3 = {mse, esr, mse + esr}), the
     global loss and its gradient (wdf_asym_esr_finish: the single-rank step's own formulas)."""
-    require_gpu()
-    sums14 = _f32_dev(sums14, "sums14")
-    if sums14.numel() != 14:
-        raise WdfHipError("sums14 must hold {S, E, gP[6], gQ[6]}")
-    if gtheta6 is None:
-        gtheta6 = torch.empty((6,), dtype=torch.float32, device=sums14.device)
-    if loss3 is None:
-        loss3 = torch.empty((3,), dtype=torch.float32, device=sums14.device)
-    _check(lib().wdf_asym_esr_finish(_ptr(sums14), float(n_global), float(eps_energy), _ptr(gtheta6), _ptr(loss3), _stream()),
-           "wdf_asym_esr_finish")
-    return gtheta6, loss3
+    return _esr_finish(lib().wdf_asym_esr_finish, sums14, "sums14", 6, (), n_global, eps_energy, gtheta6, "gtheta6", loss3)
 
 
 def asym_root(a, theta6, fs, mode, tol=1e-12, max_iter=50):
@@ -1595,6 +1455,7 @@ def ss_asym_step_built(ns, ni, loss="mse"):
 
 
 def _ss_asym_step_args(who, x, coef, rootp, ns, ni, target, n_chunks, y, z0, want_zT, ws, status):
+    require_gpu()
     x, coef, rootp, target, z0 = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(rootp, "rootp"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
     B, T = x.shape[0], x.shape[1]
     if x.numel() != B * T * ni or coef.numel() != lib().wdf_ss_ncoef(ns, ni):
@@ -1606,21 +1467,13 @@ def _ss_asym_step_args(who, x, coef, rootp, ns, ni, target, n_chunks, y, z0, wan
     if z0 is not None and tuple(z0.shape) != (ns, B):
         raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
     K = lib().wdf_ss_tp_chunks(T, int(n_chunks))
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=x.device)
-    elif tuple(_f32_dev(y, "y").shape) != (T, B):
-        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
-    zT = torch.empty((ns, B), dtype=torch.float32, device=x.device) if want_zT else None
+    y, zT = _y_zT(y, want_zT, T, B, x, ns)
     need = lib().wdf_ss_asym_step_ws_bytes(ns, ni, B, T, K)
     if need == 0:
         raise WdfHipError(f"{who}: no one-pass step is built for ns={ns}, ni={ni} (compose the loss from ss_fwd_tp and ss_bwd_tp)")
-    if ws is None:
-        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
-    elif ws.numel() * ws.element_size() < need:
-        raise WdfHipError(f"ws holds {ws.numel() * ws.element_size()} bytes, the step needs {need}")
     if status is None:
         status = torch.empty((4,), dtype=torch.int32, device=x.device)
-    return x, coef, rootp, target, z0, B, T, K, y, zT, ws, status
+    return x, coef, rootp, target, z0, B, T, K, y, zT, _ws(ws, need, x), status
 
 
 def ss_asym_step_mse(x, coef, rootp, ns, ni, target, gscale, n_chunks=1, warmup=0, tol=1e-6, y=None, z0=None, want_zT=False, ws=None,
@@ -1629,14 +1482,10 @@ def ss_asym_step_mse(x, coef, rootp, ns, ni, target, gscale, n_chunks=1, warmup=
     loss and d(gscale/2 sum (y - target)^2)/d{coef, rootp}; x [B,T,ni] and target [T,B] read once, y written once, no stash.
     n_chunks is rounded like ss_fwd_tp's (1: the exact sequential recursion); y, ws, status, out can be preallocated.
     -> y [T,B], zT [ns,B] | None, out = {sse, gcoef[ncoef], groot[5]}, status (int32[4]; read with ss_tp_status())."""
-    require_gpu()
     x, coef, rootp, target, z0, B, T, K, y, zT, ws, status = _ss_asym_step_args("ss_asym_step_mse", x, coef, rootp, ns, ni, target,
                                                                                n_chunks, y, z0, want_zT, ws, status)
     n = 1 + coef.numel() + 5
-    if out is None:
-        out = torch.empty((n,), dtype=torch.float32, device=x.device)
-    elif _f32_dev(out, "out").numel() != n:
-        raise WdfHipError(f"out must hold {{sse, gcoef, groot}} = {n} floats")
+    out = _out(out, n, "out", "{sse, gcoef, groot}", x)
     _check(lib().wdf_ss_asym_step_mse(_ptr(x), _ptr(coef), _ptr(rootp), int(ns), int(ni), _ptr(target), float(gscale), _ptr(y), _ptr(z0),
                                       _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status), _ptr(out), _stream()),
            "wdf_ss_asym_step_mse")
@@ -1650,27 +1499,13 @@ def ss_asym_step_esr(x, coef, rootp, ns, ni, target, n_global, eps_energy, skip,
     finish=True: a single rank -- the kernel forms g = dloss/d{coef, rootp} and loss3 = {mse, esr, mse + esr} itself.
     finish=False: one shard of several -- only sums = {S, E, gP[ncoef + 5], gQ[ncoef + 5]} of this call comes back.
     -> y [T,B], zT [ns,B] | None, sums, g, loss3, status (int32[4]; read with ss_tp_status())."""
-    require_gpu()
     x, coef, rootp, target, z0, B, T, K, y, zT, ws, status = _ss_asym_step_args("ss_asym_step_esr", x, coef, rootp, ns, ni, target,
                                                                                n_chunks, y, z0, want_zT, ws, status)
     if lib().wdf_ss_asym_step_esr_ws_bytes(ns, ni, B, T, K) == 0:
         raise WdfHipError(f"ss_asym_step_esr: no MSE + ESR step is built for ns={ns}, ni={ni}")
     ng = coef.numel() + 5
-    if sums is None:
-        sums = torch.empty((2 + 2 * ng,), dtype=torch.float32, device=x.device)
-    elif _f32_dev(sums, "sums").numel() != 2 + 2 * ng:
-        raise WdfHipError(f"sums must hold {{S, E, gP, gQ}} = {2 + 2 * ng} floats")
-    if not finish:
-        g = loss3 = None
-    else:
-        if g is None:
-            g = torch.empty((ng,), dtype=torch.float32, device=x.device)
-        elif _f32_dev(g, "g").numel() != ng:
-            raise WdfHipError(f"g must hold {ng} gradients")
-        if loss3 is None:
-            loss3 = torch.empty((3,), dtype=torch.float32, device=x.device)
-        elif _f32_dev(loss3, "loss3").numel() != 3:
-            raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
+    sums = _out(sums, 2 + 2 * ng, "sums", "{S, E, gP, gQ}", x)
+    g, loss3 = _esr_outs(finish, g, ng, "g", loss3, x)
     _check(lib().wdf_ss_asym_step_esr(_ptr(x), _ptr(coef), _ptr(rootp), int(ns), int(ni), _ptr(target), float(n_global), float(eps_energy),
                                       int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status),
                                       _ptr(sums), _ptr(g), _ptr(loss3), _stream()), "wdf_ss_asym_step_esr")
@@ -1692,6 +1527,7 @@ def _lin_step_shape(x_tm, coef, what="ss_lin_step_mse"):
 
 def _lin_step_args(what, ws_bytes, x_tm, coef, jac, target, n_chunks, z0, want_zT, ws, y):
     """The shape checks and buffers the two linear one-pass steps share -> x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT."""
+    require_gpu()
     x_tm, coef, target, z0 = _f32_dev(x_tm, "x_tm"), _f32_dev(coef, "coef"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
     ns, ni, B, T, ncoef = _lin_step_shape(x_tm, coef, what)
     if not (isinstance(jac, torch.Tensor) and jac.is_cuda and jac.dtype == torch.float64 and jac.is_contiguous() and jac.dim() == 2
@@ -1702,19 +1538,11 @@ def _lin_step_args(what, ws_bytes, x_tm, coef, jac, target, n_chunks, z0, want_z
         raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
     if ns > 0 and z0 is not None and tuple(z0.shape) != (ns, B):
         raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
-    if y is None:
-        y = torch.empty((T, B), dtype=torch.float32, device=x_tm.device)
-    elif tuple(_f32_dev(y, "y").shape) != (T, B):
-        raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
+    y, zT = _y_zT(y, want_zT and ns > 0, T, B, x_tm, ns)
     need = ws_bytes(ns, ni, B, T, int(n_chunks))
     if need == 0:
         raise WdfHipError(f"{what}: no step for ns={ns}, ni={ni}, B={B}, T={T}, n_chunks={n_chunks}")
-    if ws is None:
-        ws = torch.zeros((need,), dtype=torch.uint8, device=x_tm.device)
-    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.is_contiguous()) or ws.numel() * ws.element_size() < need:
-        raise WdfHipError(f"ws must hold the {need} bytes the step needs, on the GPU")
-    zT = torch.empty((ns, B), dtype=torch.float32, device=x_tm.device) if (want_zT and ns > 0) else None
-    return x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT
+    return x_tm, coef, target, z0, ns, ni, B, T, n_params, y, _ws(ws, need, x_tm, zeroed=True), zT
 
 
 def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=False, want_gcoef=False, ws=None, y=None):
@@ -1724,7 +1552,6 @@ def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=
     ws: zeroed wdf_ss_lin_step_ws_bytes() bytes when not given (the step leaves it clean); y, ws and z0 are used as they are --
     the library pairs sequences up by their addresses.
     -> dict: y [T,B], out [1 + n_params] = {SSE, gradients}, loss (0-dim), gcoef [ns^2 + ns ni + ns + ni] | None, zT [ns,B] | None, ws."""
-    require_gpu()
     x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_mse", lib().wdf_ss_lin_step_ws_bytes, x_tm, coef,
                                                                                jac, target, n_chunks, z0, want_zT, ws, y)
     out = torch.empty((1 + n_params,), dtype=torch.float32, device=x_tm.device)
@@ -1748,7 +1575,6 @@ def ss_lin_step_esr(x_tm, coef, jac, target, skip, n_chunks, n_global=None, eps=
     finish=False: one shard of several -- only sums comes back (g and loss3 None): add the shards' sums and call ss_lin_esr_finish().
     -> dict: y [T,B], sums [2 + 2 n_params] = {S, E, gP, gQ}, g [n_params] | None, loss3 [3] = {mse, esr, mse + esr} | None,
     gcoef [2 (ns^2 + ns ni + ns + ni)] = {GP, GQ} | None, zT [ns,B] | None, ws."""
-    require_gpu()
     x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_esr", lib().wdf_ss_lin_step_esr_ws_bytes, x_tm,
                                                                                coef, jac, target, n_chunks, z0, want_zT, ws, y)
     skip = int(skip)
@@ -1759,8 +1585,7 @@ def ss_lin_step_esr(x_tm, coef, jac, target, skip, n_chunks, n_global=None, eps=
         raise WdfHipError("ss_lin_step_esr: n_global > 0 and eps >= 0")
     dev = x_tm.device
     sums = torch.empty((2 + 2 * n_params,), dtype=torch.float32, device=dev)
-    g = torch.empty((n_params,), dtype=torch.float32, device=dev) if finish else None
-    loss3 = torch.empty((3,), dtype=torch.float32, device=dev) if finish else None
+    g, loss3 = _esr_outs(finish, None, n_params, "g", None, x_tm)
     gcoef = torch.empty((2 * (ns * ns + ns * ni + ns + ni),), dtype=torch.float32, device=dev) if want_gcoef else None
     _check(lib().wdf_ss_lin_step_esr(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), n_global, float(eps), skip, _ptr(y),
                                      _ptr(ws), _ptr(sums), _ptr(g), _ptr(loss3), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT),
@@ -1772,23 +1597,12 @@ def ss_lin_esr_finish(sums, n_global, eps=ESR_EPS, g=None, loss3=None):
     """Several ranks: sums = {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> (g [n_params], loss3 = {mse, esr,
     mse + esr}), the global loss and its gradient (wdf_ss_lin_esr_finish: the single-rank step's own formulas)."""
     require_gpu()
-    sums = _f32_dev(sums, "sums")
-    n_params = (sums.numel() - 2) // 2
-    if sums.dim() != 1 or sums.numel() != 2 + 2 * n_params or not 1 <= n_params <= 15:
+    n_params = (_f32_dev(sums, "sums").numel() - 2) // 2
+    if sums.dim() != 1 or not 1 <= n_params <= 15:
         raise WdfHipError("sums must hold {S, E, gP[n_params], gQ[n_params]} with 1..15 parameters")
     if not float(n_global) > 0.0 or not float(eps) >= 0.0:
         raise WdfHipError("ss_lin_esr_finish: n_global > 0 and eps >= 0")
-    if g is None:
-        g = torch.empty((n_params,), dtype=torch.float32, device=sums.device)
-    elif _f32_dev(g, "g").numel() != n_params:
-        raise WdfHipError(f"g must hold {n_params} gradients")
-    if loss3 is None:
-        loss3 = torch.empty((3,), dtype=torch.float32, device=sums.device)
-    elif _f32_dev(loss3, "loss3").numel() != 3:
-        raise WdfHipError("loss3 must hold {mse, esr, mse + esr}")
-    _check(lib().wdf_ss_lin_esr_finish(_ptr(sums), n_params, float(n_global), float(eps), _ptr(g), _ptr(loss3), _stream()),
-           "wdf_ss_lin_esr_finish")
-    return g, loss3
+    return _esr_finish(lib().wdf_ss_lin_esr_finish, sums, "sums", n_params, (n_params,), n_global, eps, g, "g", loss3)
 
 
 PROBE_MAX_OPS, PROBE_MAX_PARAMS = 384, 15                                            # csrc/wdf_ss_step.h
@@ -2137,8 +1951,7 @@ class Adam:
         grad = _f32_dev(grad, "grad")
         if theta.numel() != self.n or grad.numel() != self.n:
             raise WdfHipError(f"Adam: expected {self.n} parameters")
-        rc = lib().wdf_adam_step(_ptr(theta), _ptr(grad), _ptr(self.m), _ptr(self.v), _ptr(self.step), _ptr(self.lr),
-                                 self.b1, self.b2, self.eps, _ptr(self.lo), _ptr(self.hi), self.n, _stream())
+        rc = lib().wdf_adam_step(_ptr(theta), _ptr(grad), *_adam_args(self), self.n, _stream())
         _check(rc, "wdf_adam_step")
 
 

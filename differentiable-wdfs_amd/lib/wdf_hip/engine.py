@@ -203,21 +203,14 @@ class _ClipperAsymFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta6, x, fs, tol, max_iter, tp, mode, z0, rseq=None):
         th = theta6.detach().contiguous()
-        if rseq is not None:                     # one pot per sequence (the *_rseq entry points): theta6[4] is ignored
-            if tp is not None and tp.k_fwd > 1:
-                y, zT, zs, st = binding.clipper_asym_fwd_tp_rseq(x, rseq, th, fs, mode, tp.k_fwd, tp.warmup, tol=tol, max_iter=max_iter,
-                                                                 verify_tol=tp.tol, z0=z0, want_stash=True, want_zT=True)
-                LAST_TP_STATUS["status"] = st
-            else:
-                y, zT, _, zs = binding.clipper_asym_fwd_rseq(x, rseq, th, fs, mode, tol=tol, max_iter=max_iter, z0=z0, want_stash=True,
-                                                             want_zT=True)
-        elif tp is not None and tp.k_fwd > 1:    # time chunks, verified on the device (wdf_clipper_asym_fwd_tp)
+        # rseq: one pot per sequence (the *_rseq entry points): theta6[4] is ignored
+        if tp is not None and tp.k_fwd > 1:      # time chunks, verified on the device (wdf_clipper_asym_fwd_tp)
             y, zT, zs, st = binding.clipper_asym_fwd_tp(x, th, fs, mode, tp.k_fwd, tp.warmup, tol=tol, max_iter=max_iter,
-                                                        verify_tol=tp.tol, z0=z0, want_stash=True, want_zT=True)
+                                                        verify_tol=tp.tol, z0=z0, want_stash=True, want_zT=True, rseq=rseq)
             LAST_TP_STATUS["status"] = st
         else:
             y, zT, _, zs = binding.clipper_asym_fwd(x, th, fs, mode, tol=tol, max_iter=max_iter, z0=z0, want_stash=True,
-                                                    want_zT=True)
+                                                    want_zT=True, rseq=rseq)
         B, T = x.shape
         if tp is not None:
             k_bwd = int(tp.k_bwd)
@@ -239,6 +232,16 @@ class _ClipperAsymFn(torch.autograd.Function):
         else:
             g = binding.clipper_asym_bwd_tp(x, th, fs, mode, zs, zT, gy.contiguous(), max(1, k_bwd))
         return g, None, None, None, None, None, None, None, None
+
+
+def _z0_of(z0, x):
+    """z0: None or the state [B] a two-different-diode call starts from -> None or that state detached, float32 and flat on x's device."""
+    if z0 is None:
+        return None
+    z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+    if z0.numel() != x.shape[0]:
+        raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    return z0
 
 
 def _rseq_of(r, x):
@@ -265,10 +268,7 @@ def clipper_asym(theta6, x, fs, tol=1.0e-12, max_iter=50, tp=None, mode=None, z0
     r: one pot resistance per sequence -- [B], or a [B,T] channel constant along T (binding.r_per_sequence) -- in place of
     theta6[4], which is then ignored and receives a zero gradient (Newton modes; plan with engine.resistance_max(r))."""
     mode = binding.ASYM_NEWTON_F64 if mode is None else int(mode)
-    if z0 is not None:
-        z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
-        if z0.numel() != x.shape[0]:
-            raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    z0 = _z0_of(z0, x)
     if r is not None:
         y, zT = _ClipperAsymFn.apply(theta6, x, float(fs), float(tol), int(max_iter), tp, mode, z0, _rseq_of(r, x))
     else:
@@ -309,11 +309,8 @@ class AsymMseStep:
         theta6[4]; the stepper's plan must come from the largest pot).  Fills self.y, self.out, self.status."""
         kw = dict(tol=self.tol, max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws,
                   status=self.status, out7=self.out, opt=adam)
-        if r is None:
-            _, self.zT, _, _ = binding.clipper_asym_step_mse(x, theta6, self.fs, self.mode, target, self.gscale, self.k, self.warmup, **kw)
-        else:
-            _, self.zT, _, _ = binding.clipper_asym_step_mse_rseq(x, r, theta6, self.fs, self.mode, target, self.gscale, self.k,
-                                                                  self.warmup, **kw)
+        _, self.zT, _, _ = binding.clipper_asym_step_mse(x, theta6, self.fs, self.mode, target, self.gscale, self.k, self.warmup, rseq=r,
+                                                         **kw)
         return self.sse, self.gtheta
 
 
@@ -357,10 +354,7 @@ def clipper_asym_mse(theta6, x, target, fs, tp=None, mode=None, z0=None, return_
     r: one pot resistance per sequence ([B], or a [B,T] channel constant along T) in place of theta6[4], as in clipper_asym.
     -> loss, or (loss, y [T,B], zT [B]) with return_state: the call's output and final state, detached."""
     mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
-    if z0 is not None:
-        z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
-        if z0.numel() != x.shape[0]:
-            raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    z0 = _z0_of(z0, x)
     if r is not None:
         return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state), _rseq_of(r, x))
     return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state))
@@ -401,12 +395,8 @@ class AsymEsrStep:
         Fills self.y, self.sums, self.status and -- finish -- self.loss3, self.gtheta."""
         kw = dict(tol=self.tol, max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, z0=z0, want_zT=want_zT, ws=self.ws,
                   status=self.status, sums14=self.sums, gtheta6=self.gtheta, loss3=self.loss3, finish=finish, opt=adam)
-        if r is None:
-            self.zT = binding.clipper_asym_step_esr(x, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy, self.skip,
-                                                    self.k, self.warmup, **kw)[1]
-        else:
-            self.zT = binding.clipper_asym_step_esr_rseq(x, r, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy,
-                                                         self.skip, self.k, self.warmup, **kw)[1]
+        self.zT = binding.clipper_asym_step_esr(x, theta6, self.fs, self.mode, target, self.n_global, self.eps_energy, self.skip,
+                                                self.k, self.warmup, rseq=r, **kw)[1]
         return self.loss3, self.gtheta
 
 
@@ -456,10 +446,7 @@ def clipper_asym_mse_esr(theta6, x, target, fs, skip=0, tp=None, mode=None, z0=N
     r: one pot resistance per sequence ([B], or a [B,T] channel constant along T) in place of theta6[4], as in clipper_asym.
     -> loss, or (loss, y [T,B], zT [B]) with return_state: the call's output and final state, detached."""
     mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
-    if z0 is not None:
-        z0 = z0.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
-        if z0.numel() != x.shape[0]:
-            raise binding.WdfHipError(f"z0 must hold one state per sequence ({x.shape[0]}), got {z0.numel()}")
+    z0 = _z0_of(z0, x)
     if r is not None:
         return _ClipperAsymEsrFn.apply(theta6, x, target, float(fs), int(skip), tp, mode, z0, bool(return_state), _rseq_of(r, x))
     return _ClipperAsymEsrFn.apply(theta6, x, target, float(fs), int(skip), tp, mode, z0, bool(return_state))

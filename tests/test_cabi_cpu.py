@@ -33,6 +33,63 @@ def test_every_declared_symbol_is_exported(lib):
     assert set(binding.EXPORTED_SYMBOLS) == set(syms)
 
 
+C_SCALARS = {"float": C.c_float, "double": C.c_double, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t,
+             "long long": C.c_longlong}
+
+
+def _c_class(text, what):
+    """The class of one C parameter (`const float* x`) or return type (`size_t`): "pointer" for anything with a *, None for void,
+    the ctypes scalar otherwise.  A type this does not know fails the test."""
+    if "*" in text:
+        return "pointer"
+    words = [w for w in text.split() if w != "const"]
+    if what == "parameter":
+        assert len(words) >= 2, f"parameter without a name: {text!r}"
+        words = words[:-1]
+    ctype = " ".join(words)
+    if ctype == "void" and what == "return":
+        return None
+    assert ctype in C_SCALARS, f"unknown C type {ctype!r} in {what} {text!r}"
+    return C_SCALARS[ctype]
+
+
+def _table_class(ct):
+    if ct is None:
+        return None
+    if ct in (C.c_void_p, C.c_char_p) or issubclass(ct, C._Pointer):
+        return "pointer"
+    assert ct in C_SCALARS.values(), f"the table uses {ct}, which no C type of the header maps to"
+    return ct
+
+
+def declared_signatures():
+    """name -> (return class, [parameter classes]) of every declaration in include/wdf_hip.h."""
+    src = open(os.path.join(REPO, "include", "wdf_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", "", src, flags=re.M)
+    sigs = {}
+    for ret, name, args in re.findall(r"([\w \t\*]+?)\s*\b(wdf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in sigs, f"{name} is declared twice"
+        args = [a for a in (" ".join(a.split()) for a in args.split(",")) if a and a != "void"]
+        sigs[name] = (_c_class(" ".join(ret.split()), "return"), [_c_class(a, "parameter") for a in args])
+    return sigs
+
+
+def test_signature_table_matches_the_header():
+    """Every declaration's return type, parameter count and each parameter's class (pointer / float / double / int / int32_t /
+    int64_t / size_t / long long) against binding.SIGNATURES -- the table lib() applies.  Needs no built library."""
+    from wdf_hip import binding
+    sigs = declared_signatures()
+    assert sorted(sigs) == declared_symbols() == sorted(binding.SIGNATURES)
+    for name, (ret, params) in sigs.items():
+        restype, argtypes = binding.SIGNATURES[name]
+        assert _table_class(restype) == ret, f"{name}: returns {ret} in the header, {restype} in the table"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters in the header, {len(argtypes)} in the table"
+        for i, (a, want) in enumerate(zip(argtypes, params)):
+            assert _table_class(a) == want, f"{name}: parameter {i} is {want} in the header, {a} in the table"
+    assert binding.EXPORTED_SYMBOLS == tuple(binding.SIGNATURES)
+
+
 def test_nothing_but_the_declared_symbols_is_exported(lib):
     """The other direction: the dynamic symbol table of the shipped library is EXACTLY the header (built with
     -fvisibility=hidden + csrc/exports.map: no helper of a translation unit, no kernel host stub leaks out)."""
