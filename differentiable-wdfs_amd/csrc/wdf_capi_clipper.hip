@@ -9,20 +9,11 @@
 #include "wdf_capi_common.h"
 #include "wdf_clipper.h"
 #include "wdf_clipper_fused.h"
+#include "wdf_capi_clipper_step.h"
 #include "wdf_omega64.h"
 using namespace wdfcapi;
 
 namespace {
-
-// The kernels' four leading template parameters from runtime values: dyn is Bools{r != nullptr} or, where a kernel also has the
-// one-value-per-sequence form, Values<int, 0, 1, 2>.  TM && V4 is never built: a time-major x has no 4-step rows to load.
-template <class Dyn, class F> bool dispatch4(F&& f, Dyn dyn, bool sym, bool tm, bool v4)
-{
-    return dispatch([&](auto DYN, auto SYM, auto TM, auto V4) {
-        if constexpr (TM() && V4()) return false;
-        else return dispatch([&] { return f(DYN, SYM, TM, V4); });
-    }, dyn, Bools{sym}, Bools{tm}, Bools{v4});
-}
 
 template <bool DYN_R, bool SYM, bool TM, bool V4>
 void launch_fwd(const float* x, const float* r, const float* theta, float fs, int n_up, int n_down, float* y,
@@ -516,9 +507,12 @@ static int step_tp_common(const float* x, const float* r, float* theta, float fs
                           int warmup, float tol, void* ws, void* status, void* state, int max_warm_tiles, bool esr,
                           wdf::FusedOut out, int flags, void* stream, const char* what)
 {
-    int rc = check_common(x, theta, n_up, n_down, B, T, flags & ~(WDF_ONE_SEQUENCE_PER_LANE | WDF_R_PER_SEQUENCE));
+    int rc = check_common(x, theta, n_up, n_down, B, T, flags & ~(WDF_ONE_SEQUENCE_PER_LANE | WDF_R_PER_SEQUENCE | WDF_NO_Y_STORE));
     if (rc) return rc;
-    if (!target || !y || !ws || !status) return fail(WDF_EINVAL, "null target/y/ws/status");
+    // WDF_NO_Y_STORE: the training-only step; a y handed in with it would silently stay unwritten
+    const bool store_y = !(flags & WDF_NO_Y_STORE);
+    if (!store_y && y) return fail(WDF_EINVAL, "%s: y must be NULL with WDF_NO_Y_STORE (it would stay unwritten)", what);
+    if (!target || (store_y && !y) || !ws || !status) return fail(WDF_EINVAL, "null target/y/ws/status");
     if (!(fs > 0.0f)) return fail(WDF_EINVAL, "fs must be positive");
     if (n_chunks < 1 || warmup < 0 || !(tol >= 0.0f)) return fail(WDF_EINVAL, "n_chunks >= 1, warmup >= 0, tol >= 0");
     if (skip < 0 || skip > T) return fail(WDF_EINVAL, "skip must be in 0..T");
@@ -539,14 +533,24 @@ static int step_tp_common(const float* x, const float* r, float* theta, float fs
     }
     const bool tm = (flags & WDF_X_TIME_MAJOR) != 0;
     const bool v4 = !tm && (T % 4 == 0) && T < (1 << 23) && aligned16(x) && (!r || aligned16(r));
-    // two adjacent sequences per lane (8-byte row accesses, packed arithmetic) whenever the rows allow it
+    // two adjacent sequences per lane (8-byte row accesses, packed arithmetic) whenever the rows allow it (a null y: aligned)
     const bool pairs = !(flags & WDF_ONE_SEQUENCE_PER_LANE) && (B % 2 == 0) && aligned8(x) && aligned8(target) && aligned8(y) &&
                        (!r || aligned8(r));
     // WDF_R_PER_SEQUENCE: one pot value per sequence (the caller vouches for it): calc_impedance once per chunk, the channel not streamed
     const int dyn = r == nullptr ? 0 : ((flags & WDF_R_PER_SEQUENCE) ? 2 : 1);
     const int64_t n_waves = (B + (pairs ? 127 : 63)) / (pairs ? 128 : 64) * (int64_t)g.K;
-    const int form = fused_form(g.K, !tm && v4 && dyn != 1);    // (wdf::fused_x_window)
+    // (a step without y is built for the default form only: the finish launch; one chunk: the chunk kernel alone)
+    const int form = store_y ? fused_form(g.K, !tm && v4 && dyn != 1)    // (wdf::fused_x_window)
+                             : (g.K < 2 ? wdf::kFusedInKernel : wdf::kFusedFinishLater);
     const int64_t skew = fused_skew(n_waves, g.K, g.L, T, state ? max_warm_tiles : 0, form == wdf::kFusedGroup);
+    if (!store_y) {                                          // the instantiations without the y store: wdf_capi_clipper_noy.hip
+        const FusedWs w = fused_ws(ws, B, g.K);
+        const FusedNoYLaunch a{x, r, theta, fs, n_up, n_down, target, hgs, skip, z0, zT, w.zwarm, w.zend, w.rec, w.part, w.wpart, w.tickets,
+                               w.gticket, w.grp, (wdf::TpStatus*)status, warm.ctl, warm.snap, warm.J, tol, B, T, g.K, g.L, W,
+                               (flags & WDF_GENERAL_ROOT) ? 1 : 0, pairs, esr, out, skew, form, (hipStream_t)stream};
+        if (!launch_fused_noy(dyn, n_up == n_down, tm, v4, a)) return no_kernel(what);
+        return check_launch(what);
+    }
     const bool ok = dispatch4([&](auto DYN, auto SYM, auto TM, auto V4) {
         launch_fused<DYN(), SYM(), TM(), V4()>(x, r, theta, fs, n_up, n_down, target, hgs, skip, y, z0, zT, fused_ws(ws, B, g.K),
                                                (wdf::TpStatus*)status, tol, B, T, g, W, warm, (flags & WDF_GENERAL_ROOT) ? 1 : 0, pairs, esr, out,

@@ -328,8 +328,9 @@ size_t lin_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks, int
 }
 
 // Both losses' launches, arguments already checked: pass 1 where there is a state to carry across a chunk boundary, then pass 2
-// (the bracketed one) with the loss's own scalars and outputs in `a`.
-template <int LOSS>
+// (the bracketed one) with the loss's own scalars and outputs in `a`.  STORE_Y = false (the _noy exports): y is null and the
+// instantiation without the y store runs.
+template <int LOSS, bool STORE_Y = true>
 int lin_step_launch(const char* what, const float* x, const float* coef, const double* jac, int n_params, int ns, int ni,
                     const float* target, float* y, void* ws, float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0,
                     float* zT, const typename wdf::LinLoss<LOSS>::type& a, hipStream_t s)
@@ -350,10 +351,41 @@ int lin_step_launch(const char* what, const float* x, const float* coef, const d
         using V = std::conditional_t<PAIR(), wdf::v2f, float>;
         if (NS() > 0 && K > 1) hipLaunchKernelGGL((wdf::ss_lin_step_zero_kernel<NS(), NI(), V>), grid, dim3(64), 0, s, x, coef, uend0, B, T, L);
         EventBracket bracket(s);
-        hipLaunchKernelGGL((wdf::ss_lin_step_kernel<NS(), NI(), V, LOSS>), grid, dim3(64), 0, s, x, coef, (const float*)uend0, target, y,
+        hipLaunchKernelGGL((wdf::ss_lin_step_kernel<NS(), NI(), V, LOSS, STORE_Y>), grid, dim3(64), 0, s, x, coef, (const float*)uend0, target, y,
                            part, ticket, jac, n_params, gcoef_out, B, T, L, z0, zT, a);
     }, Values<int, 0, 1, 2>{ns}, SsInputs{ni}, Bools{pair});
     return ok ? check_launch(what) : no_kernel(what);
+}
+
+// The two losses' argument checks, shared by an export and its _noy twin (STORE_Y = false: there is no y to check or pass).
+template <bool STORE_Y>
+int lin_step_mse(const char* what, const float* x, const float* coef, const double* jac, int n_params, int ns, int ni, const float* target,
+                 float gscale, float* y, void* ws, float* out, float* loss_out, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
+                 const float* z0, float* zT, void* stream)
+{
+    if (z0 && z0 == zT) return fail(WDF_EINVAL, "%s: zT must not alias z0 (every chunk reads z0)", what);
+    if (!x || !coef || !jac || !target || (STORE_Y && !y) || !ws || !out) return fail(WDF_EINVAL, "null argument");
+    if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "%s: ns in 0..2, ni in 1..2 (got %d, %d)", what, ns, ni);
+    if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams) return fail(WDF_EINVAL, "B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
+    return lin_step_launch<0, STORE_Y>(what, x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
+                                       wdf::LinMse{gscale, out, loss_out}, (hipStream_t)stream);
+}
+
+template <bool STORE_Y>
+int lin_step_esr(const char* what, const float* x, const float* coef, const double* jac, int n_params, int ns, int ni, const float* target,
+                 double n_global, double eps_energy, int64_t skip, float* y, void* ws, float* sums, float* g, float* loss3,
+                 float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0, float* zT, void* stream)
+{
+    if (z0 && z0 == zT) return fail(WDF_EINVAL, "%s: zT must not alias z0 (every chunk reads z0)", what);
+    if (!x || !coef || !jac || !target || (STORE_Y && !y) || !ws) return fail(WDF_EINVAL, "%s: null argument", what);
+    if (!sums && !g) return fail(WDF_EINVAL, "%s: sums and g are both null (nothing to hand back)", what);
+    if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "%s: ns in 0..2, ni in 1..2 (got %d, %d)", what, ns, ni);
+    if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams)
+        return fail(WDF_EINVAL, "%s: B, T, n_chunks >= 1, 1..%d parameters", what, wdf::kProbeMaxParams);
+    if (skip < 0 || skip >= T) return fail(WDF_EINVAL, "%s: skip must be in [0, T) (got %lld, T = %lld)", what, (long long)skip, (long long)T);
+    if (!(n_global > 0.0) || !(eps_energy >= 0.0)) return fail(WDF_EINVAL, "%s: n_global > 0 and eps_energy >= 0", what);
+    return lin_step_launch<1, STORE_Y>(what, x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
+                                       wdf::LinEsr{skip, n_global, eps_energy, sums, g, loss3}, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -374,12 +406,17 @@ int wdf_ss_lin_step_mse(const float* x, const float* coef, const double* jac, in
                         float gscale, float* y, void* ws, float* out, float* loss_out, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
                         const float* z0, float* zT, void* stream)
 {
-    if (z0 && z0 == zT) return fail(WDF_EINVAL, "wdf_ss_lin_step_mse: zT must not alias z0 (every chunk reads z0)");
-    if (!x || !coef || !jac || !target || !y || !ws || !out) return fail(WDF_EINVAL, "null argument");
-    if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "wdf_ss_lin_step_mse: ns in 0..2, ni in 1..2 (got %d, %d)", ns, ni);
-    if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams) return fail(WDF_EINVAL, "B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
-    return lin_step_launch<0>("wdf_ss_lin_step_mse", x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
-                              wdf::LinMse{gscale, out, loss_out}, (hipStream_t)stream);
+    return lin_step_mse<true>("wdf_ss_lin_step_mse", x, coef, jac, n_params, ns, ni, target, gscale, y, ws, out, loss_out, gcoef_out, B, T,
+                              n_chunks, z0, zT, stream);
+}
+
+// wdf_ss_lin_step_mse without y: the same checks, workspace and results, the output never stored (12 B/sample instead of 16).
+int wdf_ss_lin_step_mse_noy(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni, const float* target,
+                            float gscale, void* ws, float* out, float* loss_out, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
+                            const float* z0, float* zT, void* stream)
+{
+    return lin_step_mse<false>("wdf_ss_lin_step_mse_noy", x, coef, jac, n_params, ns, ni, target, gscale, nullptr, ws, out, loss_out,
+                               gcoef_out, B, T, n_chunks, z0, zT, stream);
 }
 
 // The MSE + ESR step: the MSE step's layout with twice the partial sums per wave ({GP, S} and {GQ, E}).
@@ -393,16 +430,17 @@ int wdf_ss_lin_step_esr(const float* x, const float* coef, const double* jac, in
                         double n_global, double eps_energy, int64_t skip, float* y, void* ws, float* sums, float* g, float* loss3,
                         float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0, float* zT, void* stream)
 {
-    if (z0 && z0 == zT) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: zT must not alias z0 (every chunk reads z0)");
-    if (!x || !coef || !jac || !target || !y || !ws) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: null argument");
-    if (!sums && !g) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: sums and g are both null (nothing to hand back)");
-    if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "wdf_ss_lin_step_esr: ns in 0..2, ni in 1..2 (got %d, %d)", ns, ni);
-    if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams)
-        return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
-    if (skip < 0 || skip >= T) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: skip must be in [0, T) (got %lld, T = %lld)", (long long)skip, (long long)T);
-    if (!(n_global > 0.0) || !(eps_energy >= 0.0)) return fail(WDF_EINVAL, "wdf_ss_lin_step_esr: n_global > 0 and eps_energy >= 0");
-    return lin_step_launch<1>("wdf_ss_lin_step_esr", x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
-                              wdf::LinEsr{skip, n_global, eps_energy, sums, g, loss3}, (hipStream_t)stream);
+    return lin_step_esr<true>("wdf_ss_lin_step_esr", x, coef, jac, n_params, ns, ni, target, n_global, eps_energy, skip, y, ws, sums, g,
+                              loss3, gcoef_out, B, T, n_chunks, z0, zT, stream);
+}
+
+// wdf_ss_lin_step_esr without y (wdf_ss_lin_esr_finish serves both).
+int wdf_ss_lin_step_esr_noy(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni, const float* target,
+                            double n_global, double eps_energy, int64_t skip, void* ws, float* sums, float* g, float* loss3,
+                            float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0, float* zT, void* stream)
+{
+    return lin_step_esr<false>("wdf_ss_lin_step_esr_noy", x, coef, jac, n_params, ns, ni, target, n_global, eps_energy, skip, nullptr, ws,
+                               sums, g, loss3, gcoef_out, B, T, n_chunks, z0, zT, stream);
 }
 
 // sums: {S, E, gP[n_params], gQ[n_params]} summed over the ranks -> g [n_params] and (optional) loss3, one small launch.

@@ -32,6 +32,14 @@
 // shuffles: the pair lives in an aligned VGPR pair from its 8-byte load to its 8-byte store), transcendentals, compares
 // and selects stay per component.  54 issue slots per sample-step instead of 88.  Needs an even B; V = float is the
 // same code for odd batches and for A/B.
+//
+// WITHOUT THE y STORE (STORE_Y = false).  A training loop reads the loss and the gradient, not y (clipper_pot.py:245-269), and
+// the step forms both from y in registers: the store is 4 of the 12 B/sample.  STORE_Y is a compile-time argument of the chunk
+// body, clipper_fused_tp_kernel, the repair walk (fused_rerun_chunk, fused_repair_tile) and clipper_fused_finish_kernel; false
+// compiles the two stores of y out (`if constexpr`), no address is formed from y and the host passes nullptr.  Everything else --
+// state, tangents, records, snapshots, zT, verification, repair, status and warm-start steering, reduction, chain rule, Adam --
+// is the code it was.  Built for the default launch form only (kFusedFinishLater; one chunk: no second launch): the group form
+// and the round-5 in-kernel repair launch are not instantiated for it, whatever WDF_FUSED_FINISH says.
 #pragma once
 
 #include "wdf_clipper.h"
@@ -651,7 +659,7 @@ template <int NSEQ, int LOSS> struct GroupStage {
 // k of K: the wave's chunk (the kernels say which: a workgroup may hold several chunk waves).
 // LOSS = 0: the plain time-parallel forward (no target, no tangent, no record; STASH: the state before every step goes to
 // zstash [T][B] for the reverse sweep) -- clipper_fwd_tp_kernel below runs this same body.
-template <int DYN_R, bool SYM, bool TM, bool VEC4, int FAST, typename V, int LOSS, bool STASH = false>
+template <int DYN_R, bool SYM, bool TM, bool VEC4, int FAST, typename V, int LOSS, bool STASH = false, bool STORE_Y = true>
 __device__ __forceinline__ void clipper_fused_body(
     const ClipConsts& c_in, const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ target,
     float* __restrict__ y, float* __restrict__ zstash, const float* __restrict__ z0, float* __restrict__ zT, float* __restrict__ zwarm,
@@ -660,6 +668,7 @@ __device__ __forceinline__ void clipper_fused_body(
     int64_t skew = 0, double* wpart = nullptr, GroupStage<VT<V>::N, LOSS>* gs = nullptr)
 {
     constexpr int NR = FusedTile<V, DYN_R>::NR;
+    static_assert(STORE_Y || LOSS != 0, "the plain forward has nothing but y to leave");
 #ifdef WDF_DBG_TIMES
     unsigned long long dbg_p[5];
     dbg_p[0] = __builtin_amdgcn_s_memtime();
@@ -767,8 +776,9 @@ __device__ __forceinline__ void clipper_fused_body(
         const bool more = t + NR < nfull_end;
         if (snapw != nullptr && t1 - t <= (int64_t)kWarmStep * (J - 1) && (t1 - t) % kWarmStep == 0)
             store_own<V>(snapw + ((t1 - t) / kWarmStep) * K * B, q, z);   // snapshot kWarmStep j steps before the chunk's end
-        const __amdgpu_buffer_rsrc_t ry = row_rsrc(y + t * B);
-        const __amdgpu_buffer_rsrc_t rz = row_rsrc(STASH ? zstash + t * B : y + t * B);
+        // (STORE_Y = false: y is null and no address is formed from it)
+        [[maybe_unused]] const __amdgpu_buffer_rsrc_t ry = row_rsrc(STORE_Y ? y + t * B : nullptr);
+        [[maybe_unused]] const __amdgpu_buffer_rsrc_t rz = row_rsrc(STASH ? zstash + t * B : (STORE_Y ? y + t * B : nullptr));
         // steps of this tile below `skip` carry no loss (skip_samples = 50, clipper_pot.py:232): their number, a scalar
         const int64_t below = skip - t;
         const int n_masked = __builtin_amdgcn_readfirstlane((int)(below < 0 ? 0 : (below > NR ? NR : below)));
@@ -792,8 +802,11 @@ __device__ __forceinline__ void clipper_fused_body(
                 buf_store_nt(fwd_step<DYN_R, SYM, V, FAST>(c, xc[i], rc[i], z), ry, boff, i * rowb);
                 continue;
             }
-            buf_store_nt(fused_step<DYN_R, SYM, FAST, V, LOSS>(c, xc[i], rc[i], gc[i], step_loss_scale(i, n_masked, hgs), z, s), ry, boff,
-                         i * rowb);
+            if constexpr (STORE_Y)
+                buf_store_nt(fused_step<DYN_R, SYM, FAST, V, LOSS>(c, xc[i], rc[i], gc[i], step_loss_scale(i, n_masked, hgs), z, s), ry, boff,
+                             i * rowb);
+            else
+                (void)fused_step<DYN_R, SYM, FAST, V, LOSS>(c, xc[i], rc[i], gc[i], step_loss_scale(i, n_masked, hgs), z, s);
             // The tangent updates do not feed the next step's state, so left alone instruction selection
             // emits the z chain of the whole tile first and keeps every step's partials alive (200 VGPRs,
             // spills).  Pinning the tangent state (a chained, empty asm) before the scheduling barrier keeps
@@ -810,7 +823,7 @@ __device__ __forceinline__ void clipper_fused_body(
 #ifdef WDF_DBG_TIMES
         { const unsigned long long w0 = __builtin_amdgcn_s_memtime(); wait_vmcnt<NR>(); dbg_wait += __builtin_amdgcn_s_memtime() - w0; }
 #else
-        wait_vmcnt<NR * (STASH ? 2 : 1)>();
+        wait_vmcnt<STORE_Y ? NR * (STASH ? 2 : 1) : 0>();       // (no y: nothing is stored behind the next tile's loads)
 #endif
         // fp32 running sums go to the fp64 totals every kFlushSteps steps (a scalar branch per tile): flushed every tile of
         // 8 steps the 20 conversions + fp64 adds were 2 % of the kernel's VALU time
@@ -825,7 +838,8 @@ __device__ __forceinline__ void clipper_fused_body(
             continue;
         }
         const V tg = load_own<V>(target + tt * B, q);
-        store_own<V>(y + tt * B, q, fused_step<DYN_R, SYM, FAST, V, LOSS>(c, xin, rin, tg, tt >= skip ? hgs : 0.0f, z, s));
+        if constexpr (STORE_Y) store_own<V>(y + tt * B, q, fused_step<DYN_R, SYM, FAST, V, LOSS>(c, xin, rin, tg, tt >= skip ? hgs : 0.0f, z, s));
+        else (void)fused_step<DYN_R, SYM, FAST, V, LOSS>(c, xin, rin, tg, tt >= skip ? hgs : 0.0f, z, s);
     }
     d.template flush<LOSS>(s);
     publish_own<V>(zend + k * B, q, z);
@@ -1110,7 +1124,7 @@ __device__ __forceinline__ void fused_group_compose(const GroupStage<NSEQ, LOSS>
 // waves are done after their body (G = 1; clipper_fused_finish_kernel behind); 2: the group form (above; dynamic LDS:
 // G x sizeof(GroupStage); clipper_fused_group_finish_kernel behind).
 constexpr int kFusedInKernel = 0, kFusedFinishLater = 1, kFusedGroup = 2;
-template <int DYN_R, bool SYM, bool TM, bool VEC4, typename V, int LOSS>
+template <int DYN_R, bool SYM, bool TM, bool VEC4, typename V, int LOSS, bool STORE_Y = true>
 __global__ __launch_bounds__(64 * kGroupWaves) __attribute__((amdgpu_waves_per_eu(WDF_FUSED_WAVES, WDF_FUSED_WAVES))) void clipper_fused_tp_kernel(
     const float* __restrict__ x, const float* __restrict__ r, const float* theta, float fs, int n_up, int n_down,
     const float* __restrict__ target, float hgs, int64_t skip, float* __restrict__ y, const float* __restrict__ z0,
@@ -1144,17 +1158,17 @@ __global__ __launch_bounds__(64 * kGroupWaves) __attribute__((amdgpu_waves_per_e
         bool ran = false;
         if constexpr (SYM && DYN_R != 1) {
             if (tier == kRootLean) {
-                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootLean, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
+                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootLean, V, LOSS, false, STORE_Y>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
                                                                              J, B, T, L, W, hgs, skip, k, K, skew, wpart, gs);
                 ran = true;
             }
         }
         if (!ran) {
             if (tier != kRootGeneral)
-                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootFast, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
+                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootFast, V, LOSS, false, STORE_Y>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl, snap,
                                                                              J, B, T, L, W, hgs, skip, k, K, skew, wpart, gs);
             else
-                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootGeneral, V, LOSS>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl,
+                clipper_fused_body<DYN_R, SYM, TM, VEC4, kRootGeneral, V, LOSS, false, STORE_Y>(c, x, r, target, y, nullptr, z0, zT, zwarm, zend, rec, theta, ctl,
                                                                                 snap, J, B, T, L, W, hgs, skip, k, K, skew, wpart, gs);
         }
 #ifdef WDF_DBG_TIMES
@@ -1247,7 +1261,7 @@ __global__ __launch_bounds__(64) void clipper_fwd_tp_kernel(
 }
 
 // Re-run of chunk [t0, t1) for 64 sequences (one per lane, index b) from the exact state z: outputs, snapshots, record.
-template <int DYN_R, bool SYM, bool TM, int FAST, int LOSS, int NSEQ>
+template <int DYN_R, bool SYM, bool TM, int FAST, int LOSS, int NSEQ, bool STORE_Y = true>
 __device__ __forceinline__ void fused_rerun_chunk(const ClipConsts& c_in, const float* __restrict__ x, const float* __restrict__ r,
                                                   const float* __restrict__ target, float* __restrict__ y, float* rec, double* wpart,
                                                   float* __restrict__ snapw, int J, int64_t K, int64_t k, int64_t b, int64_t B,
@@ -1275,8 +1289,12 @@ __device__ __forceinline__ void fused_rerun_chunk(const ClipConsts& c_in, const 
         }
 #pragma unroll
         for (int i = 0; i < kBlk; ++i) {
-            if (t + i < t1)                                      // wave-uniform
-                y[(t + i) * B + b] = fused_step<DYN_R, SYM, FAST, float, LOSS>(c, xv[i], rv[i], gv[i], (t + i >= skip) ? hgs : 0.0f, z, s);
+            if (t + i < t1) {                                    // wave-uniform
+                if constexpr (STORE_Y)
+                    y[(t + i) * B + b] = fused_step<DYN_R, SYM, FAST, float, LOSS>(c, xv[i], rv[i], gv[i], (t + i >= skip) ? hgs : 0.0f, z, s);
+                else
+                    (void)fused_step<DYN_R, SYM, FAST, float, LOSS>(c, xv[i], rv[i], gv[i], (t + i >= skip) ? hgs : 0.0f, z, s);
+            }
         }
     }
     d.template flush<LOSS>(s);
@@ -1376,7 +1394,7 @@ __global__ __launch_bounds__(64) void clipper_fused_repair_kernel(
 // The rare path of a finish launch: one wave re-runs, in time order, every chunk of its tile that was entered more than tol off
 // (clipper_fused_repair_kernel's walk: from the exact state, one sequence per lane -- outputs, snapshots, records, sums), behind
 // the kernel boundary: the re-run rewrites rows that waves on another XCD wrote.
-template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS>
+template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS, bool STORE_Y = true>
 __device__ __forceinline__ void fused_repair_tile(
     const float* __restrict__ x, const float* __restrict__ r, const float* theta, float fs, int n_up, int n_down,
     const float* __restrict__ target, float hgs, int64_t skip, float* __restrict__ y, float* __restrict__ zT, const float* zwarm,
@@ -1407,13 +1425,13 @@ __device__ __forceinline__ void fused_repair_tile(
             bool ran = false;
             if constexpr (SYM && DYN_R != 1) {
                 if (tier == kRootLean) {
-                    fused_rerun_chunk<DYN_R, SYM, TM, kRootLean, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
+                    fused_rerun_chunk<DYN_R, SYM, TM, kRootLean, LOSS, NSEQ, STORE_Y>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
                     ran = true;
                 }
             }
             if (!ran) {
-                if (tier != kRootGeneral) fused_rerun_chunk<DYN_R, SYM, TM, kRootFast, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
-                else fused_rerun_chunk<DYN_R, SYM, TM, kRootGeneral, LOSS, NSEQ>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
+                if (tier != kRootGeneral) fused_rerun_chunk<DYN_R, SYM, TM, kRootFast, LOSS, NSEQ, STORE_Y>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
+                else fused_rerun_chunk<DYN_R, SYM, TM, kRootGeneral, LOSS, NSEQ, STORE_Y>(c, x, r, target, y, rec, wpart, snapw, J, K, k, b, B, live, h, T, t0, t1, hgs, skip, z);
             }
             __hip_atomic_store(zend + k * B + b, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (zT && t1 == T) zT[b] = z;
@@ -1436,7 +1454,7 @@ constexpr int kFinSeg = 8;          // chunk records a finishing wave holds in r
 constexpr int kFinMinSeg = 4;       // the host starts another wave per tile for every 4 chunks, up to kFinMaxWaves
 constexpr int kFinMaxWaves = 8;     // waves per tile (512 threads: the repair path needs up to 161 VGPRs)
 
-template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS>
+template <int DYN_R, bool SYM, bool TM, int NSEQ, int LOSS, bool STORE_Y = true>
 __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel(
     const float* __restrict__ x, const float* __restrict__ r, const float* theta, float fs, int n_up, int n_down,
     const float* __restrict__ target, float hgs, int64_t skip, float* __restrict__ y, float* __restrict__ zT,
@@ -1566,8 +1584,8 @@ __global__ __launch_bounds__(64 * kFinMaxWaves) void clipper_fused_finish_kernel
     if (tile_bad_pairs != 0) {
         // ---- the rare path: wave 0 re-runs the chunks that were entered off (clipper_fused_repair_kernel's walk)
         if (w == 0) {
-            fused_repair_tile<DYN_R, SYM, TM, NSEQ, LOSS>(x, r, theta, fs, n_up, n_down, target, hgs, skip, y, zT, zwarm, zend, rec, B, T, K, L, tol,
-                                                          status, ctl, snap, J, general, skew, wpart, b_first, live, lane);
+            fused_repair_tile<DYN_R, SYM, TM, NSEQ, LOSS, STORE_Y>(x, r, theta, fs, n_up, n_down, target, hgs, skip, y, zT, zwarm, zend, rec, B, T, K,
+                                                                   L, tol, status, ctl, snap, J, general, skew, wpart, b_first, live, lane);
         }
         __syncthreads();
         load_batch(k0);                                        // (agent-scope loads: past this CU's L1)

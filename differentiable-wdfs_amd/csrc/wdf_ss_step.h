@@ -355,6 +355,8 @@ __device__ __forceinline__ void lin_walk_to(const SSCoef<NS, NI>& c, const float
 //   [2 kG] = {GP, GQ} before the Jacobian.
 // The streamed pointers stay plain __restrict__ parameters (the prefetch needs its loads to move past the non-temporal y
 // stores); only what the tail touches travels in the loss's struct.
+// STORE_Y = false (the _noy exports: a training loop reads the loss and the gradient, not y): the one store of y is compiled
+// out, no address is formed from y and the host passes NULL -- 12 B/sample instead of 16.  Pass 1 never touches y.
 #ifndef WDF_LIN_BLK
 #define WDF_LIN_BLK 8
 #endif
@@ -376,7 +378,7 @@ __device__ __forceinline__ void lin_load_blk(const float* __restrict__ x, const 
     for (int i = 0; i < kLinBlk2; ++i) tn[i] = (i < n) ? lin_ld<V>(target + (ts + i) * B + b) : vsplat<V>(0.0f);
 }
 
-template <int NS, int NI, typename V, int LOSS>
+template <int NS, int NI, typename V, int LOSS, bool STORE_Y = true>
 __global__ __launch_bounds__(64) void ss_lin_step_kernel(const float* __restrict__ x, const float* __restrict__ coef,
                                                          const float* __restrict__ uend0, const float* __restrict__ target,
                                                          float* __restrict__ y, double* __restrict__ part,
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(64) void ss_lin_step_kernel(const float* __restrict
 #pragma unroll
                 for (int s = 0; s < NS; ++s) yv = vfma(c.v[C::oCy + s], u.z[s], yv);
                 const V e = yv - tg[i];
-                if (live) lin_st_nt<V>(y + (ts + i) * B + b, yv);
+                if constexpr (STORE_Y) { if (live) lin_st_nt<V>(y + (ts + i) * B + b, yv); }
                 V w[NF];                                          // the families' weights on this row's tangents
                 if constexpr (LOSS == 0) {
                     w[0] = e * gs;

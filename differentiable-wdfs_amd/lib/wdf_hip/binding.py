@@ -23,6 +23,7 @@ WDF_GENERAL_ROOT = 1 << 3
 WDF_MLP_LANE_PER_SEQUENCE = 1 << 4
 WDF_ONE_SEQUENCE_PER_LANE = 1 << 5
 WDF_R_PER_SEQUENCE = 1 << 6
+WDF_NO_Y_STORE = 1 << 7
 
 # Set True to run the one-lane-per-sequence MLP kernels (csrc/wdf_mlp.h) instead of the default
 # 16-lane row per sequence (csrc/wdf_mlp_row.h): parity tests and A/B timing.
@@ -201,6 +202,9 @@ SIGNATURES = {
 for _twin in ("wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp", "wdf_clipper_asym_bwd_tp", "wdf_clipper_asym_step_mse",
               "wdf_clipper_asym_step_esr"):
     SIGNATURES[_twin + "_rseq"] = (_ci, SIGNATURES[_twin][1][:1] + [_p] + SIGNATURES[_twin][1][1:])
+# the linear one-pass steps without y: their bases' argument lists less the y pointer (argument 8 of the MSE step, 10 of MSE + ESR)
+for _twin, _at in (("wdf_ss_lin_step_mse", 8), ("wdf_ss_lin_step_esr", 10)):
+    SIGNATURES[_twin + "_noy"] = (_ci, SIGNATURES[_twin][1][:_at] + SIGNATURES[_twin][1][_at + 1:])
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
@@ -272,9 +276,18 @@ def _out(t, n, name, holds, like):
     raise WdfHipError(f"{name} must hold {holds} ({n} floats)")
 
 
-def _y_zT(y, want_zT, T, B, like, ns=None):
-    """y [T,B], and zT ([B]; [ns,B] for a tree) where the final state is wanted."""
-    if y is None:
+def _no_y(who, y, store_y):
+    """store_y=False (the training-only steps: y is never stored) with a y handed in: refused before anything else is looked
+    at -- the buffer would silently stay unwritten."""
+    if not store_y and y is not None:
+        raise WdfHipError(f"{who}: y= was given together with store_y=False: the step would leave it unwritten")
+
+
+def _y_zT(y, want_zT, T, B, like, ns=None, store_y=True):
+    """y [T,B] (None with store_y=False: none is allocated), and zT ([B]; [ns,B] for a tree) where the final state is wanted."""
+    if not store_y:
+        y = None
+    elif y is None:
         y = torch.empty((T, B), dtype=torch.float32, device=like.device)
     elif tuple(_f32_dev(y, "y").shape) != (T, B):
         raise WdfHipError(f"y must be [T,B] = [{T},{B}]")
@@ -324,9 +337,9 @@ def _clipper_flags(time_major, fp64=False):
     return (WDF_X_TIME_MAJOR if time_major else 0) | _root_flag() | (WDF_PREC_F64 if fp64 else 0)
 
 
-def _clipper_step_flags(r, time_major):
+def _clipper_step_flags(r, time_major, store_y=True):
     return (_clipper_flags(time_major) | (WDF_ONE_SEQUENCE_PER_LANE if ONE_SEQUENCE_PER_LANE else 0) |
-            (WDF_R_PER_SEQUENCE if r_is_per_sequence(r, time_major) else 0))
+            (WDF_R_PER_SEQUENCE if r_is_per_sequence(r, time_major) else 0) | (0 if store_y else WDF_NO_Y_STORE))
 
 
 def _esr_finish(export, sums, sname, n, lead, n_global, eps, g, gname, loss3):
@@ -540,9 +553,11 @@ def step_mse_workspace(B, n_chunks, device):
     return ws
 
 
-def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish=True):
+def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish=True,
+                       store_y=True):
     """The checks and buffers the two one-pass clipper steps share
     -> x, r, theta, target, z0, B, T, K, y, zT, ws, status, (state buffer, max_warm_tiles), Adam tail, flags."""
+    _no_y(who, y, store_y)
     require_gpu()
     x, r, theta = _f32_dev(x, "x"), _f32_dev(r, "r"), _f32_dev(theta, "theta")
     target, z0 = _f32_dev(target, "target"), _f32_dev(z0, "z0")
@@ -556,7 +571,7 @@ def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, s
     if z0 is not None and z0.numel() != B:
         raise WdfHipError(f"z0 must hold one state per sequence ({B})")
     K = lib().wdf_clipper_tp_chunks(T, int(n_chunks))
-    y, zT = _y_zT(y, want_zT, T, B, x)
+    y, zT = _y_zT(y, want_zT, T, B, x, store_y=store_y)
     ws = step_mse_workspace(B, K, x.device) if ws is None else _ws(ws, lib().wdf_clipper_step_mse_tp_ws_bytes(B, K), x)
     if state is not None and ((state.B, state.T, state.K) != (B, T, K) or state.buf.device != x.device):
         raise WdfHipError("warm-start state was made for another batch shape / chunking / device")
@@ -564,19 +579,21 @@ def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, s
     if status is None:
         status = torch.empty((4,), dtype=torch.int32, device=x.device)
     return (x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm,
-            _adam_tail(opt, 4, who, "{Is, nVt, R, C}", finish), _clipper_step_flags(r, time_major))
+            _adam_tail(opt, 4, who, "{Is, nVt, R, C}", finish), _clipper_step_flags(r, time_major, store_y))
 
 
 def clipper_step_mse_tp(x, theta, fs, target, gscale, n_chunks, warmup, tol=1e-6, r=None, n_up=1, n_down=1, skip=0, y=None,
                         z0=None, want_zT=False, ws=None, status=None, state=None, gtheta=None, sse=None, accumulate=False,
-                        opt=None, time_major=False):
+                        opt=None, time_major=False, store_y=True):
     """The whole MSE training step in one pass over the data (include/wdf_hip.h, wdf_clipper_step_mse_tp):
     forward, loss and d(gscale/2 sum (y - target)^2)/d{Is, nVt, R, C}, x and target read once, y written once, no
     state stash.  n_chunks: time chunks asked for (rounded like wdf_clipper_tp_chunks does); state: a TpWarmState
     made for (B, T, n_chunks); opt: a binding.Adam(4, ...) to update theta in the same launch.
-    -> y [T,B], zT [B] | None, gtheta[4], sse[1], status (device int32[4], read with tp_status())."""
+    store_y=False: the training-only step (WDF_NO_Y_STORE) -- y is never stored or allocated, None comes back in its place, a
+    y= handed in is refused; everything else is the same call.
+    -> y [T,B] | None, zT [B] | None, gtheta[4], sse[1], status (device int32[4], read with tp_status())."""
     x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm, adam, flags = _clipper_step_args(
-        "clipper_step_mse_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major)
+        "clipper_step_mse_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, store_y=store_y)
     if gtheta is None:
         accumulate = False
     gtheta = _out(gtheta, 4, "gtheta", "four gradients", x)
@@ -591,13 +608,14 @@ def clipper_step_mse_tp(x, theta, fs, target, gscale, n_chunks, warmup, tol=1e-6
 
 def clipper_step_esr_tp(x, theta, fs, target, n_global, eps_energy, skip, n_chunks, warmup, tol=1e-6, r=None, n_up=1, n_down=1,
                         y=None, z0=None, want_zT=False, ws=None, status=None, state=None, sums10=None, gtheta=None, loss3=None,
-                        finish=True, opt=None, time_major=False):
+                        finish=True, opt=None, time_major=False, store_y=True):
     """The one-pass training step for the scripts' loss MSE + ESR past `skip` (include/wdf_hip.h, wdf_clipper_step_esr_tp).
     finish=True: the kernel finishes the step as a single rank -> gtheta[4], loss3 = {mse, esr, mse + esr} (and the Adam
     update of theta with `opt`).  finish=False: only sums10 = {S, E, gP[4], gQ[4]} of this batch comes back -- all-reduce it
-    and call esr_finish.  -> y [T,B], zT | None, sums10, gtheta | None, loss3 | None, status."""
+    and call esr_finish.  store_y=False: as clipper_step_mse_tp's (no y stored or allocated, None in its place).
+    -> y [T,B] | None, zT | None, sums10, gtheta | None, loss3 | None, status."""
     x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm, adam, flags = _clipper_step_args(
-        "clipper_step_esr_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish)
+        "clipper_step_esr_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish, store_y)
     sums10 = _out(sums10, 10, "sums10", "{S, E, gP[4], gQ[4]}", x)
     gtheta, loss3 = _esr_outs(finish, gtheta, 4, "gtheta", loss3, x)
     rc = lib().wdf_clipper_step_esr_tp(
@@ -1512,6 +1530,14 @@ def ss_asym_step_esr(x, coef, rootp, ns, ni, target, n_global, eps_energy, skip,
     return y, zT, sums, g, loss3, status
 
 
+def _lin_step_call(name, store_y, lead, y, rest):
+    """wdf_<name>(lead..., y, rest...) or, without the y store, wdf_<name>_noy(lead..., rest...): the twins share every other argument."""
+    if store_y:
+        _check(getattr(lib(), name)(*lead, _ptr(y), *rest), name)
+    else:
+        _check(getattr(lib(), name + "_noy")(*lead, *rest), name + "_noy")
+
+
 def _lin_step_shape(x_tm, coef, what="ss_lin_step_mse"):
     """(ns, ni, B, T, ncoef) of a linear one-pass step from x_tm [T,ni,B] and coef ([ncoef], or the probe's [ncoef + 1] with the
     port resistance behind it): the ns in 0..2 whose wdf_ss_ncoef fits."""
@@ -1525,8 +1551,9 @@ def _lin_step_shape(x_tm, coef, what="ss_lin_step_mse"):
     raise WdfHipError(f"{what}: coef {tuple(coef.shape)} is no coefficient vector of ns in 0..2 states and ni = {ni} inputs")
 
 
-def _lin_step_args(what, ws_bytes, x_tm, coef, jac, target, n_chunks, z0, want_zT, ws, y):
+def _lin_step_args(what, ws_bytes, x_tm, coef, jac, target, n_chunks, z0, want_zT, ws, y, store_y=True):
     """The shape checks and buffers the two linear one-pass steps share -> x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT."""
+    _no_y(what, y, store_y)
     require_gpu()
     x_tm, coef, target, z0 = _f32_dev(x_tm, "x_tm"), _f32_dev(coef, "coef"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
     ns, ni, B, T, ncoef = _lin_step_shape(x_tm, coef, what)
@@ -1538,28 +1565,29 @@ def _lin_step_args(what, ws_bytes, x_tm, coef, jac, target, n_chunks, z0, want_z
         raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
     if ns > 0 and z0 is not None and tuple(z0.shape) != (ns, B):
         raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
-    y, zT = _y_zT(y, want_zT and ns > 0, T, B, x_tm, ns)
+    y, zT = _y_zT(y, want_zT and ns > 0, T, B, x_tm, ns, store_y)
     need = ws_bytes(ns, ni, B, T, int(n_chunks))
     if need == 0:
         raise WdfHipError(f"{what}: no step for ns={ns}, ni={ni}, B={B}, T={T}, n_chunks={n_chunks}")
     return x_tm, coef, target, z0, ns, ni, B, T, n_params, y, _ws(ws, need, x_tm, zeroed=True), zT
 
 
-def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=False, want_gcoef=False, ws=None, y=None):
+def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=False, want_gcoef=False, ws=None, y=None,
+                    store_y=True):
     """The MSE training step of a LINEAR tree in one pass (wdf_ss_lin_step_mse, csrc/wdf_ss_step.h): forward, the sum of squared
     errors, d(gscale/2 x that sum)/d{A, Bx, cy, dy} carried forward in time and its contraction with jac.  x_tm [T,ni,B] time-major,
     coef in SSCoef order (ns from its length), jac float64 [ncoef (+1), n_params] (ss_probe's), target [T,B]; z0 [ns,B] or None.
     ws: zeroed wdf_ss_lin_step_ws_bytes() bytes when not given (the step leaves it clean); y, ws and z0 are used as they are --
-    the library pairs sequences up by their addresses.
-    -> dict: y [T,B], out [1 + n_params] = {SSE, gradients}, loss (0-dim), gcoef [ns^2 + ns ni + ns + ni] | None, zT [ns,B] | None, ws."""
+    the library pairs sequences up by their addresses.  store_y=False: wdf_ss_lin_step_mse_noy -- y is never stored or allocated
+    (None in the dict), a y= handed in is refused; the same workspace serves both.
+    -> dict: y [T,B] | None, out [1 + n_params] = {SSE, gradients}, loss (0-dim), gcoef [ns^2 + ns ni + ns + ni] | None, zT [ns,B] | None, ws."""
     x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_mse", lib().wdf_ss_lin_step_ws_bytes, x_tm, coef,
-                                                                               jac, target, n_chunks, z0, want_zT, ws, y)
+                                                                               jac, target, n_chunks, z0, want_zT, ws, y, store_y)
     out = torch.empty((1 + n_params,), dtype=torch.float32, device=x_tm.device)
     loss = torch.empty((), dtype=torch.float32, device=x_tm.device)
     gcoef = torch.empty((ns * ns + ns * ni + ns + ni,), dtype=torch.float32, device=x_tm.device) if want_gcoef else None
-    _check(lib().wdf_ss_lin_step_mse(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), float(gscale), _ptr(y), _ptr(ws),
-                                     _ptr(out), _ptr(loss), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()),
-           "wdf_ss_lin_step_mse")
+    _lin_step_call("wdf_ss_lin_step_mse", store_y, (_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), float(gscale)), y,
+                   (_ptr(ws), _ptr(out), _ptr(loss), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()))
     return {"y": y, "out": out, "loss": loss, "gcoef": gcoef, "zT": zT, "ws": ws}
 
 
@@ -1567,16 +1595,17 @@ ESR_EPS = 2.220446049250313e-16      # what the scripts' esr_loss adds to the en
 
 
 def ss_lin_step_esr(x_tm, coef, jac, target, skip, n_chunks, n_global=None, eps=ESR_EPS, z0=None, want_zT=False, want_gcoef=False,
-                    ws=None, y=None, finish=True):
+                    ws=None, y=None, finish=True, store_y=True):
     """The MSE + ESR training step of a LINEAR tree in one pass (wdf_ss_lin_step_esr, csrc/wdf_ss_step.h): loss = S/n +
     sqrt(S / (E + eps) / n) on the rows t >= skip (0 <= skip < T), S = sum (y - target)^2, E = sum y^2, n = n_global (None: this
     call's own B (T - skip)).  Arguments, shape checks and buffers as ss_lin_step_mse; ws: zeroed wdf_ss_lin_step_esr_ws_bytes()
     bytes when not given.  finish=True: a single rank -- the kernel's last wave forms g = dloss/d params and loss3 itself;
     finish=False: one shard of several -- only sums comes back (g and loss3 None): add the shards' sums and call ss_lin_esr_finish().
-    -> dict: y [T,B], sums [2 + 2 n_params] = {S, E, gP, gQ}, g [n_params] | None, loss3 [3] = {mse, esr, mse + esr} | None,
+    store_y=False: wdf_ss_lin_step_esr_noy, as ss_lin_step_mse's.
+    -> dict: y [T,B] | None, sums [2 + 2 n_params] = {S, E, gP, gQ}, g [n_params] | None, loss3 [3] = {mse, esr, mse + esr} | None,
     gcoef [2 (ns^2 + ns ni + ns + ni)] = {GP, GQ} | None, zT [ns,B] | None, ws."""
     x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_esr", lib().wdf_ss_lin_step_esr_ws_bytes, x_tm,
-                                                                               coef, jac, target, n_chunks, z0, want_zT, ws, y)
+                                                                               coef, jac, target, n_chunks, z0, want_zT, ws, y, store_y)
     skip = int(skip)
     if not 0 <= skip < T:
         raise WdfHipError(f"ss_lin_step_esr: skip must be in [0, T) = [0, {T}), got {skip}")
@@ -1587,9 +1616,8 @@ def ss_lin_step_esr(x_tm, coef, jac, target, skip, n_chunks, n_global=None, eps=
     sums = torch.empty((2 + 2 * n_params,), dtype=torch.float32, device=dev)
     g, loss3 = _esr_outs(finish, None, n_params, "g", None, x_tm)
     gcoef = torch.empty((2 * (ns * ns + ns * ni + ns + ni),), dtype=torch.float32, device=dev) if want_gcoef else None
-    _check(lib().wdf_ss_lin_step_esr(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), n_global, float(eps), skip, _ptr(y),
-                                     _ptr(ws), _ptr(sums), _ptr(g), _ptr(loss3), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT),
-                                     _stream()), "wdf_ss_lin_step_esr")
+    _lin_step_call("wdf_ss_lin_step_esr", store_y, (_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), n_global, float(eps), skip),
+                   y, (_ptr(ws), _ptr(sums), _ptr(g), _ptr(loss3), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()))
     return {"y": y, "sums": sums, "g": g, "loss3": loss3, "gcoef": gcoef, "zT": zT, "ws": ws}
 
 

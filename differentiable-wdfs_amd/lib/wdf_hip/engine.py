@@ -463,14 +463,17 @@ class MseStep:
     for all 501 epochs, clipper_pot.py:245-248), giving fully coalesced loads."""
 
     def __init__(self, B, T, fs, tp, device, n_up=1, n_down=1, n_global=None, time_major=False, loss="mse",
-                 skip=0, sums_allreduce=None, warm=False, max_warm_tiles=16):
+                 skip=0, sums_allreduce=None, warm=False, max_warm_tiles=16, store_output=True):
         """loss: "mse" (mean over n_global samples) or "mse+esr", the training loss of
         clipper_pot.py:177 evaluated past `skip` samples (:232,248; n_global then counts the samples
         past skip over all ranks).  sums_allreduce: in-place SUM all-reduce for the two float64 loss
         sums when the batch is sharded (wdf_hip.dist.allreduce_sum_).
         warm: this stepper always sees the SAME resident x (a training set re-visited every epoch,
         clipper_pot.py:245-269): keep the forward's warm-start state between calls
-        (binding.TpWarmState; call reset_warm() if x changes)."""
+        (binding.TpWarmState; call reset_warm() if x changes).
+        store_output=False: a training-only stepper -- step_fused runs the one-pass step without the y store (8 B/sample
+        instead of 12) and allocates no y (self.y stays None), single-rank and with sums_allreduce; forward() / backward() /
+        step(), the two-kernel path that needs y and the stash, raise WdfHipError."""
         if loss not in ("mse", "mse+esr"):
             raise binding.WdfHipError(f"unknown loss {loss!r}")
         if loss == "mse" and skip:
@@ -478,6 +481,7 @@ class MseStep:
         self.B, self.T, self.fs, self.tp = B, T, float(fs), tp
         self.n_up, self.n_down, self.time_major = n_up, n_down, bool(time_major)
         self.loss_kind, self.skip, self.sums_allreduce = loss, int(skip), sums_allreduce
+        self.store_output = bool(store_output)
         self.n_global = float(n_global if n_global is not None else B * (T - self.skip))
         self.gscale = 2.0 / self.n_global
         if loss == "mse+esr":
@@ -504,7 +508,12 @@ class MseStep:
         if self.warm is not None:
             self.warm.reset()
 
+    def _needs_output(self, what):
+        if not self.store_output:
+            raise binding.WdfHipError(f"MseStep.{what}: made with store_output=False (no y, no stash): only step_fused runs")
+
     def forward(self, theta, x, r=None):
+        self._needs_output("forward")
         tp = self.tp
         if tp is not None and tp.k_fwd > 1:
             self.y, self.zs, self.zT, _ = binding.clipper_fwd_tp(
@@ -519,6 +528,7 @@ class MseStep:
     def backward(self, theta, x, target, r=None, adam=None):
         """adam: a binding.Adam(4, ...) to update theta in the sweep's own last kernel (single rank,
         MSE loss); otherwise the caller applies its optimizer to self.gtheta afterwards."""
+        self._needs_output("backward")
         kb = self.tp.k_bwd if self.tp is not None else 1
         if adam is not None and self.loss_kind == "mse":
             binding.clipper_bwd_mse_tp_adam(x, theta, self.fs, self.zs, self.zT, target, self.gscale, kb, adam, r=r,
@@ -542,6 +552,7 @@ class MseStep:
         return self.sse, self.gtheta
 
     def step(self, theta, x, target, r=None):
+        self._needs_output("step")
         self.forward(theta, x, r)
         return self.backward(theta, x, target, r)
 
@@ -550,25 +561,29 @@ class MseStep:
         read once and y written once -- no state stash, one root solve per sample, the gradient carried forward as the
         state's tangent.  Chunking / verification / warm start as forward(); fills self.y, self.sse, self.gtheta (for
         "mse+esr" also self.loss = {mse, esr, mse + esr}) and, with `adam` on a single rank, updates theta in the same launch.
+        (store_output=False: y is neither written nor allocated, self.y is None.)
         With sums_allreduce set (sharded batch, "mse+esr") the ten sums are all-reduced between the pass and its finish."""
         tp = self.tp
         k = tp.k_fwd if tp is not None else 1
         if self.ws_s is None or self.ws_s_k != k:
             self.ws_s, self.ws_s_k = binding.step_mse_workspace(self.B, binding.lib().wdf_clipper_tp_chunks(self.T, k), x.device), k
+            self.y = self.zs = self.zT = None
+        if self.store_output and self.y is None:                 # (made by the first call that wants it)
             self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=x.device)
-            self.zs = self.zT = None
+        y = self.y if self.store_output else None
         W, tol = (tp.warmup, tp.tol) if tp is not None else (0, 1.0e-6)
         if self.loss_kind == "mse":
             binding.clipper_step_mse_tp(x, theta, self.fs, target, self.gscale, k, W, tol=tol, r=r, n_up=self.n_up,
-                                        n_down=self.n_down, y=self.y, ws=self.ws_s, status=self.status, state=self.warm,
-                                        gtheta=self.gtheta, sse=self.sse, opt=adam, time_major=self.time_major)
+                                        n_down=self.n_down, y=y, ws=self.ws_s, status=self.status, state=self.warm,
+                                        gtheta=self.gtheta, sse=self.sse, opt=adam, time_major=self.time_major,
+                                        store_y=self.store_output)
             return self.sse, self.gtheta
         eps = float(torch.finfo(torch.float64).eps)
         local = self.sums_allreduce is None
         binding.clipper_step_esr_tp(x, theta, self.fs, target, self.n_global, eps, self.skip, k, W, tol=tol, r=r, n_up=self.n_up,
-                                    n_down=self.n_down, y=self.y, ws=self.ws_s, status=self.status, state=self.warm,
+                                    n_down=self.n_down, y=y, ws=self.ws_s, status=self.status, state=self.warm,
                                     sums10=self.sums10, gtheta=self.gtheta, loss3=self.loss, finish=local,
-                                    opt=adam if local else None, time_major=self.time_major)
+                                    opt=adam if local else None, time_major=self.time_major, store_y=self.store_output)
         if not local:
             self.sums_allreduce(self.sums10)
             binding.esr_finish(self.sums10, self.n_global, eps, gtheta=self.gtheta, loss3=self.loss)

@@ -460,10 +460,11 @@ class _LinResident:
             self._hc_key, self._hc_val, self.plans = hv, (vals[:-1], float(vals[-1])), {}
         return self._hc_val
 
-    def entry(self, x, target, loss="mse", skip=0):
+    def entry(self, x, target, loss="mse", skip=0, store_output=True):
         """The buffers of one training set: per (x, target) pair and -- for the diode-root step's MSE + ESR loss -- per
         (loss, skip), so that an MSE and an ESR loop over the same data each keep their own workspace (snapshots, warm-up
-        control, chunk count)."""
+        control, chunk count).  The output buffer ent["y"] is made by the first call that wants it (store_output; output()):
+        an entry only ever run without the y store holds none, and calls with and without it share the entry."""
         extra = None if loss == "mse" else (loss, int(skip))
         ent = self.cache.get((x, target), extra)
         if ent is None:
@@ -481,7 +482,6 @@ class _LinResident:
                 per_wave = 64                                     # (the diode-root MSE + ESR step pairs them up on the smallest tree only;
                 #                                                    the linear one pairs them up on every tree, as its MSE step does)
             L_ = binding.lib()
-            y = torch.empty((T, B), dtype=torch.float32, device=dev)
             if circ.root_kind == "DiodePair":
                 # the tangent-carried step of a diode-pair root: chunks no shorter than 64 steps, one wave per SIMD and up
                 k = max(1, min(T // 64, (_NL_OCC * N_SIMD) // max(1, -(-B // per_wave))))
@@ -500,12 +500,23 @@ class _LinResident:
             # (a row of the diode-root MSE + ESR step: {S, gradients}, then {mse, esr, mse + esr}; of the linear one: {0, gradients},
             #  {mse, esr, mse + esr}, then this call's sums {S, E, gP[n], gQ[n]}: the C ABI hands S back with the sums)
             width = 2 if loss == "mse" else (4 if circ.root_kind == "DiodePair" else 6 + 2 * self.pb.n)
-            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": y, "ws": ws,
+            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": None, "ws": ws,
                                        "ring": torch.zeros((_ROWS, width + self.pb.n), dtype=torch.float32, device=dev),
                                        "turn": 0, "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0,
                                        "loss": loss, "skip": int(skip)},
-                                 extra, nbytes=_nbytes(x_tm, tgt, y, ws))
+                                 extra, nbytes=_nbytes(x_tm, tgt, tgt, ws))      # (y, where one is made, is the size of tgt)
+        # this call's choice; a diode-pair root has no step without the y store and always stores
+        ent["store_y"] = bool(store_output) or self.circ.root_kind == "DiodePair"
+        if ent["store_y"]:
+            self.output(ent)
         return ent
+
+    @staticmethod
+    def output(ent):
+        """The entry's output buffer y [T,B], made on first use."""
+        if ent["y"] is None:
+            ent["y"] = torch.empty((ent["T"], ent["B"]), dtype=torch.float32, device=ent["t"].device)
+        return ent["y"]
 
     def _plan_nl(self, B, T, k, dev, cold_floor=0):
         """Workspace of the diode-root step for k chunks, planned: cold first call, then the device steers the warm-up."""
@@ -612,30 +623,30 @@ class _LinResident:
             return out, loss
         zT = None
         if want_zT and circ.ns > 0:
-            bufs = ent.setdefault("zT_bufs", [torch.empty((circ.ns, B), dtype=torch.float32, device=ent["y"].device) for _ in range(2)])
+            bufs = ent.setdefault("zT_bufs", [torch.empty((circ.ns, B), dtype=torch.float32, device=ent["t"].device) for _ in range(2)])
             zT = bufs[0] if (z0 is None or z0.data_ptr() != bufs[0].data_ptr()) else bufs[1]
         ent["zT"] = zT
+        store_y = ent["store_y"]                                  # (False: the _noy twins -- no y argument, nothing stored)
+        ynoy = (binding._ptr(ent["y"]),) if store_y else ()
         if ent.get("loss", "mse") != "mse":
             # MSE + ESR past skip on a linear tree (wdf_ss_lin_step_esr): the gradients land in out[1:] and {mse, esr, mse + esr} in
             # the row behind them, then this call's sums {S, E, gP, gQ} (what a data-parallel loop would all-reduce): the C ABI
             # hands S back with the sums, not in front of g, so out[0] stays 0 and S is row[4 + n] -- per call like the rest of the
             # row, never written again.  (Addresses inside the row by arithmetic: every view is microseconds of host time.)
             at = row.data_ptr()
-            rc = binding.lib().wdf_ss_lin_step_esr(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), n, circ.ns,
-                                                   circ.ni, binding._ptr(ent["t"]), float(B * (T - ent["skip"])), ESR_EPS, int(ent["skip"]),
-                                                   binding._ptr(ent["y"]), binding._ptr(ent["ws"]), ctypes.c_void_p(at + 4 * (4 + n)),
-                                                   ctypes.c_void_p(at + 4), ctypes.c_void_p(at + 4 * (1 + n)), None, B, T, ent["k"],
-                                                   None if z0 is None else binding._ptr(z0), None if zT is None else binding._ptr(zT),
-                                                   binding._stream())
-            binding._check(rc, "wdf_ss_lin_step_esr")
+            step = binding.lib().wdf_ss_lin_step_esr if store_y else binding.lib().wdf_ss_lin_step_esr_noy
+            rc = step(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), n, circ.ns, circ.ni, binding._ptr(ent["t"]),
+                      float(B * (T - ent["skip"])), ESR_EPS, int(ent["skip"]), *ynoy, binding._ptr(ent["ws"]),
+                      ctypes.c_void_p(at + 4 * (4 + n)), ctypes.c_void_p(at + 4), ctypes.c_void_p(at + 4 * (1 + n)), None, B, T, ent["k"],
+                      None if z0 is None else binding._ptr(z0), None if zT is None else binding._ptr(zT), binding._stream())
+            binding._check(rc, "wdf_ss_lin_step_esr" if store_y else "wdf_ss_lin_step_esr_noy")
             ent["row"] = row                                      # ({0, g[n], mse, esr, mse + esr, S, E, gP[n], gQ[n]} of this call)
             return out, row[3 + n]
-        rc = binding.lib().wdf_ss_lin_step_mse(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), self.pb.n,
-                                               circ.ns, circ.ni, binding._ptr(ent["t"]), 2.0 / float(B * T), binding._ptr(ent["y"]),
-                                               binding._ptr(ent["ws"]), binding._ptr(out), binding._ptr(loss), None, B, T, ent["k"],
-                                               None if z0 is None else binding._ptr(z0), None if zT is None else binding._ptr(zT),
-                                               binding._stream())
-        binding._check(rc, "wdf_ss_lin_step_mse")
+        step = binding.lib().wdf_ss_lin_step_mse if store_y else binding.lib().wdf_ss_lin_step_mse_noy
+        rc = step(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), self.pb.n, circ.ns, circ.ni, binding._ptr(ent["t"]),
+                  2.0 / float(B * T), *ynoy, binding._ptr(ent["ws"]), binding._ptr(out), binding._ptr(loss), None, B, T, ent["k"],
+                  None if z0 is None else binding._ptr(z0), None if zT is None else binding._ptr(zT), binding._stream())
+        binding._check(rc, "wdf_ss_lin_step_mse" if store_y else "wdf_ss_lin_step_mse_noy")
         return out, loss
 
 
@@ -972,10 +983,11 @@ class Circuit:
             return h[2], h[3]
         return float(parts[2]), float(parts[3])
 
-    def _loss_resident(self, x, target, kind="mse", skip=0):
+    def _loss_resident(self, x, target, kind="mse", skip=0, store_output=True):
         """mse() / mse_esr() on a resident circuit: inputs prepared once per (x, target) pair -- a training set and a
         validation set alternate in clipper_pot.py:245-262, each keeps its own stepper and warm-start state -- then one pass
-        of the one-pass training step per call."""
+        of the one-pass training step per call.  store_output=False: the step without the y store; the pair's entry (stepper,
+        workspace, warm-start state) is the same either way, and its y buffer is made by the first call that wants it."""
         from . import engine
         pb = self._pblock
         pb.flush()                                               # (queued optimizer updates of the block go out first)
@@ -999,20 +1011,22 @@ class Circuit:
                                        time_major=True, R_min=None if r is None else engine.resistance_min(r), fused=True)
             T, B = xv.shape
             st = engine.MseStep(B, T, float(cap.FS), tp, pb.block.device, n_up=dp.N_up, n_down=dp.N_down, time_major=True,
-                                warm=True, loss=kind, skip=int(skip))
+                                warm=True, loss=kind, skip=int(skip), store_output=store_output)
             live = [(i, v) for i, v in sorted(pb.members.items()) if v.requires_grad]
             ent = self._res_cache.put((x, target), (st, xv, r, tgt, 1.0 / float(B * T) if kind == "mse" else 1.0,
                                                     [i for i, _ in live], [v for _, v in live], {id(v): i for i, v in live}),
                                       (kind, int(skip)), 3 * _nbytes(xv, r, tgt))
         st, xv, r, tgt, inv_n, idx, live = ent[:7]
+        st.store_output = bool(store_output)                     # (this call's choice: step_fused makes y on first use)
         engine.LAST_TP_STATUS["status"] = st.status
         loss, out = engine._ResidentMseFn.apply(st, pb.block, xv, r, tgt, inv_n, idx, *live)
         loss = loss.as_subclass(tf.Tensor)
         # d loss / d Variable is already known: tape.gradient(loss, ...) on THIS tensor reads it (compat_tf.GradientTape)
         loss._wdf_fused = (out, ent[7])
+        self.last_output = st.y if store_output else None        # (the stepper's own y [T,B], valid until the pair's next call)
         return loss
 
-    def mse_esr(self, x, target, skip=0, z0=None, carry_state=False):
+    def mse_esr(self, x, target, skip=0, z0=None, carry_state=False, store_output=True):
         """The training loss of clipper_pot.py:146-156,177 on this circuit's output past `skip` samples (:232,248):
         mean((y - t)^2) + sqrt(sum((y - t)^2) / (sum(y^2) + eps) / n)  -- the scripts call esr_loss(outs, train_Y) on a
         function declared (target, predicted), so the normalising energy is the OUTPUT's.  target: [T,B] like the output.
@@ -1025,7 +1039,14 @@ class Circuit:
         `circ.last_output` the batch's output buffer); anything else composes it from the forward.
         z0 / carry_state: as in mse() -- the state the call starts from, or the one the previous carry_state call ended in
         (`circ.last_state`); composed from __call__(x, z0, return_state) (the resident one-pass steps start from zero state,
-        which is what clipper_pot.py:110-111 does before every forward)."""
+        which is what clipper_pot.py:110-111 does before every forward).
+        store_output=False: as in mse() -- "I will not read y"; `circ.last_output` is None after the call."""
+        loss = self._mse_esr(x, target, skip, z0, carry_state, bool(store_output))
+        if not store_output:
+            self.last_output = None
+        return loss
+
+    def _mse_esr(self, x, target, skip, z0, carry_state, store_output):
         binding.require_gpu()
         stateful = (z0 is not None or carry_state) and self.ns > 0
         if self.root_kind == "AsymDiodePair" and not self._asym_generic and self.root.mode != binding.ASYM_OMEGA_F32 \
@@ -1041,7 +1062,7 @@ class Circuit:
                 and isinstance(target, torch.Tensor) and x.dim() >= 2 and 0 <= int(skip) < int(x.shape[1]):
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
-            return self._mse_esr_lin_step(x, target, int(skip), z0, stateful)      # the linear step takes z0 / zT itself
+            return self._mse_esr_lin_step(x, target, int(skip), z0, stateful, store_output)      # the linear step takes z0 / zT itself
         if stateful:
             if carry_state and z0 is None:
                 z0 = getattr(self, "last_state", None)
@@ -1065,7 +1086,7 @@ class Circuit:
                 return loss
         if (getattr(self, "_pblock", None) is not None and isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)
                 and not self.force_generic):
-            return self._loss_resident(x, target, "mse+esr", skip)
+            return self._loss_resident(x, target, "mse+esr", skip, store_output)
         # (a resident small tree under a DiodePair root has a one-pass step for this loss too -- _nl_step_tree /
         #  _mse_esr_nl_step, wdf_ss_nl_step_esr -- which this method does not take until tools/ss_nl_esr_step_bench.py has
         #  shown it faster than the composed path below at both of its shapes)
@@ -1126,7 +1147,7 @@ class Circuit:
         self.last_output = ent["y"]
         return loss
 
-    def _mse_esr_lin_step(self, x, target, skip=0, z0=None, stateful=False):
+    def _mse_esr_lin_step(self, x, target, skip=0, z0=None, stateful=False, store_output=True):
         """mse_esr(x, target, skip) of a resident LINEAR tree as ONE pass (wdf_ss_lin_step_esr) through the MSE step's autograd
         function, factor 1.0: the loss carries the gradient the pass produced (`_wdf_fused`), the queued optimizer updates ride in
         its probe launch, `last_output` is the step's y.  z0 [ns,B] / stateful: the step's own z0 / zT, as in mse(); `last_state`
@@ -1141,11 +1162,11 @@ class Circuit:
             stateful, z0 = False, None                            # (no capacitor: nothing to carry)
         with torch._C.DisableTorchFunctionSubclass():
             lin.check()
-            ent = lin.entry(x, target, "mse+esr", int(skip))
+            ent = lin.entry(x, target, "mse+esr", int(skip), store_output)
             live = [(i, v) for i, v in sorted(lin.pb.members.items()) if v.requires_grad]
             z0d = None
             if z0 is not None:
-                z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["y"].device).float().reshape(self.ns, ent["B"]).contiguous()
+                z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["t"].device).float().reshape(self.ns, ent["B"]).contiguous()
         loss, out = _LinResidentMseFn.apply(lin, ent, 1.0, [i for i, _ in live], z0d, bool(stateful), *[v for _, v in live])
         loss = loss.as_subclass(tf.Tensor)
         loss._wdf_fused = (out, {id(v): i for i, v in live})
@@ -1220,7 +1241,7 @@ class Circuit:
         return tree
 
     # -- topology tests
-    def mse(self, x, target, z0=None, carry_state=False):
+    def mse(self, x, target, z0=None, carry_state=False, store_output=True):
         """tf.reduce_mean(tf.square(self(x) - target)) as ONE fused evaluation where the kernels allow
         it (diode-pair clipper: forward kernel + MSE-fused reverse sweep, the gradient of every
         trainable component ready when tape.gradient asks; the clipper under an AsymDiodePair root with a Newton solver: the
@@ -1234,7 +1255,21 @@ class Circuit:
         (set whenever z0 / carry_state is used; a tensor of its own that later calls leave alone); `circ.reset_state()` forgets
         it.  A resident linear tree runs this inside the one-pass step (wdf_ss_lin_step_mse's z0 / zT); every other circuit
         composes it from __call__(x, z0, return_state).  `circ.last_output` [T,B] is the call's y; on a resident tree it is the
-        batch's own output buffer, valid until the next call on the same (x, target) -- clone it to keep it longer."""
+        batch's own output buffer, valid until the next call on the same (x, target) -- clone it to keep it longer.
+
+        store_output=False is a permission: "I will not read y" (a training loop reads the loss and the gradient,
+        clipper_pot.py:245-269).  A resident diode-pair clipper and a resident linear tree then run their one-pass step
+        without the y store (8 instead of 12, 12 instead of 16 B/sample); every other circuit computes exactly as with the
+        default.  In every case `circ.last_output` is None after such a call.  The resident cache keeps ONE entry per
+        (x, target) pair whichever way it is called -- one workspace, one warm-start state -- and allocates the pair's y buffer
+        lazily, on the first call that wants it: a training set only ever run without y holds no y buffer, and a later
+        storing call on the same pair gets its y."""
+        loss = self._mse(x, target, z0, carry_state, bool(store_output))
+        if not store_output:
+            self.last_output = None
+        return loss
+
+    def _mse(self, x, target, z0, carry_state, store_output):
         binding.require_gpu()
         stateful = z0 is not None or carry_state
         if carry_state and z0 is None:
@@ -1250,11 +1285,11 @@ class Circuit:
         if lin is not None and isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor):
             with torch._C.DisableTorchFunctionSubclass():        # (asking a tensor for its version or requires_grad must not
                 lin.check()                                      #  send the queued optimizer updates: the probe carries them)
-                ent = lin.entry(x, target)
+                ent = lin.entry(x, target, store_output=store_output)
                 live = [(i, v) for i, v in sorted(lin.pb.members.items()) if v.requires_grad]
                 z0d = None
                 if z0 is not None:                               # the linear step takes the state in and hands it out
-                    z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["y"].device).float().reshape(self.ns, ent["B"]).contiguous()
+                    z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["t"].device).float().reshape(self.ns, ent["B"]).contiguous()
             loss, out = _LinResidentMseFn.apply(lin, ent, 1.0 / float(ent["B"] * ent["T"]), [i for i, _ in live], z0d, stateful,
                                                 *[v for _, v in live])
             loss = loss.as_subclass(tf.Tensor)
@@ -1276,7 +1311,7 @@ class Circuit:
             return tf.reduce_mean(tf.square(y - target))
         from . import engine
         if getattr(self, "_pblock", None) is not None and isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor):
-            return self._loss_resident(x, target)
+            return self._loss_resident(x, target, store_output=store_output)
         anchor = x if isinstance(x, torch.Tensor) else None
         x = torch.as_tensor(x).as_subclass(torch.Tensor)
         x = (x if x.is_cuda else x.cuda()).float()

@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed).  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -61,9 +61,12 @@ enum {
                                   constant along every sequence (the reference's recordings: one pot value per file,
                                   dataimport.py:96) -- calc_impedance is then evaluated once per chunk from each sequence's
                                   first sample and the channel is not streamed; results as with the per-sample evaluation */
-    WDF_ONE_SEQUENCE_PER_LANE = 1 << 5 /* wdf_clipper_step_mse_tp: one sequence per lane even when the batch is even
+    WDF_ONE_SEQUENCE_PER_LANE = 1 << 5, /* wdf_clipper_step_mse_tp: one sequence per lane even when the batch is even
                                   (by default a lane then runs two adjacent sequences with packed fp32
                                   arithmetic); for parity tests and A/B timing */
+    WDF_NO_Y_STORE = 1 << 7    /* wdf_clipper_step_mse_tp / _esr_tp only: the training-only step, y is never stored (8 B/sample
+                                  instead of 12, no y buffer).  y must then be NULL (a buffer handed in would silently stay
+                                  unwritten: WDF_EINVAL); every other entry point refuses the bit */
 };
 
 /* ------------------------------------------------------------------------------------
@@ -195,7 +198,11 @@ int wdf_clipper_bwd_mse_tp_adam(const float* x, const float* r, float* theta, fl
  * dL/dy = gscale (y - target) on steps >= skip (gscale = 2/N, N the GLOBAL number of samples past skip);
  * *sse receives sum (y - target)^2 over those steps of this call's batch, gtheta[4] the gradient.
  * n_chunks must be a value wdf_clipper_tp_chunks returns.  ws: wdf_clipper_step_mse_tp_ws_bytes bytes,
- * initialised ONCE with wdf_clipper_step_mse_tp_ws_init (ticket words the kernels count in and leave at zero). */
+ * initialised ONCE with wdf_clipper_step_mse_tp_ws_init (ticket words the kernels count in and leave at zero).
+ * WDF_NO_Y_STORE (with y = NULL): the same step without the store of y -- a training loop reads the loss and the gradient
+ * (clipper_pot.py:245-269) -- x and target read once, nothing else streamed: 8 B/sample.  State, zT, status, warm-start
+ * steering, repairs, sums and Adam are what they are with y; every other argument and flag means the same.  Such a call
+ * always takes the default launch form (the finish launch behind the chunk kernel), whatever WDF_FUSED_FINISH names. */
 size_t wdf_clipper_step_mse_tp_ws_bytes(int64_t B, int n_chunks);
 int wdf_clipper_step_mse_tp_ws_init(void* ws, int64_t B, int n_chunks, void* stream);
 int wdf_clipper_step_mse_tp(const float* x, const float* r, float* theta, float fs, int n_up, int n_down,
@@ -211,7 +218,8 @@ int wdf_clipper_step_mse_tp(const float* x, const float* r, float* theta, float 
  * carries both tangent-weighted sums and hands back sums10 = {S, E, gP[4], gQ[4]} of this call's batch (gP = d(S/2)/dtheta,
  * gQ = d(E/2)/dtheta): with several ranks all-reduce the ten floats and call wdf_esr_finish (-> gtheta = ga gP + gb gQ and
  * loss3 = {mse, esr, mse + esr}), then wdf_adam_step.  With gtheta != NULL the kernel finishes the step itself as a single
- * rank (same formulas; loss3 optional; Adam when m != NULL).  Workspace and state as wdf_clipper_step_mse_tp (same sizes). */
+ * rank (same formulas; loss3 optional; Adam when m != NULL).  Workspace and state as wdf_clipper_step_mse_tp (same sizes).
+ * WDF_NO_Y_STORE with y = NULL as there: E = sum y^2 is formed from y in registers, so the loss needs no stored y either. */
 int wdf_clipper_step_esr_tp(const float* x, const float* r, float* theta, float fs, int n_up, int n_down,
                             const float* target, double n_global, double eps_energy, int64_t skip, float* y, const float* z0,
                             float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol, void* ws, void* status,
@@ -380,6 +388,18 @@ int wdf_ss_lin_step_esr(const float* x, const float* coef, const double* jac, in
                         const float* target, double n_global, double eps_energy, int64_t skip, float* y, void* ws,
                         float* sums, float* g, float* loss3, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
                         const float* z0, float* zT, void* stream);
+/* The two steps without y (additions to ABI 6): the signatures of their bases less the y parameter, the same checks, workspace
+ * (wdf_ss_lin_step_ws_bytes / _esr_ws_bytes; one workspace may serve a storing and a no-y call in turn) and results; the output
+ * is formed in registers for the loss and never stored: 12 B/sample instead of 16, no y buffer.  wdf_ss_lin_esr_finish serves
+ * both. */
+int wdf_ss_lin_step_mse_noy(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni,
+                            const float* target, float gscale, void* ws, float* out, float* loss_out,
+                            float* gcoef_out, int64_t B, int64_t T, int n_chunks, const float* z0, float* zT,
+                            void* stream);
+int wdf_ss_lin_step_esr_noy(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni,
+                            const float* target, double n_global, double eps_energy, int64_t skip, void* ws,
+                            float* sums, float* g, float* loss3, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
+                            const float* z0, float* zT, void* stream);
 int wdf_ss_lin_esr_finish(const float* sums, int n_params, double n_global, double eps_energy, float* g, float* loss3,
                           void* stream);
 
