@@ -48,12 +48,7 @@ int check_common(const float* x, const float* theta, int n_up, int n_down, int64
 
 // ---- time-parallel clipper (chunk lengths and warm-ups: multiples of wdf::kTile steps) ------------
 
-// state: nullptr (stateless, cold every call) or the caller's persistent warm-start buffer
-// [TpCtl][tile tickets + accumulators][snapshot ring kTpRing x J x K x B floats]
-struct TpWarm { wdf::TpCtl* ctl; float* snap; int J; };
-
-// per-tile tickets, 4 accumulator words, per-tile repair flags
-inline size_t tp_ticket_bytes(int64_t B) { return round_up((2 * waves64(B) + 4) * sizeof(unsigned), 64); }
+// (TpWarm, tp_ticket_bytes, tp_state: wdf_capi_clipper_step.h -- the evaluation pass takes the same warm-start state)
 
 // the forward's workspace: zwarm [K][B], zend [K][B], then (stateless calls) the tile tickets
 struct TpFwdWs { float* zwarm; float* zend; unsigned* tickets; size_t bytes; };
@@ -64,19 +59,6 @@ inline TpFwdWs tp_fwd_ws(void* ws, int64_t B, int K)
     w.zwarm = c.take<float>((size_t)K * (size_t)B);
     w.zend = c.take<float>((size_t)K * (size_t)B);
     w.tickets = c.take<unsigned>(tp_ticket_bytes(B) / sizeof(unsigned));
-    w.bytes = c.off;
-    return w;
-}
-
-// the caller's persistent warm-start state: [TpCtl][tile tickets + accumulators][snapshot ring]
-struct TpState { wdf::TpCtl* ctl; unsigned* tickets; float* snap; size_t bytes; };
-inline TpState tp_state(void* state, int64_t B, size_t ring_floats)
-{
-    Carver c(state);
-    TpState w;
-    w.ctl = c.take<wdf::TpCtl>(1);
-    w.tickets = c.take<unsigned>(tp_ticket_bytes(B) / sizeof(unsigned));
-    w.snap = c.take<float>(ring_floats);
     w.bytes = c.off;
     return w;
 }

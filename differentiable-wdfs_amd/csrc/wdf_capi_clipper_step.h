@@ -1,7 +1,7 @@
-// wdf_capi_clipper_step.h -- what wdf_capi_clipper.hip and wdf_capi_clipper_noy.hip share: the dispatcher of the clipper kernels'
-// four leading template parameters, and the hand-over of a checked one-pass step to the translation unit that holds the
-// instantiations WITHOUT the y store (a unit of its own: the storing step's unit is the longest compile of the library, and the
-// two compile side by side).
+// wdf_capi_clipper_step.h -- what wdf_capi_clipper.hip, wdf_capi_clipper_noy.hip and wdf_capi_clipper_eval.hip share: the dispatcher
+// of the clipper kernels' four leading template parameters, the layout of the caller's warm-start state, and the hand-over of a
+// checked one-pass step to the translation unit that holds the instantiations WITHOUT the y store (a unit of its own: the storing
+// step's unit is the longest compile of the library, and the two compile side by side).
 #pragma once
 #include "wdf_capi_common.h"
 #include "wdf_clipper_fused.h"
@@ -16,6 +16,26 @@ template <class Dyn, class F> bool dispatch4(F&& f, Dyn dyn, bool sym, bool tm, 
         if constexpr (TM() && V4()) return false;
         else return dispatch([&] { return f(DYN, SYM, TM, V4); });
     }, dyn, Bools{sym}, Bools{tm}, Bools{v4});
+}
+
+// state: nullptr (stateless, cold every call) or the caller's persistent warm-start buffer
+// [TpCtl][tile tickets + accumulators][snapshot ring kTpRing x J x K x B floats]
+struct TpWarm { wdf::TpCtl* ctl; float* snap; int J; };
+
+// per-tile tickets, 4 accumulator words, per-tile repair flags
+inline size_t tp_ticket_bytes(int64_t B) { return round_up((2 * waves64(B) + 4) * sizeof(unsigned), 64); }
+
+// the caller's persistent warm-start state: [TpCtl][tile tickets + accumulators][snapshot ring]
+struct TpState { wdf::TpCtl* ctl; unsigned* tickets; float* snap; size_t bytes; };
+inline TpState tp_state(void* state, int64_t B, size_t ring_floats)
+{
+    Carver c(state);
+    TpState w;
+    w.ctl = c.take<wdf::TpCtl>(1);
+    w.tickets = c.take<unsigned>(tp_ticket_bytes(B) / sizeof(unsigned));
+    w.snap = c.take<float>(ring_floats);
+    w.bytes = c.off;
+    return w;
 }
 
 // A one-pass step without y, arguments checked and workspace carved (step_tp_common): everything launch_fused takes but y.

@@ -205,6 +205,10 @@ for _twin in ("wdf_clipper_asym_fwd", "wdf_clipper_asym_fwd_tp", "wdf_clipper_as
 # the linear one-pass steps without y: their bases' argument lists less the y pointer (argument 8 of the MSE step, 10 of MSE + ESR)
 for _twin, _at in (("wdf_ss_lin_step_mse", 8), ("wdf_ss_lin_step_esr", 10)):
     SIGNATURES[_twin + "_noy"] = (_ci, SIGNATURES[_twin][1][:_at] + SIGNATURES[_twin][1][_at + 1:])
+# the clipper's loss-only evaluation pass: the MSE + ESR step's arguments up to max_warm_tiles (theta const), then sums, loss3, flags, stream
+SIGNATURES["wdf_clipper_eval_tp_ws_bytes"] = SIGNATURES["wdf_clipper_step_mse_tp_ws_bytes"]
+SIGNATURES["wdf_clipper_eval_tp_ws_init"] = SIGNATURES["wdf_clipper_step_mse_tp_ws_init"]
+SIGNATURES["wdf_clipper_eval_tp"] = (_ci, SIGNATURES["wdf_clipper_step_esr_tp"][1][:22] + [_p, _p, _ci, _p])
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
@@ -553,9 +557,17 @@ def step_mse_workspace(B, n_chunks, device):
     return ws
 
 
+def eval_workspace(B, n_chunks, device):
+    """Workspace of the loss-only evaluation pass (clipper_eval_tp) with its ticket words cleared: allocate once, reuse."""
+    ws = torch.empty((lib().wdf_clipper_eval_tp_ws_bytes(int(B), int(n_chunks)),), dtype=torch.uint8, device=device)
+    _check(lib().wdf_clipper_eval_tp_ws_init(_ptr(ws), int(B), int(n_chunks), _stream()), "wdf_clipper_eval_tp_ws_init")
+    return ws
+
+
 def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, opt, time_major, finish=True,
-                       store_y=True):
-    """The checks and buffers the two one-pass clipper steps share
+                       store_y=True, workspace=(step_mse_workspace, "wdf_clipper_step_mse_tp_ws_bytes")):
+    """The checks and buffers the two one-pass clipper steps and the evaluation pass share (workspace: who makes one, and the
+    export that sizes it)
     -> x, r, theta, target, z0, B, T, K, y, zT, ws, status, (state buffer, max_warm_tiles), Adam tail, flags."""
     _no_y(who, y, store_y)
     require_gpu()
@@ -572,7 +584,7 @@ def _clipper_step_args(who, x, r, theta, target, n_chunks, y, z0, want_zT, ws, s
         raise WdfHipError(f"z0 must hold one state per sequence ({B})")
     K = lib().wdf_clipper_tp_chunks(T, int(n_chunks))
     y, zT = _y_zT(y, want_zT, T, B, x, store_y=store_y)
-    ws = step_mse_workspace(B, K, x.device) if ws is None else _ws(ws, lib().wdf_clipper_step_mse_tp_ws_bytes(B, K), x)
+    ws = workspace[0](B, K, x.device) if ws is None else _ws(ws, getattr(lib(), workspace[1])(B, K), x)
     if state is not None and ((state.B, state.T, state.K) != (B, T, K) or state.buf.device != x.device):
         raise WdfHipError("warm-start state was made for another batch shape / chunking / device")
     warm = (None, 0) if state is None else (_ptr(state.buf), state.max_warm_tiles)
@@ -624,6 +636,30 @@ def clipper_step_esr_tp(x, theta, fs, target, n_global, eps_energy, skip, n_chun
         _ptr(gtheta), _ptr(loss3), *adam, flags, _stream())
     _check(rc, "wdf_clipper_step_esr_tp")
     return y, zT, sums10, gtheta, loss3, status
+
+
+def clipper_eval_tp(x, theta, fs, target, n_global, eps_energy, skip, n_chunks, warmup, tol=1e-6, r=None, n_up=1, n_down=1, y=None,
+                    store_y=True, z0=None, want_zT=False, ws=None, status=None, state=None, sums=None, loss3=None, time_major=False):
+    """The loss-only evaluation pass (include/wdf_hip.h, wdf_clipper_eval_tp): forward and the loss sums S = sum (y - target)^2,
+    E = sum y^2 past `skip` in one pass -- no tangent, no gradient, theta untouched.  Arguments as clipper_step_esr_tp's;
+    store_y=False: y is never stored or allocated (8 B/sample), None comes back in its place, a y= handed in is refused.
+    sums: float64[2] on the device (what several ranks all-reduce before esr_coef); loss3 = {S/n, sqrt(S/(E + eps)/n), their sum}
+    with n = n_global.  ws: eval_workspace(B, K, device).
+    -> y [T,B] | None, zT [B] | None, sums, loss3, status (device int32[4], read with tp_status())."""
+    x, r, theta, target, z0, B, T, K, y, zT, ws, status, warm, _, flags = _clipper_step_args(
+        "clipper_eval_tp", x, r, theta, target, n_chunks, y, z0, want_zT, ws, status, state, None, time_major, store_y=store_y,
+        workspace=(eval_workspace, "wdf_clipper_eval_tp_ws_bytes"))
+    if sums is None:
+        sums = torch.empty((2,), dtype=torch.float64, device=x.device)
+    elif not (isinstance(sums, torch.Tensor) and sums.dtype == torch.float64 and sums.is_cuda and sums.numel() == 2 and sums.is_contiguous()):
+        raise WdfHipError("sums must be a float64[2] device tensor")
+    loss3 = _out(loss3, 3, "loss3", "{mse, esr, mse + esr}", x)
+    rc = lib().wdf_clipper_eval_tp(
+        _ptr(x), _ptr(r), _ptr(theta), float(fs), int(n_up), int(n_down), _ptr(target), float(n_global), float(eps_energy),
+        int(skip), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(tol), _ptr(ws), _ptr(status), *warm, _ptr(sums),
+        _ptr(loss3), flags & ~WDF_NO_Y_STORE, _stream())        # (no y: a null pointer says it, the entry point knows no such flag)
+    _check(rc, "wdf_clipper_eval_tp")
+    return y, zT, sums, loss3, status
 
 
 def esr_finish(sums10, n_global, eps_energy, gtheta=None, loss3=None):

@@ -500,6 +500,8 @@ class MseStep:
         self.sse, self.gtheta = self.out[0:1], self.out[1:5]
         self.y = self.zs = self.zT = None
         self.ws_s, self.ws_s_k = None, None          # workspace of step_fused (made on first use)
+        self.ws_e, self.ws_e_k = None, None          # workspace of eval_fused (its own, made on first use)
+        self.sums_eval = self.loss_eval = None       # eval_fused: {S, E} (float64, the all-reduce payload), {mse, esr, mse + esr}
         self.warm = None
         if warm and tp is not None and tp.k_fwd > 1:
             self.warm = binding.TpWarmState(B, T, tp.k_fwd, max(max_warm_tiles, -(-tp.warmup // binding.warm_unit())), device)
@@ -589,6 +591,32 @@ class MseStep:
             binding.esr_finish(self.sums10, self.n_global, eps, gtheta=self.gtheta, loss3=self.loss)
         self.sse.copy_(self.sums10[0:1])
         return self.sse, self.gtheta
+
+
+    def eval_fused(self, theta, x, target, r=None):
+        """The loss WITHOUT its gradient in one pass over the data (csrc/wdf_clipper_eval.h, binding.clipper_eval_tp): forward and
+        the two loss sums, no tangent, no records -- a validation pass.  Chunking / verification / warm start as step_fused;
+        honours store_output (False: no y, self.y stays None) and sums_allreduce (the two float64 sums are all-reduced, then
+        binding.esr_coef).  Fills self.loss_eval = {mse, esr, mse + esr} (for "mse": skip = 0 and n = n_global, the loss is
+        loss_eval[0]) and self.y; self.gtheta and self.sse are not touched.  -> self.loss_eval."""
+        tp = self.tp
+        k = tp.k_fwd if tp is not None else 1
+        if self.ws_e is None or self.ws_e_k != k:
+            self.ws_e, self.ws_e_k = binding.eval_workspace(self.B, binding.lib().wdf_clipper_tp_chunks(self.T, k), x.device), k
+            self.sums_eval = torch.zeros((2,), dtype=torch.float64, device=x.device)
+            self.loss_eval = torch.zeros((3,), dtype=torch.float32, device=x.device)
+        if self.store_output and self.y is None:                 # (made by the first call that wants it)
+            self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=x.device)
+        W, tol = (tp.warmup, tp.tol) if tp is not None else (0, 1.0e-6)
+        eps = float(torch.finfo(torch.float64).eps)
+        binding.clipper_eval_tp(x, theta, self.fs, target, self.n_global, eps, self.skip, k, W, tol=tol, r=r, n_up=self.n_up,
+                                n_down=self.n_down, y=self.y if self.store_output else None, store_y=self.store_output, ws=self.ws_e,
+                                status=self.status, state=self.warm, sums=self.sums_eval, loss3=self.loss_eval,
+                                time_major=self.time_major)
+        if self.sums_allreduce is not None:
+            self.sums_allreduce(self.sums_eval)
+            binding.esr_coef(self.sums_eval, self.n_global, eps, loss=self.loss_eval)
+        return self.loss_eval
 
 
 def autotune_time_parallel(theta, x, target, fs, plan, time_major=False, n_up=1, n_down=1, reps=7, r=None):

@@ -39,6 +39,11 @@ ASYM_TREE_STEP_SERVES = {"mse": False, "mse_esr": False}
 # sample beats the composed path's fastest at both shapes of tools/ss_lin_esr_step_bench.py (the linear step's section).
 # Measured (profiles/r17_ss_lin_esr_step.jsonl): 0.142 ms against 0.905 ms at 8192 x 4096, 0.079 ms against 0.620 ms at 1340 x 2048.
 LIN_ESR_STEP_SERVES = True
+# Whether Circuit.mse / mse_esr(..., grad=False) take the loss-only evaluation pass on a resident diode-pair clipper
+# (csrc/wdf_clipper_eval.h; Circuit._eval_resident reaches it either way).  True only where tools/eval_pass_bench.py shows the pass
+# below the one-pass training step in the same process, storing y and not, each by more than the step's own min-max spread over
+# the rounds (profiles/eval_pass.jsonl).  False: grad=False runs the step and detaches.
+EVAL_PASS_SERVES = True
 
 
 def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
@@ -1026,7 +1031,71 @@ class Circuit:
         self.last_output = st.y if store_output else None        # (the stepper's own y [T,B], valid until the pair's next call)
         return loss
 
-    def mse_esr(self, x, target, skip=0, z0=None, carry_state=False, store_output=True):
+    def _loss_no_grad(self, kind, x, target, skip, z0, carry_state, store_output):
+        """mse() / mse_esr() with grad=False: the loss as a detached scalar.  The resident diode-pair clipper takes the loss-only
+        evaluation pass (EVAL_PASS_SERVES: DESIGN section 4), the resident MLP-root clipper its forward and loss sums; every
+        other circuit (and every stateful call) runs the default's code and the result is detached."""
+        binding.require_gpu()
+        tensors = isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)
+        stateful = (z0 is not None or carry_state) and self.ns > 0
+        if tensors and not stateful and not self.force_generic:
+            mres = getattr(self, "_mlp", None)
+            if kind == "mse+esr" and mres is not None and int(x.shape[1]) % 16 == 0:
+                return self._mlp_loss_no_grad(mres, x, target, skip, store_output)
+            if (EVAL_PASS_SERVES and getattr(self, "_pblock", None) is not None and self._is_clipper() and self.root_kind == "DiodePair"
+                    and 0 <= skip < int(x.shape[1])):
+                return self._eval_resident(x, target, kind, skip, store_output)
+        if kind == "mse":
+            loss = self.mse(x, target, z0=z0, carry_state=carry_state, store_output=store_output)
+        else:
+            loss = self.mse_esr(x, target, skip, z0=z0, carry_state=carry_state, store_output=store_output)
+        return loss.detach()                                     # (a new tensor: the pass's gradient is not attached to it)
+
+    def _mlp_loss_no_grad(self, mres, x, target, skip, store_output):
+        """The resident MLP-root clipper's loss without its gradient: the step's forward and loss-sum phases, then the loss from
+        the sums.  No reverse sweep, st.gw untouched; the entry's call count and its re-plan are not advanced."""
+        from . import mlp_root
+        ent = mres.entry(x, target, skip)
+        st = ent["st"]
+        st._call(mlp_root.PHASE_FWD | mlp_root.PHASE_SUMS, None)
+        if "eval_out" not in ent:
+            ent["eval_out"] = (torch.zeros(2, dtype=torch.float32, device=st.sums.device), torch.zeros(3, dtype=torch.float32, device=st.sums.device))
+        gcoef, loss3 = ent["eval_out"]
+        binding.esr_coef(st.sums, st.n_global, st.eps_energy, gcoef=gcoef, loss=loss3)
+        self.last_output = st.y if store_output else None
+        return loss3[2].clone().as_subclass(tf.Tensor)
+
+    def _eval_resident(self, x, target, kind, skip, store_output):
+        """grad=False on a resident diode-pair clipper: one evaluation pass (engine.MseStep.eval_fused) on an entry of its own,
+        keyed (kind, skip, "eval") -- its own stepper and warm-start state; the training entry of the same pair is never touched.
+        The plan is the training step's (engine.tuned_plan, fused: the same two sequences per lane)."""
+        from . import engine
+        pb = self._pblock
+        pb.flush()                                               # (queued optimizer updates of the block go out first)
+        ent = self._res_cache.get((x, target), (kind, int(skip), "eval"))
+        if ent is None:
+            dp, cap = self.root, self.top.P2
+            xd = x.as_subclass(torch.Tensor).to(pb.block.device).float()
+            xv, r = engine.split_channels(xd, self.per_sample_R is not None, time_major=True, anchor=x)
+            tgt = target.as_subclass(torch.Tensor).to(pb.block.device).float().reshape(xv.shape).contiguous()
+            host = pb.host_values()
+            R_plan = host[2] if r is None else engine.resistance_max(r)
+            tp = self.time_parallel
+            if tp == "auto":
+                tp = engine.tuned_plan(pb.block, xv, r, float(cap.FS), R_plan, host[3], n_up=dp.N_up, n_down=dp.N_down,
+                                       time_major=True, R_min=None if r is None else engine.resistance_min(r), fused=True)
+            T, B = xv.shape
+            st = engine.MseStep(B, T, float(cap.FS), tp, pb.block.device, n_up=dp.N_up, n_down=dp.N_down, time_major=True,
+                                warm=True, loss=kind, skip=int(skip), store_output=store_output)
+            ent = self._res_cache.put((x, target), (st, xv, r, tgt), (kind, int(skip), "eval"), 3 * _nbytes(xv, r, tgt))
+        st, xv, r, tgt = ent
+        st.store_output = bool(store_output)                     # (this call's choice: eval_fused makes y on first use)
+        engine.LAST_TP_STATUS["status"] = st.status
+        loss3 = st.eval_fused(pb.block, xv, tgt, r)
+        self.last_output = st.y if store_output else None
+        return loss3[0 if kind == "mse" else 2].clone().as_subclass(tf.Tensor)
+
+    def mse_esr(self, x, target, skip=0, z0=None, carry_state=False, store_output=True, grad=True):
         """The training loss of clipper_pot.py:146-156,177 on this circuit's output past `skip` samples (:232,248):
         mean((y - t)^2) + sqrt(sum((y - t)^2) / (sum(y^2) + eps) / n)  -- the scripts call esr_loss(outs, train_Y) on a
         function declared (target, predicted), so the normalising energy is the OUTPUT's.  target: [T,B] like the output.
@@ -1040,7 +1109,11 @@ class Circuit:
         z0 / carry_state: as in mse() -- the state the call starts from, or the one the previous carry_state call ended in
         (`circ.last_state`); composed from __call__(x, z0, return_state) (the resident one-pass steps start from zero state,
         which is what clipper_pot.py:110-111 does before every forward).
-        store_output=False: as in mse() -- "I will not read y"; `circ.last_output` is None after the call."""
+        store_output=False: as in mse() -- "I will not read y"; `circ.last_output` is None after the call.
+        grad=False: as in mse() -- "I will not differentiate this loss" (the validation line, clipper_pot.py:262-264); a
+        resident MLP-root clipper then runs its forward and the two loss sums only (no reverse sweep, no weight gradient)."""
+        if not grad:
+            return self._loss_no_grad("mse+esr", x, target, int(skip), z0, carry_state, bool(store_output))
         loss = self._mse_esr(x, target, skip, z0, carry_state, bool(store_output))
         if not store_output:
             self.last_output = None
@@ -1241,7 +1314,7 @@ class Circuit:
         return tree
 
     # -- topology tests
-    def mse(self, x, target, z0=None, carry_state=False, store_output=True):
+    def mse(self, x, target, z0=None, carry_state=False, store_output=True, grad=True):
         """tf.reduce_mean(tf.square(self(x) - target)) as ONE fused evaluation where the kernels allow
         it (diode-pair clipper: forward kernel + MSE-fused reverse sweep, the gradient of every
         trainable component ready when tape.gradient asks; the clipper under an AsymDiodePair root with a Newton solver: the
@@ -1263,7 +1336,16 @@ class Circuit:
         default.  In every case `circ.last_output` is None after such a call.  The resident cache keeps ONE entry per
         (x, target) pair whichever way it is called -- one workspace, one warm-start state -- and allocates the pair's y buffer
         lazily, on the first call that wants it: a training set only ever run without y holds no y buffer, and a later
-        storing call on the same pair gets its y."""
+        storing call on the same pair gets its y.
+
+        grad=False is a permission too: "I will not differentiate this loss" (a validation pass).  The loss that comes back is
+        detached in every case (`requires_grad` False, no gradient attached).  A resident diode-pair clipper then runs the
+        loss-only evaluation pass (csrc/wdf_clipper_eval.h: forward and the loss sums, no tangent, no gradient) on an entry of
+        its own per (x, target) pair -- its own stepper, workspace and warm-start state; a training entry on the same pair is not
+        touched; every other circuit computes exactly as with the default and detaches the result.  grad=True runs the code
+        it always ran; torch.no_grad() routes nothing."""
+        if not grad:
+            return self._loss_no_grad("mse", x, target, 0, z0, carry_state, bool(store_output))
         loss = self._mse(x, target, z0, carry_state, bool(store_output))
         if not store_output:
             self.last_output = None

@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed).  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -227,6 +227,25 @@ int wdf_clipper_step_esr_tp(const float* x, const float* r, float* theta, float 
                             int32_t* step, const float* lr, float beta1, float beta2, float eps, const float* lo,
                             const float* hi, int flags, void* stream);
 int wdf_esr_finish(const float* sums10, double n_global, double eps_energy, float* gtheta, float* loss3, void* stream);
+
+/* The LOSS-ONLY evaluation pass (csrc/wdf_clipper_eval.h): the forward and the two loss sums S = sum (y - target)^2 and
+ * E = sum y^2 over the steps >= skip in one pass, for a loss nobody differentiates -- the validation half of every epoch
+ * (clipper_pot.py:245-269).  No tangent, no chunk records, no gradient, no optimizer: theta is const.  x and target [T][B] read
+ * once; y [T][B] written once, or -- y = NULL -- not at all (8 B/sample).  Chunks are time-parallel and verified like
+ * wdf_clipper_step_mse_tp's: state (the same buffer type, wdf_clipper_fwd_tp_state_bytes / _reset; NULL: cold every call),
+ * status, n_chunks (a value wdf_clipper_tp_chunks returns), warmup, tol and max_warm_tiles mean what they mean there.
+ * sums[2] (device doubles, required) receives {S, E} of this call's batch: with several ranks all-reduce it and call
+ * wdf_esr_coef.  loss3 (optional) receives {S/n, sqrt(S / (E + eps_energy) / n), their sum}, n = n_global (wdf_esr_coef's
+ * formulas).  skip in 0..T-1.  ws: wdf_clipper_eval_tp_ws_bytes bytes, initialised ONCE with wdf_clipper_eval_tp_ws_init.
+ * flags: WDF_X_TIME_MAJOR, WDF_GENERAL_ROOT, WDF_R_PER_SEQUENCE, WDF_ONE_SEQUENCE_PER_LANE; every other bit (WDF_NO_Y_STORE
+ * among them: pass y = NULL instead) is an unknown flag.  The same call on the same inputs returns the same bits. */
+size_t wdf_clipper_eval_tp_ws_bytes(int64_t B, int n_chunks);
+int wdf_clipper_eval_tp_ws_init(void* ws, int64_t B, int n_chunks, void* stream);
+int wdf_clipper_eval_tp(const float* x, const float* r, const float* theta, float fs, int n_up, int n_down,
+                        const float* target, double n_global, double eps_energy, int64_t skip,
+                        float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup, float tol,
+                        void* ws, void* status, void* state, int max_warm_tiles,
+                        double* sums, float* loss3, int flags, void* stream);
 
 /* MSE + ESR, the training loss of clipper_pot.py (:146-156 esr_loss, :177 loss_func, :232,248
  * evaluated past skip_samples with (outs, target) passed as (target_y, predicted_y), so the energy
