@@ -209,6 +209,9 @@ for _twin, _at in (("wdf_ss_lin_step_mse", 8), ("wdf_ss_lin_step_esr", 10)):
 SIGNATURES["wdf_clipper_eval_tp_ws_bytes"] = SIGNATURES["wdf_clipper_step_mse_tp_ws_bytes"]
 SIGNATURES["wdf_clipper_eval_tp_ws_init"] = SIGNATURES["wdf_clipper_step_mse_tp_ws_init"]
 SIGNATURES["wdf_clipper_eval_tp"] = (_ci, SIGNATURES["wdf_clipper_step_esr_tp"][1][:22] + [_p, _p, _ci, _p])
+# the MLP-root clipper's loss-only evaluation pass: the resident step's head up to y (x, p, lr, theta2, w, hidden, n_layers,
+# activation, fs, target, skip, n_global, eps_energy, y), then state, B, T, n_items, sums, loss3, stream
+SIGNATURES["wdf_clipper_mlp_eval"] = (_ci, SIGNATURES["wdf_clipper_mlp_step"][1][:14] + [_p, _i64, _i64, _ci, _p, _p, _p])
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 

@@ -44,6 +44,14 @@ LIN_ESR_STEP_SERVES = True
 # below the one-pass training step in the same process, storing y and not, each by more than the step's own min-max spread over
 # the rounds (profiles/eval_pass.jsonl).  False: grad=False runs the step and detaches.
 EVAL_PASS_SERVES = True
+# Whether Circuit.mse_esr(..., grad=False) takes the MLP-root clipper's loss-only evaluation pass (csrc/wdf_mlp_eval.h:
+# wdf_clipper_mlp_eval, mlp_root.MlpEvalPass) on a resident MLP-root clipper.  True only where tools/mlp_eval_pass_bench.py shows the
+# pass, storing y and not, below BOTH the full training step and the step's forward + loss-sum phases followed by wdf_esr_coef, each
+# by more than the compared variant's own min-max spread over the rounds, in a loop whose weights move
+# (profiles/mlp_eval_pass.jsonl).  False: grad=False runs the step's forward and loss-sum phases.
+# Measured at 1340 x 2048, 2x16 (median, min-max over 20 rounds): step 0.390 ms (0.382-0.408), forward + sums + esr_coef 0.373
+# (0.372-0.374), the pass 0.188 (0.175-0.195) storing y and 0.189 (0.177-0.197) without: below both by more than their spreads.
+MLP_EVAL_PASS_SERVES = True
 
 
 def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
@@ -1033,7 +1041,7 @@ class Circuit:
 
     def _loss_no_grad(self, kind, x, target, skip, z0, carry_state, store_output):
         """mse() / mse_esr() with grad=False: the loss as a detached scalar.  The resident diode-pair clipper takes the loss-only
-        evaluation pass (EVAL_PASS_SERVES: DESIGN section 4), the resident MLP-root clipper its forward and loss sums; every
+        evaluation pass (EVAL_PASS_SERVES: DESIGN section 4), the resident MLP-root clipper its own (MLP_EVAL_PASS_SERVES); every
         other circuit (and every stateful call) runs the default's code and the result is detached."""
         binding.require_gpu()
         tensors = isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)
@@ -1052,11 +1060,25 @@ class Circuit:
         return loss.detach()                                     # (a new tensor: the pass's gradient is not attached to it)
 
     def _mlp_loss_no_grad(self, mres, x, target, skip, store_output):
-        """The resident MLP-root clipper's loss without its gradient: the step's forward and loss-sum phases, then the loss from
-        the sums.  No reverse sweep, st.gw untouched; the entry's call count and its re-plan are not advanced."""
+        """The resident MLP-root clipper's loss without its gradient.  MLP_EVAL_PASS_SERVES: the loss-only evaluation pass
+        (mlp_root.MlpEvalPass, made on first use inside the pair's entry: its own state block, the entry's tensors) -- the training
+        side of the entry (its state block, st.gw, zstash, kappa, the call count and its re-plan) is not touched, so training is
+        bit for bit what it is without the call, on the validated pair too.  Otherwise the step's forward and loss-sum phases,
+        then the loss from the sums: no reverse sweep, st.gw untouched, the entry's call count and re-plan not advanced."""
         from . import mlp_root
         ent = mres.entry(x, target, skip)
         st = ent["st"]
+        if MLP_EVAL_PASS_SERVES:
+            ev = ent.get("eval")
+            if ev is None:
+                ev = ent["eval"] = mlp_root.MlpEvalPass.of(st)
+                ent["eval_calls"] = 0
+            loss3 = ev.run(store_output=store_output)
+            ent["eval_calls"] += 1
+            if ent["eval_calls"] == 24:                          # the controller has settled: one measured re-plan (the training entry's rule)
+                ev.replan()
+            self.last_output = st.y if store_output else None
+            return loss3[2].clone().as_subclass(tf.Tensor)
         st._call(mlp_root.PHASE_FWD | mlp_root.PHASE_SUMS, None)
         if "eval_out" not in ent:
             ent["eval_out"] = (torch.zeros(2, dtype=torch.float32, device=st.sums.device), torch.zeros(3, dtype=torch.float32, device=st.sums.device))

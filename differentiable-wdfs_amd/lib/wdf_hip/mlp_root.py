@@ -498,18 +498,12 @@ def plan_step_items(T, wcol_steps, n_items, min_chunk=32):
     return _np.asarray(items, dtype=_np.int32).reshape(-1, 4)
 
 
-class MlpTrainStep:
-    """The resident training step of the MLP-root pot clipper (include/wdf_hip.h: wdf_clipper_mlp_step).
+class _MlpResident:
+    """What the resident training step (MlpTrainStep) and the loss-only evaluation pass (MlpEvalPass) share: the resident set and
+    its per-sample coefficients, the first guess of the columns' warm-ups, and the state block of csrc/wdf_mlp_step.h with its
+    plan, controller knobs and read-backs (wdf_clipper_mlp_step_state_bytes / _plan / _read / _set / _set_wcol)."""
 
-        st = MlpTrainStep(x, r, target, w, hidden, n_layers, fs, C, skip=50, adam=binding.Adam(...))
-        for epoch in ...: st.step()          # w and the Adam moments are updated in place; st.loss3 = {mse, esr, loss}
-
-    x, r [B,T] (r None: static R), target [T,B]: the resident training set.  w: the flat weights (float32, device, updated
-    in place).  Everything a step reads or writes lives in buffers that do not move: capture-safe (HIP graph)."""
-
-    def __init__(self, x, r, target, w, hidden, n_layers, fs, C, R_static=None, skip=50, adam=None, n_global=None,
-                 eps_energy=None, activation="tanh", n_items=None, wgrad_chunks=None, tol=4.0e-6, sums_allreduce=None,
-                 grad_allreduce=None):
+    def _init_set(self, x, r, target, w, hidden, n_layers, fs, C, R_static, skip, n_global, eps_energy, activation, n_items, tol):
         binding.require_gpu()
         self.lib = binding.lib()
         f32 = binding._f32_dev
@@ -526,7 +520,6 @@ class MlpTrainStep:
         self.skip = int(skip)
         self.n_global = float(n_global if n_global is not None else B * (T - self.skip))
         self.eps_energy = float(_np.finfo(float).eps if eps_energy is None else eps_energy)
-        self.adam, self.sums_allreduce, self.grad_allreduce = adam, sums_allreduce, grad_allreduce
         self.ncol = (B + 15) // 16
         Rv = float(R_static) if R_static is not None else 45.0e3
         self.theta2 = torch.tensor([Rv, float(C)], dtype=torch.float32, device=dev)
@@ -550,19 +543,10 @@ class MlpTrainStep:
         self.cold = int(-(-int(1.15 * _np.max(_np.ceil(_np.log(0.01 * tol) / _np.log(rho)))) // 16) * 16)
         self.cold = min(self.cold, T)
         self.w_max = max(2, min(self.cold // 16, 40))
-        w0 = _np.clip(_np.ceil(_np.log(1.0e-5) / _np.log(rho) / 16.0), 2, self.w_max).astype(_np.int32)
+        self._w0 = _np.clip(_np.ceil(_np.log(1.0e-5) / _np.log(rho) / 16.0), 2, self.w_max).astype(_np.int32)
         # one wave per SIMD (the forward is a dependent chain per wave; a second wave on a SIMD would just share its issue slots)
         self.n_items_max = int(n_items) if n_items else max(self.ncol, min(engine.N_SIMD, self.ncol * (T // 64)))
-        self.wgrad_chunks = int(wgrad_chunks) if wgrad_chunks else max(1, min(2 * engine.N_SIMD // self.ncol, T // 64))
         self.tol = float(tol)
-        self.y = torch.empty((T, B), dtype=torch.float32, device=dev)
-        self.zstash, self.kappa = torch.empty_like(self.y), torch.empty_like(self.y)
-        self.sums = torch.zeros(2, dtype=torch.float64, device=dev)
-        self.gw = torch.zeros(self.w.numel(), dtype=torch.float32, device=dev)
-        self.loss3 = torch.zeros(3, dtype=torch.float32, device=dev)
-        self.gcoef = torch.zeros(2, dtype=torch.float32, device=dev)
-        self.state = None
-        self._install_plan(w0, reset=True)
 
     # -- plan ---------------------------------------------------------------------------------------------------
     def _geom(self):
@@ -646,6 +630,51 @@ class MlpTrainStep:
         self._install_plan(wp, reset=False)
         return True
 
+    def freeze(self, on=True):
+        binding._check(self.lib.wdf_clipper_mlp_step_set(binding._ptr(self.state), 12, 1 if on else 0, binding._stream()),
+                       "wdf_clipper_mlp_step_set")
+
+    def set_controller(self, cold16=None, tol=None, repair_at=None):
+        """Controller words of the live state (wdf_clipper_mlp_step_set): cold16 -- the cold call's warm-up in 16-step units;
+        tol -- the chunk verification's tolerance; repair_at -- a re-run chunk has met the old trajectory at repair_at * tol."""
+        words = []
+        if cold16 is not None:
+            words.append((3, int(cold16)))
+        for field, v in ((9, tol), (13, repair_at)):
+            if v is not None:
+                words.append((field, int(_np.float32(v).view(_np.int32))))
+        for field, bits in words:
+            binding._check(self.lib.wdf_clipper_mlp_step_set(binding._ptr(self.state), field, bits, binding._stream()),
+                           "wdf_clipper_mlp_step_set")
+        if tol is not None:
+            self.tol = float(tol)
+
+
+class MlpTrainStep(_MlpResident):
+    """The resident training step of the MLP-root pot clipper (include/wdf_hip.h: wdf_clipper_mlp_step).
+
+        st = MlpTrainStep(x, r, target, w, hidden, n_layers, fs, C, skip=50, adam=binding.Adam(...))
+        for epoch in ...: st.step()          # w and the Adam moments are updated in place; st.loss3 = {mse, esr, loss}
+
+    x, r [B,T] (r None: static R), target [T,B]: the resident training set.  w: the flat weights (float32, device, updated
+    in place).  Everything a step reads or writes lives in buffers that do not move: capture-safe (HIP graph)."""
+
+    def __init__(self, x, r, target, w, hidden, n_layers, fs, C, R_static=None, skip=50, adam=None, n_global=None,
+                 eps_energy=None, activation="tanh", n_items=None, wgrad_chunks=None, tol=4.0e-6, sums_allreduce=None,
+                 grad_allreduce=None):
+        self._init_set(x, r, target, w, hidden, n_layers, fs, C, R_static, skip, n_global, eps_energy, activation, n_items, tol)
+        B, T, dev = self.B, self.T, x.device
+        self.adam, self.sums_allreduce, self.grad_allreduce = adam, sums_allreduce, grad_allreduce
+        self.wgrad_chunks = int(wgrad_chunks) if wgrad_chunks else max(1, min(2 * engine.N_SIMD // self.ncol, T // 64))
+        self.y = torch.empty((T, B), dtype=torch.float32, device=dev)
+        self.zstash, self.kappa = torch.empty_like(self.y), torch.empty_like(self.y)
+        self.sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.gw = torch.zeros(self.w.numel(), dtype=torch.float32, device=dev)
+        self.loss3 = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.gcoef = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.state = None
+        self._install_plan(self._w0, reset=True)
+
     def autotune(self, calls=16, verbose=False):
         """Pick the chunk plan by MEASURING: a handful of candidate plans (the columns' peak / current warm-ups, with and
         without head room, three values of the planner's warm-up cost) are each run for `calls` training steps -- one
@@ -679,25 +708,6 @@ class MlpTrainStep:
         ms, label, items = min(results, key=lambda r_: r_[0])
         self._install_plan(None, reset=False, items=items)
         return label, ms
-
-    def freeze(self, on=True):
-        binding._check(self.lib.wdf_clipper_mlp_step_set(binding._ptr(self.state), 12, 1 if on else 0, binding._stream()),
-                       "wdf_clipper_mlp_step_set")
-
-    def set_controller(self, cold16=None, tol=None, repair_at=None):
-        """Controller words of the live state (wdf_clipper_mlp_step_set): cold16 -- the cold call's warm-up in 16-step units;
-        tol -- the chunk verification's tolerance; repair_at -- a re-run chunk has met the old trajectory at repair_at * tol."""
-        words = []
-        if cold16 is not None:
-            words.append((3, int(cold16)))
-        for field, v in ((9, tol), (13, repair_at)):
-            if v is not None:
-                words.append((field, int(_np.float32(v).view(_np.int32))))
-        for field, bits in words:
-            binding._check(self.lib.wdf_clipper_mlp_step_set(binding._ptr(self.state), field, bits, binding._stream()),
-                           "wdf_clipper_mlp_step_set")
-        if tol is not None:
-            self.tol = float(tol)
 
     # -- the step -------------------------------------------------------------------------------------------------
     def _call(self, phase, adam):
@@ -741,6 +751,58 @@ class MlpTrainStep:
 
     def backward_only(self):
         self._call(PHASE_BWD, self.adam)
+
+
+class MlpEvalPass(_MlpResident):
+    """The loss-only evaluation pass of the MLP-root pot clipper on one resident set (include/wdf_hip.h: wdf_clipper_mlp_eval;
+    clipper_pot.py:251-262: the validation line of an epoch).
+
+        ev = MlpEvalPass.of(st)                  # on the set of an MlpTrainStep: shares its x, p, lr, theta2, target, w and y
+        ev = MlpEvalPass(x, r, target, w, hidden, n_layers, fs, C, skip=50)
+        loss3 = ev.run()                         # {mse, esr, loss}; ev.sums = {S, E}; ev.y unless store_output=False
+
+    Four launches on a state block of its own (the step's layout, planned by plan_step_items from the same first-guess
+    warm-ups); every call commits itself, so the next one starts its chunks from this one's snapshots and the device steers the
+    warm-ups as it does for training steps.  Nothing of a training step is written: not its state block, gw, zstash, kappa or
+    the weights.  Buffers do not move: capture-safe."""
+
+    _SHARED = ("lib", "x", "r", "p", "lr", "theta2", "target", "w", "y", "B", "T", "hidden", "n_layers", "fs", "act", "skip", "n_global",
+               "eps_energy", "ncol", "cold", "w_max", "_w0", "tol")
+
+    def __init__(self, x, r, target, w, hidden, n_layers, fs, C, R_static=None, skip=50, n_global=None, eps_energy=None,
+                 activation="tanh", n_items=None, tol=4.0e-6):
+        self._init_set(x, r, target, w, hidden, n_layers, fs, C, R_static, skip, n_global, eps_energy, activation, n_items, tol)
+        self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=x.device)
+        self._init_pass()
+
+    @classmethod
+    def of(cls, step, n_items=None):
+        """The pass on the resident set of an MlpTrainStep: its tensors are shared (no second wdf_clipper_mlp_step_prepare, no
+        copies); the pass owns its state block, sums and loss3."""
+        self = cls.__new__(cls)
+        for name in cls._SHARED:
+            setattr(self, name, getattr(step, name))
+        self.n_items_max = int(n_items) if n_items else step.n_items_max
+        self._init_pass()
+        return self
+
+    def _init_pass(self):
+        dev = self.x.device
+        self.wgrad_chunks = 1                                    # (the state block's layout argument: no reverse sweep here)
+        self.sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.loss3 = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.state = None
+        self._install_plan(self._w0, reset=True)
+
+    def run(self, store_output=True):
+        """One evaluation call -> loss3 (device float[3] = {mse, esr, mse + esr}; the pass's own buffer)."""
+        rc = self.lib.wdf_clipper_mlp_eval(
+            binding._ptr(self.x), binding._ptr(self.p), binding._ptr(self.lr), binding._ptr(self.theta2), binding._ptr(self.w),
+            self.hidden, self.n_layers, self.act, self.fs, binding._ptr(self.target), self.skip, self.n_global, self.eps_energy,
+            binding._ptr(self.y) if store_output else None, binding._ptr(self.state), self.B, self.T, self.n_items,
+            binding._ptr(self.sums), binding._ptr(self.loss3), binding._stream())
+        binding._check(rc, "wdf_clipper_mlp_eval")
+        return self.loss3
 
 
 # ------------------------------------------------------------------------------ the resident step behind the element API

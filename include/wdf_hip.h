@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -515,6 +515,29 @@ int wdf_clipper_mlp_step(const float* x, const float* p, const float* lr, const 
                          int n_items, int wgrad_chunks, int phase, double* sums, float* gw, float* loss3, float* gcoef,
                          float* adam_m, float* adam_v, int32_t* adam_step, const float* adam_lr, float beta1, float beta2,
                          float eps, void* stream);
+
+/* The LOSS-ONLY evaluation pass of the same resident clipper (csrc/wdf_mlp_eval.h): the validation line of every epoch of
+ * clipper_pot.py:251-262 -- forward, MSE + ESR past skip, no gradient -- as FOUR launches steered on the device (every
+ * buffer fixed: one HIP graph can replay it): the step's chunked, verified forward and its two gated repair launches
+ * around a block that computes y and the two loss sums only (no input Jacobian, no adjoint maps, no zstash / kappa),
+ * then one wave that adds the columns' sums, writes the losses and COMMITS the call (call count, snapshot parity,
+ * have_snap), so the next call starts its chunks from this call's snapshots and the warm-up controller is steered
+ * without a training step ever running on the state.
+ *
+ *   state   the step's own state block: wdf_clipper_mlp_step_state_bytes / _plan / _read / _set / _set_wcol with
+ *           wgrad_chunks = 1.  A block of its own per evaluated set; never the block a training step runs on.  The
+ *           block maps and weight-gradient partials in it are left untouched.
+ *   x, p, lr, theta2, target   as wdf_clipper_mlp_step's (p and lr both NULL: static R from theta2); w is read only.
+ *   y       [T][B], or NULL: the outputs are not stored.
+ *   sums    device double[2] = {S = sum (y - target)^2, E = sum y^2} past skip (E without eps_energy), always written.
+ *   loss3   device float[3] = {S/n, sqrt(S/(E + eps_energy)/n), their sum}, n = n_global; may be NULL.
+ * WDF_EINVAL before any HIP call: a null x / w / target / state / sums; p without lr or the reverse; static R without
+ * theta2; fs <= 0, skip < 0, n_global <= 0, eps_energy < 0; x / p / lr not 16-byte aligned; a network, T or plan size
+ * that wdf_clipper_mlp_step refuses (with that function's message).                                            */
+int wdf_clipper_mlp_eval(const float* x, const float* p, const float* lr, const float* theta2, const float* w, int hidden,
+                         int n_layers, int activation, float fs, const float* target, int64_t skip, double n_global,
+                         double eps_energy, float* y, void* state, int64_t B, int64_t T, int n_items, double* sums,
+                         float* loss3, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Generic tree + one root, as a state-space recursion (csrc/wdf_statespace.h):
