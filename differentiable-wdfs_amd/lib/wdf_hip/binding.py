@@ -212,6 +212,13 @@ SIGNATURES["wdf_clipper_eval_tp"] = (_ci, SIGNATURES["wdf_clipper_step_esr_tp"][
 # the MLP-root clipper's loss-only evaluation pass: the resident step's head up to y (x, p, lr, theta2, w, hidden, n_layers,
 # activation, fs, target, skip, n_global, eps_energy, y), then state, B, T, n_items, sums, loss3, stream
 SIGNATURES["wdf_clipper_mlp_eval"] = (_ci, SIGNATURES["wdf_clipper_mlp_step"][1][:14] + [_p, _i64, _i64, _ci, _p, _p, _p])
+# the diode-root trees' loss-only evaluation pass: the step's workspace walk, plan, set and read; the entry point takes the MSE + ESR
+# step's head less jac (x, coef, params, n_tree, ns, ni, n_up, n_down, target, skip), then n_global, eps, y, ws, sums, loss3, B, T,
+# n_chunks, stream
+for _fn in ("ws_bytes", "plan", "set", "read"):
+    SIGNATURES["wdf_ss_nl_eval_" + _fn] = SIGNATURES["wdf_ss_nl_step_" + _fn]
+_nl = SIGNATURES["wdf_ss_nl_step_esr"][1]
+SIGNATURES["wdf_ss_nl_eval"] = (_ci, _nl[:3] + _nl[4:11] + [_cd, _cd, _p, _p, _p, _p, _i64, _i64, _ci, _p])
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
@@ -1658,6 +1665,76 @@ def ss_lin_step_esr(x_tm, coef, jac, target, skip, n_chunks, n_global=None, eps=
     _lin_step_call("wdf_ss_lin_step_esr", store_y, (_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), n_global, float(eps), skip),
                    y, (_ptr(ws), _ptr(sums), _ptr(g), _ptr(loss3), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()))
     return {"y": y, "sums": sums, "g": g, "loss3": loss3, "gcoef": gcoef, "zT": zT, "ws": ws}
+
+
+NL_EVAL_SECANT = 12                  # wdf_ss_nl_eval_set: the secant switch, behind the step's fields 2..11
+
+
+def ss_nl_eval_plan(ns, ni, B, T, n_chunks, cold_warmup, warm_warmup, w_min, w_max, tol, like):
+    """A workspace of the diode-root evaluation pass (wdf_ss_nl_eval_ws_bytes), planned (wdf_ss_nl_eval_plan) on the device of
+    `like`: the first call starts its chunks from z = 0 with cold_warmup, later ones from the snapshots the calls on THIS
+    workspace took."""
+    require_gpu()
+    need = lib().wdf_ss_nl_eval_ws_bytes(int(ns), int(ni), int(B), int(T), int(n_chunks))
+    if need == 0:
+        raise WdfHipError(lib().wdf_last_error().decode() or "wdf_ss_nl_eval_ws_bytes: bad arguments")
+    ws = torch.empty((need,), dtype=torch.uint8, device=like.device)
+    _check(lib().wdf_ss_nl_eval_plan(_ptr(ws), int(ns), int(ni), int(B), int(T), int(n_chunks), int(cold_warmup), int(warm_warmup),
+                                     int(w_min), int(w_max), float(tol), _stream()), "wdf_ss_nl_eval_plan")
+    return ws
+
+
+def ss_nl_eval_set(ws, field, value):
+    """Field 2..11 of the control block (the step's), or NL_EVAL_SECANT (0: chunks start from the last snapshot as it is)."""
+    _check(lib().wdf_ss_nl_eval_set(_ptr(ws), int(field), float(value), _stream()), "wdf_ss_nl_eval_set")
+
+
+def ss_nl_eval_read(ws):
+    """The control block as a dict (NlStepCtl: the step's 32 words, the step's meaning) -- synchronises."""
+    raw = np.zeros(32, dtype=np.int32)
+    _check(lib().wdf_ss_nl_eval_read(_ptr(ws), raw.ctypes.data, _stream()), "wdf_ss_nl_eval_read")
+    f = raw.view(np.float32)
+    return {"call": int(raw[0]), "parity": int(raw[1]), "have_snap": int(raw[2]), "w_cur": int(raw[3]), "w_snap": int(raw[4]),
+            "w_min": int(raw[5]), "w_max": int(raw[6]), "cool": int(raw[7]), "tol": float(f[8]), "n_bad": int(raw[12]),
+            "max_miss": float(f[13]), "gated_groups": int(raw[14]), "total_gated": int(raw[15]), "w_used": int(raw[19])}
+
+
+def ss_nl_eval(x_tm, coef, params, n_tree, ns, ni, target, n_chunks, ws, skip=0, n_global=None, eps=ESR_EPS, n_up=1, n_down=1, y=None,
+               store_y=True, sums=None, loss3=None):
+    """The loss-only evaluation pass of a small tree with a diode-pair root (wdf_ss_nl_eval, csrc/wdf_ss_nl_eval.h): forward and
+    the two loss sums past skip in one sweep, no gradient.  x_tm [T,ni,B] time-major, coef the probe's outputs (coefficients, then
+    the port resistance), params the component values with Is, nVt at [n_tree], [n_tree + 1], target [T,B]; ws from
+    ss_nl_eval_plan().  store_y=False: y is never stored or allocated (None in the dict), a y= handed in is refused.
+    -> dict: y [T,B] | None, sums [2] float64 = {S, E}, loss3 [3] = {mse, esr, mse + esr} with n = n_global (None: B (T - skip)), ws."""
+    _no_y("ss_nl_eval", y, store_y)
+    require_gpu()
+    x_tm, coef, params, target = _f32_dev(x_tm, "x"), _f32_dev(coef, "coef"), _f32_dev(params, "params"), _f32_dev(target, "target")
+    ns, ni, n_tree, skip = int(ns), int(ni), int(n_tree), int(skip)
+    if x_tm.dim() != 3 or x_tm.shape[1] != ni:
+        raise WdfHipError(f"ss_nl_eval: x must be time-major [T,{ni},B], got {tuple(x_tm.shape)}")
+    T, _, B = (int(v) for v in x_tm.shape)
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if not 0 <= skip < T:
+        raise WdfHipError(f"ss_nl_eval: skip must be in [0, T) = [0, {T}), got {skip}")
+    n_global = float(B * (T - skip)) if n_global is None else float(n_global)
+    if not n_global > 0.0 or not float(eps) >= 0.0:
+        raise WdfHipError("ss_nl_eval: n_global > 0 and eps >= 0")
+    y, _ = _y_zT(y, False, T, B, x_tm, None, store_y)
+    need = lib().wdf_ss_nl_eval_ws_bytes(ns, ni, B, T, int(n_chunks))
+    if need == 0:
+        raise WdfHipError(lib().wdf_last_error().decode() or "wdf_ss_nl_eval_ws_bytes: bad arguments")
+    if ws is None:
+        raise WdfHipError("ss_nl_eval: ws must be a workspace planned by ss_nl_eval_plan()")
+    ws = _ws(ws, need, x_tm)
+    if sums is None:
+        sums = torch.empty((2,), dtype=torch.float64, device=x_tm.device)
+    elif not (isinstance(sums, torch.Tensor) and sums.is_cuda and sums.dtype == torch.float64 and sums.numel() == 2 and sums.is_contiguous()):
+        raise WdfHipError("sums must hold {S, E} (2 doubles) on the GPU")
+    loss3 = _out(loss3, 3, "loss3", "{mse, esr, mse + esr}", x_tm)
+    _check(lib().wdf_ss_nl_eval(_ptr(x_tm), _ptr(coef), _ptr(params), n_tree, ns, ni, int(n_up), int(n_down), _ptr(target), skip, n_global,
+                                float(eps), _ptr(y), _ptr(ws), _ptr(sums), _ptr(loss3), B, T, int(n_chunks), _stream()), "wdf_ss_nl_eval")
+    return {"y": y, "sums": sums, "loss3": loss3, "ws": ws}
 
 
 def ss_lin_esr_finish(sums, n_global, eps=ESR_EPS, g=None, loss3=None):

@@ -52,6 +52,10 @@ EVAL_PASS_SERVES = True
 # Measured at 1340 x 2048, 2x16 (median, min-max over 20 rounds): step 0.390 ms (0.382-0.408), forward + sums + esr_coef 0.373
 # (0.372-0.374), the pass 0.188 (0.175-0.195) storing y and 0.189 (0.177-0.197) without: below both by more than their spreads.
 MLP_EVAL_PASS_SERVES = True
+# grad=False on a resident diode-root tree: the loss-only evaluation pass (csrc/wdf_ss_nl_eval.h) instead of the training step.
+# Decided by tools/ss_nl_eval_bench.py (profiles/ss_nl_eval_pass.jsonl): the storing pass is below the MSE step
+# and below the composed MSE + ESR route, each by more than the other's own min-max spread, at both shapes.
+NL_EVAL_PASS_SERVES = True
 
 
 def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
@@ -376,6 +380,9 @@ def _nbytes(*ts):
 _LIN_OCC = int(os.environ.get("WDF_LIN_OCC", "2"))       # chunks are cut so that every SIMD gets this many waves
 _NL_OCC = int(os.environ.get("WDF_NL_OCC", "1"))
 _NL_WMIN = int(os.environ.get("WDF_NL_WMIN", "16"))      # the shortest warm-up the device's controller may settle on
+# chunk waves per SIMD of the diode-root evaluation pass: 1, as the step (the fastest of the sweep over 1, 2, 4 at 8192 x 4096;
+# at 1340 x 2048 the 64-step floor of a chunk caps the count before it matters: DESIGN section 4)
+_NL_EVAL_OCC = int(os.environ.get("WDF_NL_EVAL_OCC", str(_NL_OCC)))
 _ROWS = 1024                                             # result rows per slab (see _LinResident.entry)
 NL_TOL = 1.0e-6                                          # boundary tolerance of the diode-root one-pass step (plan_ss_time_parallel's)
 ESR_EPS = float(np.finfo(float).eps)                     # what the scripts' esr_loss adds to the energy (clipper_pot.py:146-156)
@@ -482,14 +489,7 @@ class _LinResident:
         ent = self.cache.get((x, target), extra)
         if ent is None:
             circ, dev = self.circ, self.pb.block.device
-            xd = x.as_subclass(torch.Tensor).to(dev).float()
-            if xd.dim() == 2:
-                xd = xd.unsqueeze(-1)
-            B, T, ni = xd.shape
-            if ni != circ.ni:
-                raise binding.WdfHipError(f"x must be [B,T,{circ.ni}] (or [B,T] for one channel), got {tuple(x.shape)}")
-            x_tm = xd.permute(1, 2, 0).contiguous()               # [T][ni][B]: once per training set
-            tgt = target.as_subclass(torch.Tensor).to(dev).float().reshape(T, B).contiguous()
+            x_tm, tgt, B, T = self._resident_pair(x, target)
             per_wave = 128 if B % 2 == 0 else 64                  # (two sequences per lane when the rows pair up)
             if loss != "mse" and circ.root_kind == "DiodePair" and circ.ns * circ.ni > 1:
                 per_wave = 64                                     # (the diode-root MSE + ESR step pairs them up on the smallest tree only;
@@ -524,6 +524,17 @@ class _LinResident:
             self.output(ent)
         return ent
 
+    def _resident_pair(self, x, target):
+        """-> x time-major [T][ni][B] and target [T][B] on the block's device (made once per set), B, T"""
+        dev = self.pb.block.device
+        xd = x.as_subclass(torch.Tensor).to(dev).float()
+        if xd.dim() == 2:
+            xd = xd.unsqueeze(-1)
+        B, T, ni = xd.shape
+        if ni != self.circ.ni:
+            raise binding.WdfHipError(f"x must be [B,T,{self.circ.ni}] (or [B,T] for one channel), got {tuple(x.shape)}")
+        return xd.permute(1, 2, 0).contiguous(), target.as_subclass(torch.Tensor).to(dev).float().reshape(T, B).contiguous(), B, T
+
     @staticmethod
     def output(ent):
         """The entry's output buffer y [T,B], made on first use."""
@@ -546,8 +557,9 @@ class _LinResident:
                                               max(16, Lc // 16 * 16), float(NL_TOL), binding._stream()), "wdf_ss_nl_step_plan")
         return ws
 
-    def _watch(self, ent):
-        """Every 16th call, WITHOUT a synchronisation: look at the control block as it was 16 calls ago.  Groups that keep
+    def _watch(self, ent, plan=None):
+        """(plan: what makes a fresh workspace -- the step's _plan_nl, or the evaluation pass's _plan_nl_eval on its own entry.)
+        Every 16th call, WITHOUT a synchronisation: look at the control block as it was 16 calls ago.  Groups that keep
         missing although the warm-up already is as long as a chunk (a circuit whose memory outlasts the chunks: every miss
         costs a sequential pass of its group) -> half as many chunks, twice the room; down to one chunk, which has no
         boundary to miss."""
@@ -567,12 +579,73 @@ class _LinResident:
             Lc = binding.lib().wdf_ss_nl_step_chunk_len(ent["T"], ent["k"])
             if delta >= 2 and w_snap >= min(w_max, Lc // 16 * 16) and ent["k"] > 1:
                 ent["k"] = max(1, ent["k"] // 2)
-                ent["ws"] = self._plan_nl(ent["B"], ent["T"], ent["k"], ent["ws"].device, cold_floor=4 * w_snap)
+                ent["ws"] = (plan or self._plan_nl)(ent["B"], ent["T"], ent["k"], ent["ws"].device, cold_floor=4 * w_snap)
                 ent["watch"], ent["replans"] = None, ent["replans"] + 1
                 return
         w["buf"].copy_(ent["ws"][:128].view(torch.int32), non_blocking=True)
         w["event"] = torch.cuda.Event()
         w["event"].record()
+
+    # ---- grad=False on a diode-pair root: the loss-only evaluation pass (csrc/wdf_ss_nl_eval.h) on entries of its own
+    @staticmethod
+    def _nl_eval_k(T, k):
+        """The chunk count the pass is called with: the chunks of wdf_ss_nl_step_chunk_len(T, k) that T really takes."""
+        return -(-T // binding.lib().wdf_ss_nl_step_chunk_len(T, max(1, k)))
+
+    def _plan_nl_eval(self, B, T, k, dev, cold_floor=0):
+        """Workspace of the evaluation pass for k chunks, planned as _plan_nl plans the step's."""
+        Lc = binding.lib().wdf_ss_nl_step_chunk_len(T, k)
+        cold = min(4096, max(self.cold_warmup(), int(cold_floor) // 16 * 16))
+        warm = max(16, min(Lc // 16 * 16, 64))
+        return binding.ss_nl_eval_plan(self.circ.ns, self.circ.ni, B, T, self._nl_eval_k(T, k), cold, warm, max(16, _NL_WMIN // 16 * 16),
+                                       max(16, Lc // 16 * 16), float(NL_TOL), torch.empty(0, device=dev))
+
+    def eval_entry(self, x, target):
+        """The buffers of one evaluated set: an entry of its own per (x, target) pair -- its own workspace (snapshot ring, warm-up
+        control, chunk count) and result rows; the training entry of the same pair is never touched.  One entry serves both
+        losses and every skip (the pass's sums are the same two); it holds no y until a call wants one."""
+        ent = self.cache.get((x, target), ("eval",))
+        if ent is None:
+            dev = self.pb.block.device
+            x_tm, tgt, B, T = self._resident_pair(x, target)
+            groups = -(-B // (128 if B % 2 == 0 else 64))         # (two sequences per lane when the rows pair up, on every tree)
+            k = max(1, min(T // 64, (_NL_EVAL_OCC * N_SIMD) // groups))
+            ws = self._plan_nl_eval(B, T, k, dev)
+            # a call's {mse, esr, mse + esr} in a row of its OWN, from a slab (entry()): a val_loss history stays what it was
+            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": None, "ws": ws,
+                                               "ring": torch.zeros((_ROWS, 4), dtype=torch.float32, device=dev),
+                                               "sums": torch.zeros(2, dtype=torch.float64, device=dev),
+                                               "turn": 0, "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0},
+                                 ("eval",), nbytes=_nbytes(x_tm, tgt, tgt, ws))
+        return ent
+
+    def evaluate(self, ent, kind, skip, store_output):
+        """probe + one evaluation pass -> the loss `kind` asks for ("mse": the mean squared error, else mse + esr) past skip, a view
+        into this call's own result row; the three terms {mse, esr, mse + esr} stay in ent["loss3"].  The
+        probe applies the optimizer updates queued since the last step (a validation call reads the parameters AFTER them);
+        the next training step's probe then finds none."""
+        circ = self.circ
+        self.check()
+        self.probe()
+        B, T = ent["B"], ent["T"]
+        if ent["turn"] >= ent["ring"].shape[0]:
+            ent["ring"], ent["turn"] = torch.zeros_like(ent["ring"]), 0
+        loss3 = ent["ring"][ent["turn"]][:3]
+        ent["turn"] += 1
+        y = self.output(ent) if store_output else None
+        rc = binding.lib().wdf_ss_nl_eval(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.pb.block), self.n_tree,
+                                          circ.ns, circ.ni, int(circ.root.N_up), int(circ.root.N_down), binding._ptr(ent["t"]), int(skip),
+                                          float(B * (T - int(skip))), ESR_EPS, binding._ptr(y), binding._ptr(ent["ws"]),
+                                          binding._ptr(ent["sums"]), binding._ptr(loss3), B, T, self._nl_eval_k(T, ent["k"]),
+                                          binding._stream())
+        binding._check(rc, "wdf_ss_nl_eval")
+        self._watch(ent, self._plan_nl_eval)
+        ent["loss3"] = loss3
+        return loss3[0 if kind == "mse" else 2]
+
+    def read_eval_ctl(self, ent):
+        """The evaluation entry's control block (the step's 32 words) as a dict -- synchronises."""
+        return binding.ss_nl_eval_read(ent["ws"])
 
     def cold_warmup(self):
         """Warm-up of a chunk that starts from z = 0 (the first call on a batch): outlasts the slowest mode of the step's
@@ -1041,8 +1114,8 @@ class Circuit:
 
     def _loss_no_grad(self, kind, x, target, skip, z0, carry_state, store_output):
         """mse() / mse_esr() with grad=False: the loss as a detached scalar.  The resident diode-pair clipper takes the loss-only
-        evaluation pass (EVAL_PASS_SERVES: DESIGN section 4), the resident MLP-root clipper its own (MLP_EVAL_PASS_SERVES); every
-        other circuit (and every stateful call) runs the default's code and the result is detached."""
+        evaluation pass (EVAL_PASS_SERVES: DESIGN section 4), the resident MLP-root clipper its own (MLP_EVAL_PASS_SERVES), a resident
+        diode-root tree with one or two states and sources its own (NL_EVAL_PASS_SERVES); every other circuit (and every stateful call) runs the default's code and the result is detached."""
         binding.require_gpu()
         tensors = isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)
         stateful = (z0 is not None or carry_state) and self.ns > 0
@@ -1053,6 +1126,15 @@ class Circuit:
             if (EVAL_PASS_SERVES and getattr(self, "_pblock", None) is not None and self._is_clipper() and self.root_kind == "DiodePair"
                     and 0 <= skip < int(x.shape[1])):
                 return self._eval_resident(x, target, kind, skip, store_output)
+            tree = getattr(self, "_tree", None)
+            if (NL_EVAL_PASS_SERVES and tree is not None and self.root_kind == "DiodePair" and 1 <= self.ns <= 2 and 1 <= self.ni <= 2
+                    and 0 <= skip < int(x.shape[1])):
+                # a resident diode-root tree: the loss-only pass on an entry of its own (csrc/wdf_ss_nl_eval.h)
+                with torch._C.DisableTorchFunctionSubclass():
+                    ent = tree.eval_entry(x, target)
+                    loss = tree.evaluate(ent, kind, int(skip), store_output)
+                self.last_output = ent["y"] if store_output else None
+                return loss.as_subclass(tf.Tensor)
         if kind == "mse":
             loss = self.mse(x, target, z0=z0, carry_state=carry_state, store_output=store_output)
         else:

@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -466,6 +466,36 @@ size_t wdf_ss_nl_step_esr_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_c
 int wdf_ss_nl_step_esr(const float* x, const float* coef, const float* params, const double* jac, int n_tree, int ns,
                        int ni, int n_up, int n_down, const float* target, int64_t skip, double eps, float* y, void* ws,
                        float* out, float* loss3_out, int64_t B, int64_t T, int n_chunks, void* stream);
+
+/* The LOSS-ONLY evaluation pass of the same trees (csrc/wdf_ss_nl_eval.h): the validation line of every epoch of
+ * clipper_pot.py:245-269 -- forward, S = sum (y - target)^2 and E = sum y^2 on the rows t >= skip, no gradient: no tangents,
+ * no chunk records, no jac, no out, no optimizer.  x [T][ni][B], target and y [T][B] as the step's; coef and params are the
+ * probe's outputs and the parameter block, both read only; the chunk length is wdf_ss_nl_step_chunk_len.
+ *   ws      wdf_ss_nl_eval_ws_bytes() bytes, planned by wdf_ss_nl_eval_plan (the step's arguments; cold_warmup a multiple of 8,
+ *           the other warm-ups multiples of 16): the control block (the step's 32 words with the step's meaning:
+ *           wdf_ss_nl_eval_read, w_used in multiples of 16 as run; wdf_ss_nl_eval_set: its fields 2..11, and 12: the secant switch, default on), the chunks'
+ *           boundary states, their {S, E}, and a RING OF SNAPSHOTS over the last three calls: the state in front of every 16th
+ *           step (0.25 bytes per sample and state).  Chunk k starts its warm-up from z = 0 on the first call, from the last
+ *           call's snapshot at that very sample on the second, and from the secant through the last two along the change of
+ *           {coefficients, L, V} afterwards; every boundary is verified (tol) and a group that missed is re-run from its
+ *           first missed boundary, so the start decides the speed, never the result.  The snapshots belong to the calls made
+ *           on this workspace: one per evaluated set, never the block a training step runs on.
+ *   Two launches: the chunk kernel, and a finish (one wave per group of sequences: verify, repair, reduce in a fixed order,
+ *   steer the warm-up, advance the ring) -- the same calls on the same history give the same bits.
+ *   y       [T][B], or NULL: the outputs are not stored -- 8 bytes per sample (x and the target in) instead of 12.
+ *   sums    device double[2] = {S, E} (E without eps), always written.
+ *   loss3   device float[3] = {S/n, sqrt(S/(E + eps)/n), their sum}, n = n_global; may be NULL.
+ * WDF_EINVAL before any HIP call: a null x / coef / params / target / ws / sums; ns or ni outside 1..2; skip outside [0, T);
+ * n_global <= 0; eps < 0; an n_chunks for which (K - 1) L < T <= K L does not hold; n_up or n_down < 1.  wdf_ss_nl_eval_ws_bytes:
+ * 0 on bad arguments, with wdf_last_error set.                                                                          */
+size_t wdf_ss_nl_eval_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+int wdf_ss_nl_eval_plan(void* ws, int ns, int ni, int64_t B, int64_t T, int n_chunks, int cold_warmup, int warm_warmup,
+                        int w_min, int w_max, float tol, void* stream);
+int wdf_ss_nl_eval_set(void* ws, int field, double value, void* stream);
+int wdf_ss_nl_eval_read(const void* ws, int32_t* ctl_out, void* stream);
+int wdf_ss_nl_eval(const float* x, const float* coef, const float* params, int n_tree, int ns, int ni, int n_up, int n_down,
+                   const float* target, int64_t skip, double n_global, double eps, float* y, void* ws, double* sums,
+                   float* loss3, int64_t B, int64_t T, int n_chunks, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The RESIDENT training step of the MLP-root pot clipper (csrc/wdf_mlp_step.h): what one epoch of
