@@ -219,6 +219,10 @@ for _fn in ("ws_bytes", "plan", "set", "read"):
     SIGNATURES["wdf_ss_nl_eval_" + _fn] = SIGNATURES["wdf_ss_nl_step_" + _fn]
 _nl = SIGNATURES["wdf_ss_nl_step_esr"][1]
 SIGNATURES["wdf_ss_nl_eval"] = (_ci, _nl[:3] + _nl[4:11] + [_cd, _cd, _p, _p, _p, _p, _i64, _i64, _ci, _p])
+# the linear trees' loss-only evaluation pass: the step's workspace arguments; x, coef, ns, ni, target, skip, n_global, eps_energy,
+# gscale, y, ws, sums, loss3, loss_out, B, T, n_chunks, z0, zT, stream
+SIGNATURES["wdf_ss_lin_eval_ws_bytes"] = (_sz, _STEP_WS)
+SIGNATURES["wdf_ss_lin_eval"] = (_ci, [_p, _p, _ci, _ci, _p, _i64, _cd, _cd, _cf, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p, _p, _p])
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
@@ -1735,6 +1739,52 @@ def ss_nl_eval(x_tm, coef, params, n_tree, ns, ni, target, n_chunks, ws, skip=0,
     _check(lib().wdf_ss_nl_eval(_ptr(x_tm), _ptr(coef), _ptr(params), n_tree, ns, ni, int(n_up), int(n_down), _ptr(target), skip, n_global,
                                 float(eps), _ptr(y), _ptr(ws), _ptr(sums), _ptr(loss3), B, T, int(n_chunks), _stream()), "wdf_ss_nl_eval")
     return {"y": y, "sums": sums, "loss3": loss3, "ws": ws}
+
+
+def ss_lin_eval(x_tm, coef, target, n_chunks, skip=0, n_global=None, eps=ESR_EPS, gscale=None, z0=None, want_zT=False, ws=None, y=None,
+                store_y=True, sums=None, loss3=None, loss=None):
+    """The loss-only evaluation pass of a LINEAR tree (wdf_ss_lin_eval, csrc/wdf_ss_lin_eval.h): forward and the two loss sums on
+    the rows t >= skip, no gradient -- no jac, no out, no optimizer.  x_tm, coef, target, n_chunks, z0 / want_zT and the buffers as
+    ss_lin_step_esr's (at the same n_chunks and addresses' alignment the results are that step's bit for bit); ws: zeroed
+    wdf_ss_lin_eval_ws_bytes() bytes when not given (the pass leaves it clean; one workspace serves storing and no-y calls).
+    gscale: None -> 2 / (B T), the mean squared error in `loss`.  store_y=False: y is never stored or allocated (None in the dict),
+    a y= handed in is refused; a y of another shape than [T,B] or on another device than x_tm is refused here, before anything runs.
+    -> dict: y [T,B] | None, sums [2] float64 = {S, E}, loss3 [3] = {mse, esr, mse + esr} with n = n_global (None: B (T - skip)),
+    loss (0-dim) = gscale/2 x S, zT [ns,B] | None, ws."""
+    _no_y("ss_lin_eval", y, store_y)
+    if y is not None:
+        want = (int(x_tm.shape[0]), int(x_tm.shape[2])) if isinstance(x_tm, torch.Tensor) and x_tm.dim() == 3 else None
+        if not isinstance(y, torch.Tensor) or want is None or tuple(y.shape) != want or y.device != x_tm.device:
+            raise WdfHipError(f"ss_lin_eval: y must be a [T,B] = {list(want) if want else '[T,B]'} tensor on x_tm's device, got "
+                              f"{tuple(getattr(y, 'shape', ()))} on {getattr(y, 'device', None)}")
+    require_gpu()
+    x_tm, coef, target, z0 = _f32_dev(x_tm, "x_tm"), _f32_dev(coef, "coef"), _f32_dev(target, "target"), _f32_dev(z0, "z0")
+    ns, ni, B, T, _ = _lin_step_shape(x_tm, coef, "ss_lin_eval")
+    if tuple(target.shape) != (T, B):
+        raise WdfHipError(f"target must be [T,B] = [{T},{B}]")
+    if ns > 0 and z0 is not None and tuple(z0.shape) != (ns, B):
+        raise WdfHipError(f"z0 must be [ns,B] = [{ns},{B}]")
+    skip = int(skip)
+    if not 0 <= skip < T:
+        raise WdfHipError(f"ss_lin_eval: skip must be in [0, T) = [0, {T}), got {skip}")
+    n_global = float(B * (T - skip)) if n_global is None else float(n_global)
+    if not n_global > 0.0 or not float(eps) >= 0.0:
+        raise WdfHipError("ss_lin_eval: n_global > 0 and eps >= 0")
+    gscale = 2.0 / (B * T) if gscale is None else float(gscale)
+    y, zT = _y_zT(y, want_zT and ns > 0, T, B, x_tm, ns, store_y)
+    need = lib().wdf_ss_lin_eval_ws_bytes(ns, ni, B, T, int(n_chunks))
+    if need == 0:
+        raise WdfHipError(lib().wdf_last_error().decode() or "wdf_ss_lin_eval_ws_bytes: bad arguments")
+    ws = _ws(ws, need, x_tm, zeroed=True)
+    if sums is None:
+        sums = torch.empty((2,), dtype=torch.float64, device=x_tm.device)
+    elif not (isinstance(sums, torch.Tensor) and sums.is_cuda and sums.dtype == torch.float64 and sums.numel() == 2 and sums.is_contiguous()):
+        raise WdfHipError("sums must hold {S, E} (2 doubles) on the GPU")
+    loss3 = _out(loss3, 3, "loss3", "{mse, esr, mse + esr}", x_tm)
+    loss = torch.empty((), dtype=torch.float32, device=x_tm.device) if loss is None else _out(loss, 1, "loss", "gscale/2 x S", x_tm)
+    _check(lib().wdf_ss_lin_eval(_ptr(x_tm), _ptr(coef), ns, ni, _ptr(target), skip, n_global, float(eps), gscale, _ptr(y), _ptr(ws),
+                                 _ptr(sums), _ptr(loss3), _ptr(loss), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()), "wdf_ss_lin_eval")
+    return {"y": y, "sums": sums, "loss3": loss3, "loss": loss, "zT": zT, "ws": ws}
 
 
 def ss_lin_esr_finish(sums, n_global, eps=ESR_EPS, g=None, loss3=None):

@@ -56,6 +56,19 @@ MLP_EVAL_PASS_SERVES = True
 # Decided by tools/ss_nl_eval_bench.py (profiles/ss_nl_eval_pass.jsonl): the storing pass is below the MSE step
 # and below the composed MSE + ESR route, each by more than the other's own min-max spread, at both shapes.
 NL_EVAL_PASS_SERVES = True
+# grad=False on a resident LINEAR tree: the loss-only evaluation pass (csrc/wdf_ss_lin_eval.h) instead of the one-pass training step.
+# True only if tools/ss_lin_eval_bench.py shows the storing pass below the MSE step and below the MSE + ESR step at both shapes, each
+# by more than the compared step's own min-max spread (profiles/ss_lin_eval_pass.jsonl).  _LinResident.evaluate
+# reaches the pass either way.
+# Measured on one MI355X, RC low-pass, ms per call, median [min-max] over 20 rounds of 5 calls:
+#   8192 x 4096: MSE step 0.1165 [0.1151-0.1191], MSE + ESR step 0.1251 [0.1233-0.1284], the pass storing y 0.1174 [0.1167-0.1191],
+#                without y 0.0959 [0.0949-0.0983]
+#   1340 x 2048: MSE step 0.0481 [0.0470-0.0835], MSE + ESR step 0.0502 [0.0497-0.0591], the pass storing y 0.0417 [0.0408-0.0424],
+#                without y 0.0392 [0.0377-0.0419]
+# At 8192 x 4096 the storing pass is NOT below the MSE step: both move 16 B/sample at 4.6 TB/s, and on this one-capacitor tree the
+# step's tangents hide under its memory time.  Below the MSE + ESR step by 0.008 ms there (its spread: 0.005); at 1340 x 2048 below
+# both steps' medians by 13 % and 17 %, inside their spreads.  Hence False: grad=False runs the step and detaches, as before.
+LIN_EVAL_PASS_SERVES = False
 
 
 def plan_ss_time_parallel(coef64, ns, ni, root_kind, B, T, tol=1.0e-6):
@@ -383,6 +396,9 @@ _NL_WMIN = int(os.environ.get("WDF_NL_WMIN", "16"))      # the shortest warm-up 
 # chunk waves per SIMD of the diode-root evaluation pass: 1, as the step (the fastest of the sweep over 1, 2, 4 at 8192 x 4096;
 # at 1340 x 2048 the 64-step floor of a chunk caps the count before it matters: DESIGN section 4)
 _NL_EVAL_OCC = int(os.environ.get("WDF_NL_EVAL_OCC", str(_NL_OCC)))
+# chunk waves per SIMD of the linear trees' evaluation pass: the step's, and it has to stay the step's by default -- the chunk
+# count decides the bits (the order of the sums, where the walk rounds), and grad=False must report what the default reports
+_LIN_EVAL_OCC = int(os.environ.get("WDF_LIN_EVAL_OCC", str(_LIN_OCC)))
 _ROWS = 1024                                             # result rows per slab (see _LinResident.entry)
 NL_TOL = 1.0e-6                                          # boundary tolerance of the diode-root one-pass step (plan_ss_time_parallel's)
 ESR_EPS = float(np.finfo(float).eps)                     # what the scripts' esr_loss adds to the energy (clipper_pot.py:146-156)
@@ -605,6 +621,22 @@ class _LinResident:
         control, chunk count) and result rows; the training entry of the same pair is never touched.  One entry serves both
         losses and every skip (the pass's sums are the same two); it holds no y until a call wants one."""
         ent = self.cache.get((x, target), ("eval",))
+        if ent is None and self.circ.root_kind != "DiodePair":
+            # a linear tree (csrc/wdf_ss_lin_eval.h): the training entry's chunk formula, a zeroed workspace of the pass's own size
+            # (the ticket, the chunks' zero-state ends, two partial sums per wave), result rows {mse, esr, mse + esr, mse by gscale}
+            circ, dev = self.circ, self.pb.block.device
+            x_tm, tgt, B, T = self._resident_pair(x, target)
+            per_wave = 128 if B % 2 == 0 else 64
+            k = max(1, min(T // 64, (_LIN_EVAL_OCC * N_SIMD) // max(1, -(-B // per_wave))))
+            nbytes = binding.lib().wdf_ss_lin_eval_ws_bytes(circ.ns, circ.ni, B, T, k)
+            if nbytes == 0:
+                raise binding.WdfHipError(binding.lib().wdf_last_error().decode() or "wdf_ss_lin_eval_ws_bytes: unsupported tree")
+            ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": None, "ws": ws,
+                                               "ring": torch.zeros((_ROWS, 4), dtype=torch.float32, device=dev),
+                                               "sums": torch.zeros(2, dtype=torch.float64, device=dev),
+                                               "turn": 0, "B": B, "T": T, "k": k, "zT": None},
+                                 ("eval",), nbytes=_nbytes(x_tm, tgt, tgt, ws))
         if ent is None:
             dev = self.pb.block.device
             x_tm, tgt, B, T = self._resident_pair(x, target)
@@ -619,17 +651,39 @@ class _LinResident:
                                  ("eval",), nbytes=_nbytes(x_tm, tgt, tgt, ws))
         return ent
 
-    def evaluate(self, ent, kind, skip, store_output):
+    def evaluate(self, ent, kind, skip, store_output, z0=None, want_zT=False):
         """probe + one evaluation pass -> the loss `kind` asks for ("mse": the mean squared error, else mse + esr) past skip, a view
         into this call's own result row; the three terms {mse, esr, mse + esr} stay in ent["loss3"].  The
         probe applies the optimizer updates queued since the last step (a validation call reads the parameters AFTER them);
-        the next training step's probe then finds none."""
+        the next training step's probe then finds none.  A linear tree (wdf_ss_lin_eval): kind "mse" is skip 0 with the MSE
+        step's gscale = 2 / (B T) and its loss_out formula, else n = B (T - skip) and loss3[2] -- the numbers the training steps
+        report; z0 [ns,B] / want_zT as in step(), the final states in ent["zT"] (one of two buffers of the eval entry's own)."""
         circ = self.circ
         self.check()
         self.probe()
         B, T = ent["B"], ent["T"]
         if ent["turn"] >= ent["ring"].shape[0]:
             ent["ring"], ent["turn"] = torch.zeros_like(ent["ring"]), 0
+        if circ.root_kind != "DiodePair":
+            row = ent["ring"][ent["turn"]]
+            ent["turn"] += 1
+            zT = None
+            if want_zT and circ.ns > 0:
+                bufs = ent.setdefault("zT_bufs", [torch.empty((circ.ns, B), dtype=torch.float32, device=ent["t"].device) for _ in range(2)])
+                zT = bufs[0] if (z0 is None or z0.data_ptr() != bufs[0].data_ptr()) else bufs[1]
+            ent["zT"] = zT
+            y = self.output(ent) if store_output else None
+            mse = kind == "mse"
+            skip = 0 if mse else int(skip)
+            at = row.data_ptr()
+            rc = binding.lib().wdf_ss_lin_eval(binding._ptr(ent["x"]), binding._ptr(self.coef), circ.ns, circ.ni, binding._ptr(ent["t"]),
+                                               skip, float(B * (T - skip)), ESR_EPS, 2.0 / float(B * T), binding._ptr(y),
+                                               binding._ptr(ent["ws"]), binding._ptr(ent["sums"]), ctypes.c_void_p(at),
+                                               ctypes.c_void_p(at + 12), B, T, ent["k"], None if z0 is None else binding._ptr(z0),
+                                               None if zT is None else binding._ptr(zT), binding._stream())
+            binding._check(rc, "wdf_ss_lin_eval")
+            ent["loss3"] = row[:3]
+            return row[3 if mse else 2]
         loss3 = ent["ring"][ent["turn"]][:3]
         ent["turn"] += 1
         y = self.output(ent) if store_output else None
@@ -1115,7 +1169,10 @@ class Circuit:
     def _loss_no_grad(self, kind, x, target, skip, z0, carry_state, store_output):
         """mse() / mse_esr() with grad=False: the loss as a detached scalar.  The resident diode-pair clipper takes the loss-only
         evaluation pass (EVAL_PASS_SERVES: DESIGN section 4), the resident MLP-root clipper its own (MLP_EVAL_PASS_SERVES), a resident
-        diode-root tree with one or two states and sources its own (NL_EVAL_PASS_SERVES); every other circuit (and every stateful call) runs the default's code and the result is detached."""
+        diode-root tree with one or two states and sources its own (NL_EVAL_PASS_SERVES), a resident linear tree its own
+        (LIN_EVAL_PASS_SERVES: csrc/wdf_ss_lin_eval.h, calls with z0 / carry_state included -- the pass takes the state in and hands
+        it out as the step does, and its numbers are the step's bit for bit); every other circuit (and every other stateful call)
+        runs the default's code and the result is detached."""
         binding.require_gpu()
         tensors = isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)
         stateful = (z0 is not None or carry_state) and self.ns > 0
@@ -1135,6 +1192,24 @@ class Circuit:
                     loss = tree.evaluate(ent, kind, int(skip), store_output)
                 self.last_output = ent["y"] if store_output else None
                 return loss.as_subclass(tf.Tensor)
+        lin = getattr(self, "_lin", None)
+        if LIN_EVAL_PASS_SERVES and lin is not None and tensors and x.dim() >= 2 and 0 <= skip < int(x.shape[1]):
+            # a resident linear tree: the loss-only pass on an entry of its own (csrc/wdf_ss_lin_eval.h), stateful calls included --
+            # z0 / carry_state are the pass's own z0 / zT, as they are the step's in _mse / _mse_esr_lin_step
+            if carry_state and z0 is None:
+                z0 = getattr(self, "last_state", None)
+            if self.ns == 0:
+                stateful, z0 = False, None                        # (no capacitor: nothing to carry)
+            with torch._C.DisableTorchFunctionSubclass():
+                ent = lin.eval_entry(x, target)
+                z0d = None
+                if z0 is not None:
+                    z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["t"].device).float().reshape(self.ns, ent["B"]).contiguous()
+                loss = lin.evaluate(ent, kind, int(skip), store_output, z0d, bool(stateful))
+            self.last_output = ent["y"] if store_output else None
+            if stateful:
+                self.last_state = ent["zT"].clone()              # (ent["zT"] is one of two ping-pong buffers: kept by value)
+            return loss.as_subclass(tf.Tensor)
         if kind == "mse":
             loss = self.mse(x, target, z0=z0, carry_state=carry_state, store_output=store_output)
         else:
@@ -1215,7 +1290,9 @@ class Circuit:
         which is what clipper_pot.py:110-111 does before every forward).
         store_output=False: as in mse() -- "I will not read y"; `circ.last_output` is None after the call.
         grad=False: as in mse() -- "I will not differentiate this loss" (the validation line, clipper_pot.py:262-264); a
-        resident MLP-root clipper then runs its forward and the two loss sums only (no reverse sweep, no weight gradient)."""
+        resident MLP-root clipper then runs its forward and the two loss sums only (no reverse sweep, no weight gradient); a
+        resident linear tree has a loss-only evaluation pass of its own (csrc/wdf_ss_lin_eval.h: the step without tangents and
+        Jacobian, the same bits; z0 / carry_state included), taken where LIN_EVAL_PASS_SERVES says the measurement allows it."""
         if not grad:
             return self._loss_no_grad("mse+esr", x, target, int(skip), z0, carry_state, bool(store_output))
         loss = self._mse_esr(x, target, skip, z0, carry_state, bool(store_output))
@@ -1446,8 +1523,10 @@ class Circuit:
         detached in every case (`requires_grad` False, no gradient attached).  A resident diode-pair clipper then runs the
         loss-only evaluation pass (csrc/wdf_clipper_eval.h: forward and the loss sums, no tangent, no gradient) on an entry of
         its own per (x, target) pair -- its own stepper, workspace and warm-start state; a training entry on the same pair is not
-        touched; every other circuit computes exactly as with the default and detaches the result.  grad=True runs the code
-        it always ran; torch.no_grad() routes nothing."""
+        touched; a resident linear tree has its own pass too (csrc/wdf_ss_lin_eval.h: forward and the two loss sums in the
+        step's chunks, bit for bit the step's loss, y and final state, with z0 / carry_state as the step takes them; an entry of
+        its own per pair; taken where LIN_EVAL_PASS_SERVES says the measurement allows it); every other circuit computes exactly
+        as with the default and detaches the result.  grad=True runs the code it always ran; torch.no_grad() routes nothing."""
         if not grad:
             return self._loss_no_grad("mse", x, target, 0, z0, carry_state, bool(store_output))
         loss = self._mse(x, target, z0, carry_state, bool(store_output))

@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too; + wdf_ss_lin_eval(_ws_bytes), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -421,6 +421,28 @@ int wdf_ss_lin_step_esr_noy(const float* x, const float* coef, const double* jac
                             const float* z0, float* zT, void* stream);
 int wdf_ss_lin_esr_finish(const float* sums, int n_params, double n_global, double eps_energy, float* g, float* loss3,
                           void* stream);
+/* The LOSS-ONLY evaluation pass of the same linear trees (csrc/wdf_ss_lin_eval.h; additions to ABI 6): the validation line of an
+ * epoch -- forward, S = sum (y - target)^2 and E = sum y^2 on the rows t >= skip, no gradient: no tangents, no jac, no out, no
+ * optimizer.  The step's two passes on z alone (every chunk but the last from z = 0; then every chunk from its exact start, the
+ * wave building A^L and walking the earlier chunks' ends itself), the step's own expressions in the step's order: at the same
+ * n_chunks, lane width and alignment y, zT, (float)S, (float)E and loss3 are BIT FOR BIT what wdf_ss_lin_step_esr writes, and at
+ * skip = 0 *loss_out is wdf_ss_lin_step_mse's.  x [T][ni][B], coef (wdf_ss_probe's float32 output), target and y [T][B], z0 / zT
+ * [ns][B] or NULL and n_chunks as the step's; ns 0..2, ni 1..2.
+ *   y         [T][B], or NULL: the kernels without the y store run -- 12 B/sample instead of 16, no address formed from y.
+ *   ws        wdf_ss_lin_eval_ws_bytes() bytes, ZERO before the first call; the pass leaves it clean (its ticket at 0).  One
+ *             workspace may serve storing and no-y calls in turn.
+ *   sums      device double[2] = {S, E} (E without eps), or NULL.
+ *   loss3     device float[3] = {S/n, sqrt(S/(E + eps_energy)/n), their sum}, n = n_global, or NULL.
+ *   loss_out  device float <- (float)(0.5 gscale S): the mean squared error when gscale = 2 / (B T) and skip = 0, or NULL.
+ *             sums, loss3 and loss_out must not all be NULL.
+ * Two sequences per lane when B is even and x, target, y, z0, zT and ws are 8-byte aligned (the step's rule).
+ * WDF_EINVAL before any device work: a null x / coef / target / ws; all three outputs null; ns outside 0..2 or ni outside 1..2;
+ * B, T or n_chunks < 1; skip outside [0, T); n_global <= 0; eps_energy < 0; zT aliasing z0.  wdf_ss_lin_eval_ws_bytes: 0 on bad
+ * arguments, with wdf_last_error set. */
+size_t wdf_ss_lin_eval_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+int wdf_ss_lin_eval(const float* x, const float* coef, int ns, int ni, const float* target, int64_t skip, double n_global,
+                    double eps_energy, float gscale, float* y, void* ws, double* sums, float* loss3, float* loss_out,
+                    int64_t B, int64_t T, int n_chunks, const float* z0, float* zT, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The one-pass MSE training step of small trees with a DIODE-PAIR root (csrc/wdf_ss_nl_step.h): the same epoch
