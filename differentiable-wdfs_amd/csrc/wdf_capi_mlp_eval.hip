@@ -1,5 +1,6 @@
 // wdf_capi_mlp_eval.hip -- C ABI of the MLP-root pot clipper's loss-only evaluation pass (csrc/wdf_mlp_eval.h): argument
-// checking, template dispatch and the four launches of wdf_clipper_mlp_eval.  The state block is the training step's
+// checking, template dispatch and the four launches of wdf_clipper_mlp_eval (three of the step's forward kernel under the pass's
+// tag, MlpEvalPass<STORE_Y>, then the finish).  The state block is the training step's
 // (wdf_capi_mlp_step_layout.h: one layout walk for both).  A translation unit of its own: it compiles beside the step's.
 #include "wdf_capi_mlp_step_layout.h"
 #include "wdf_mlp_eval.h"
@@ -14,10 +15,10 @@ void launch_mlp_eval(const wdf::MlpStepArgs& A, int n_items, int n_cols, double 
     const dim3 items((unsigned)((n_items + 3) / 4)), cols((unsigned)((n_cols + 3) / 4));
     {
         EventBracket bracket(s);
-        hipLaunchKernelGGL((wdf::mlp_eval_fwd_kernel<NL, DYN_R, ACT, 0, STORE_Y>), items, dim3(256), 0, s, A);
+        hipLaunchKernelGGL((wdf::mlp_step_fwd_kernel<NL, DYN_R, ACT, 0, wdf::MlpEvalPass<STORE_Y>>), items, dim3(256), 0, s, A);
     }
-    hipLaunchKernelGGL((wdf::mlp_eval_fwd_kernel<NL, DYN_R, ACT, 1, STORE_Y>), items, dim3(256), 0, s, A);
-    hipLaunchKernelGGL((wdf::mlp_eval_fwd_kernel<NL, DYN_R, ACT, 2, STORE_Y>), cols, dim3(256), 0, s, A);
+    hipLaunchKernelGGL((wdf::mlp_step_fwd_kernel<NL, DYN_R, ACT, 1, wdf::MlpEvalPass<STORE_Y>>), items, dim3(256), 0, s, A);
+    hipLaunchKernelGGL((wdf::mlp_step_fwd_kernel<NL, DYN_R, ACT, 2, wdf::MlpEvalPass<STORE_Y>>), cols, dim3(256), 0, s, A);
     hipLaunchKernelGGL(wdf::mlp_eval_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)A.colsum, n_cols, n_global, eps_energy, sums,
                        loss3, A.ctl);
 }

@@ -252,16 +252,11 @@ struct StepSpan {
     float z;
 };
 
-// One block of 16 steps.  OWNED: outputs, kappa, loss sums, the block's adjoint map; otherwise a warm-up block: state only.
-// Straight-line code (the whole block is one basic block): the scheduler places step i's kappa chain beside step i + 1's
-// forward chain -- they are independent.
-template <int NL, bool DYN_R, int ACT, bool OWNED>
-__device__ __forceinline__ void mlp_step_block(const MlpStepArgs& A, const StepWeights<NL>& Wt, const MlpClipConsts& c, int64_t tb,
-                                               int col, int64_t b, bool live, int g, const float* __restrict__ xp,
-                                               const float* __restrict__ pp, const float* __restrict__ lp, StepSpan& sp)
+// a block's 16 input samples (and, DYN_R, its 16 p and lr): four 16-byte loads per array
+template <bool DYN_R>
+__device__ __forceinline__ void step_load_inputs(const float* __restrict__ xp, const float* __restrict__ pp, const float* __restrict__ lp,
+                                                 int64_t tb, float (&xs)[16], float (&ps)[16], float (&ls)[16])
 {
-    const int64_t B = A.B;
-    float xs[16], ps[16], ls[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float4 xv = *reinterpret_cast<const float4*>(xp + tb + 4 * q);
@@ -273,6 +268,27 @@ __device__ __forceinline__ void mlp_step_block(const MlpStepArgs& A, const StepW
             ls[4 * q] = lv.x; ls[4 * q + 1] = lv.y; ls[4 * q + 2] = lv.z; ls[4 * q + 3] = lv.w;
         }
     }
+}
+
+// The chunked forward serves two passes, and a pass is a tag type: it selects the 16-step block (an overload of mlp_step_block
+// on the tag) and says where a repair finds the OLD state before step tb + 16 (mlp_step_fwd_kernel's MODE 1).  This is the
+// training step's; the evaluation pass's is wdf_mlp_eval.h's MlpEvalPass.
+struct MlpTrainPass {
+    static __device__ __forceinline__ float old_state(const MlpStepArgs& A, const float*, int64_t tb, int64_t b)
+    { return A.zstash[(tb + 16) * A.B + b]; }
+};
+
+// One block of 16 steps.  OWNED: outputs, kappa, loss sums, the block's adjoint map; otherwise a warm-up block: state only.
+// Straight-line code (the whole block is one basic block): the scheduler places step i's kappa chain beside step i + 1's
+// forward chain -- they are independent.
+template <int NL, bool DYN_R, int ACT, bool OWNED>
+__device__ __forceinline__ void mlp_step_block(MlpTrainPass, const MlpStepArgs& A, const StepWeights<NL>& Wt, const MlpClipConsts& c,
+                                               int64_t tb, int col, int64_t b, bool live, int g, const float* __restrict__ xp,
+                                               const float* __restrict__ pp, const float* __restrict__ lp, StepSpan& sp)
+{
+    const int64_t B = A.B;
+    float xs[16], ps[16], ls[16];
+    step_load_inputs<DYN_R>(xp, pp, lp, tb, xs, ps, ls);
     float tt[4] = {0.0f, 0.0f, 0.0f, 0.0f};                     // group g looks after the steps i = g (mod 4)
     if constexpr (OWNED) {
 #pragma unroll
@@ -333,8 +349,8 @@ __device__ __forceinline__ void mlp_step_block(const MlpStepArgs& A, const StepW
 }
 
 // One span of one column: steps [tw, t0) warm up, [t0, t1) are owned (outputs written).  Returns the end state.
-// snap_w: the snapshot set this call writes.  PUBLISH: boundary data for a verifier in the same launch.
-template <int NL, bool DYN_R, int ACT, bool PUBLISH>
+// snap_w: the snapshot set this call writes.  PUBLISH: boundary data for a verifier in the same launch.  P: the pass.
+template <int NL, bool DYN_R, int ACT, bool PUBLISH, class P>
 __device__ __forceinline__ float mlp_step_span(const MlpStepArgs& A, const StepWeights<NL>& Wt, const MlpClipConsts& c,
                                                int item, int col, int64_t tw, int64_t t0, int64_t t1, float z,
                                                float* __restrict__ snap_w)
@@ -351,16 +367,17 @@ __device__ __forceinline__ float mlp_step_span(const MlpStepArgs& A, const StepW
     for (int64_t tb = tw; tb < t0; tb += 16) {                   // ---- warm-up blocks
         const int64_t j = (t0 - tb) >> 4;                        // 16-step units before the first owned step
         if (g == 0 && j <= kStepPre) step_publish(A.zpre + ((int64_t)item * kStepPre + (j - 1)) * 16 + n, sp.z);
-        mlp_step_block<NL, DYN_R, ACT, false>(A, Wt, c, tb, col, b, live, g, xp, pp, lp, sp);
+        mlp_step_block<NL, DYN_R, ACT, false>(P{}, A, Wt, c, tb, col, b, live, g, xp, pp, lp, sp);
     }
     if (g == 0) {
         if constexpr (PUBLISH) step_publish(A.zwarm + (int64_t)item * 16 + n, sp.z);
         else A.zwarm[(int64_t)item * 16 + n] = sp.z;
     }
     for (int64_t tb = t0; tb < t1; tb += 16) {                   // ---- owned blocks
-        // the state a later call may start from (and this call's verifier compares shorter warm-ups against)
+        // the state a later call may start from; this call's verifier compares shorter warm-ups against it, and the evaluation
+        // pass's MODE 1 holds a re-run chunk against it
         if (g == 0 && live) step_publish(snap_w + (tb >> 4) * B + b, sp.z);
-        mlp_step_block<NL, DYN_R, ACT, true>(A, Wt, c, tb, col, b, live, g, xp, pp, lp, sp);
+        mlp_step_block<NL, DYN_R, ACT, true>(P{}, A, Wt, c, tb, col, b, live, g, xp, pp, lp, sp);
     }
     return sp.z;
 }
@@ -386,7 +403,9 @@ __device__ __forceinline__ void mlp_step_column_loss(const MlpStepArgs& A, int c
 // Workgroups are FOUR waves (four items; MODE 2: four columns): the dispatcher spreads a workgroup's waves over the four
 // SIMDs of its CU, whereas single-wave workgroups land wherever the previous kernel left each CU's SIMD pointer -- with
 // one wave per SIMD wanted, 30 doubled-up SIMDs of 1024 cost the forward +55 % (tools/mlp_step_placement.py).
-template <int NL, bool DYN_R, int ACT, int MODE>
+// P: the pass (MlpTrainPass; MlpEvalPass<STORE_Y>: A.zstash, A.kappa and A.maps are null and never looked at, A.y is null
+// when !STORE_Y).
+template <int NL, bool DYN_R, int ACT, int MODE, class P = MlpTrainPass>
 __global__ __launch_bounds__(256) void mlp_step_fwd_kernel(const MlpStepArgs A)
 {
     const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
@@ -404,7 +423,6 @@ __global__ __launch_bounds__(256) void mlp_step_fwd_kernel(const MlpStepArgs A)
     int* st = ctl->status[ctl->call & 1];
     if constexpr (MODE == 2) {
         const int col = unit;
-        if (A.colseq[col] == 0u) return;
         const MlpStepCol cinfo = A.cols[col];
         const MlpClipConsts c = DYN_R ? MlpClipConsts{} : mlp_load_consts(A.theta2, A.fs);
         const StepWeights<NL> Wt = step_load_weights<NL, ACT>(A.w, A.H, lane);
@@ -412,7 +430,7 @@ __global__ __launch_bounds__(256) void mlp_step_fwd_kernel(const MlpStepArgs A)
         float z = 0.0f;                                            // reset(): clipper_pot.py:110-111
         for (int k = 0; k < cinfo.K; ++k) {
             const MlpStepItem it = A.items[cinfo.first + k];
-            z = mlp_step_span<NL, DYN_R, ACT, false>(A, Wt, c, cinfo.first + k, col, it.t0, it.t0, it.t1, z, snap_w);
+            z = mlp_step_span<NL, DYN_R, ACT, false, P>(A, Wt, c, cinfo.first + k, col, it.t0, it.t0, it.t1, z, snap_w);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         mlp_step_column_loss(A, col);
@@ -431,10 +449,6 @@ __global__ __launch_bounds__(256) void mlp_step_fwd_kernel(const MlpStepArgs A)
                 int* nx = ctl->status[(ctl->call + 1) & 1];
                 nx[0] = 0; nx[1] = 0; nx[2] = 0; nx[3] = 0;
             }
-        } else {
-            if (A.flag[item] == 0u) return;
-        }
-        if constexpr (MODE == 0) {
             if (lane == 0) {
                 A.hwid[2 * item] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));       // HW_REG_HW_ID
                 A.hwid[2 * item + 1] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
@@ -454,15 +468,21 @@ __global__ __launch_bounds__(256) void mlp_step_fwd_kernel(const MlpStepArgs A)
                 tw = it.t0 > W ? it.t0 - W : 0;
                 z = (warm && tw > 0) ? snap_r[(tw >> 4) * A.B + b] : 0.0f;
             }
-            z = mlp_step_span<NL, DYN_R, ACT, true>(A, Wt, c, item, it.col, tw, it.t0, it.t1, z, snap_w);
+            z = mlp_step_span<NL, DYN_R, ACT, true, P>(A, Wt, c, item, it.col, tw, it.t0, it.t1, z, snap_w);
             if (g == 0) step_publish(A.zend + (int64_t)item * 16 + n, z);
         } else {
             // The repair: the flagged chunk again from the state its predecessor ended in -- but only as far as it takes:
-            // after every block the new state is held against the OLD trajectory (the stash row of the next step, still
-            // untouched); once they agree to repair_at x tol the rest of the chunk stands (a miss of a few tol is forgotten within
+            // after every block the new state is held against the OLD trajectory (P::old_state: the old state before step
+            // tb + 16); once they agree to repair_at x tol the rest of the chunk stands (a miss of a few tol is forgotten within
             // a few dozen steps).  A chunk that reaches its end still off by more than that carries on into its successor's
             // steps -- unless the successor is being re-run itself (from a state that is now stale): then the column goes
             // sequential.
+            // Where the old state comes from: the training step reads the stash row of step tb + 16, still untouched (the block
+            // that rewrites it runs in the next iteration).  The evaluation pass has no stash; it reads row (tb + 16) / 16 of
+            // the snapshot set this call writes: MODE 0 published the state before every owned block there -- the same number.
+            // The row is read BEFORE this loop publishes over it (row tb now, row tb + 16 in the next iteration), and nobody else
+            // writes it: the chunk that owns it is either not flagged (it does not run in this launch) or, if it is, this wave stops
+            // at its boundary (the column goes sequential).  At a chunk's end the reference is the recorded end state, for both.
             const float* __restrict__ xp = A.x + b * A.T;
             const float* __restrict__ pp = DYN_R ? A.p + b * A.T : nullptr;
             const float* __restrict__ lp = DYN_R ? A.lr + b * A.T : nullptr;
@@ -478,10 +498,9 @@ __global__ __launch_bounds__(256) void mlp_step_fwd_kernel(const MlpStepArgs A)
                     t_end = A.items[cur].t1;
                 }
                 if (g == 0 && live) step_publish(snap_w + (tb >> 4) * A.B + b, sp.z);
-                const float z_old_next = (tb + 16 < A.T) ? A.zstash[(tb + 16) * A.B + b] : sp.z;
+                const float z_old_next = (tb + 16 < A.T) ? P::old_state(A, snap_w, tb, b) : sp.z;
                 const float z_end_old = A.zend[(int64_t)cur * 16 + n];
-                mlp_step_block<NL, DYN_R, ACT, true>(A, Wt, c, tb, it.col, b, live, g, xp, pp, lp, sp);
-                // (the stash row of step tb + 16 holds the state BEFORE that step; at a chunk's end the recorded end state)
+                mlp_step_block<NL, DYN_R, ACT, true>(P{}, A, Wt, c, tb, it.col, b, live, g, xp, pp, lp, sp);
                 const float ref = (tb + 16 == t_end) ? z_end_old : z_old_next;
                 const bool off = live && !(fabsf(sp.z - ref) <= eps_c);
                 if (tb + 16 < A.T && __ballot(off) == 0ull) break;

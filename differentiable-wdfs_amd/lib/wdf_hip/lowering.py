@@ -621,33 +621,26 @@ class _LinResident:
         control, chunk count) and result rows; the training entry of the same pair is never touched.  One entry serves both
         losses and every skip (the pass's sums are the same two); it holds no y until a call wants one."""
         ent = self.cache.get((x, target), ("eval",))
-        if ent is None and self.circ.root_kind != "DiodePair":
-            # a linear tree (csrc/wdf_ss_lin_eval.h): the training entry's chunk formula, a zeroed workspace of the pass's own size
-            # (the ticket, the chunks' zero-state ends, two partial sums per wave), result rows {mse, esr, mse + esr, mse by gscale}
-            circ, dev = self.circ, self.pb.block.device
-            x_tm, tgt, B, T = self._resident_pair(x, target)
-            per_wave = 128 if B % 2 == 0 else 64
-            k = max(1, min(T // 64, (_LIN_EVAL_OCC * N_SIMD) // max(1, -(-B // per_wave))))
-            nbytes = binding.lib().wdf_ss_lin_eval_ws_bytes(circ.ns, circ.ni, B, T, k)
-            if nbytes == 0:
-                raise binding.WdfHipError(binding.lib().wdf_last_error().decode() or "wdf_ss_lin_eval_ws_bytes: unsupported tree")
-            ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": None, "ws": ws,
-                                               "ring": torch.zeros((_ROWS, 4), dtype=torch.float32, device=dev),
-                                               "sums": torch.zeros(2, dtype=torch.float64, device=dev),
-                                               "turn": 0, "B": B, "T": T, "k": k, "zT": None},
-                                 ("eval",), nbytes=_nbytes(x_tm, tgt, tgt, ws))
         if ent is None:
-            dev = self.pb.block.device
+            circ, dev = self.circ, self.pb.block.device
+            nl = circ.root_kind == "DiodePair"
             x_tm, tgt, B, T = self._resident_pair(x, target)
             groups = -(-B // (128 if B % 2 == 0 else 64))         # (two sequences per lane when the rows pair up, on every tree)
-            k = max(1, min(T // 64, (_NL_EVAL_OCC * N_SIMD) // groups))
-            ws = self._plan_nl_eval(B, T, k, dev)
+            k = max(1, min(T // 64, ((_NL_EVAL_OCC if nl else _LIN_EVAL_OCC) * N_SIMD) // groups))     # the training entry's chunk formula
+            if nl:
+                ws, own = self._plan_nl_eval(B, T, k, dev), {"calls": 0, "watch": None, "replans": 0}
+            else:
+                # a linear tree (csrc/wdf_ss_lin_eval.h): a zeroed workspace of the pass's own size (the ticket, the chunks'
+                # zero-state ends, two partial sums per wave); its result rows are {mse, esr, mse + esr, mse by gscale}
+                nbytes = binding.lib().wdf_ss_lin_eval_ws_bytes(circ.ns, circ.ni, B, T, k)
+                if nbytes == 0:
+                    raise binding.WdfHipError(binding.lib().wdf_last_error().decode() or "wdf_ss_lin_eval_ws_bytes: unsupported tree")
+                ws, own = torch.zeros((nbytes,), dtype=torch.uint8, device=dev), {"zT": None}
             # a call's {mse, esr, mse + esr} in a row of its OWN, from a slab (entry()): a val_loss history stays what it was
             ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": None, "ws": ws,
                                                "ring": torch.zeros((_ROWS, 4), dtype=torch.float32, device=dev),
                                                "sums": torch.zeros(2, dtype=torch.float64, device=dev),
-                                               "turn": 0, "B": B, "T": T, "k": k, "calls": 0, "watch": None, "replans": 0},
+                                               "turn": 0, "B": B, "T": T, "k": k, **own},
                                  ("eval",), nbytes=_nbytes(x_tm, tgt, tgt, ws))
         return ent
 
@@ -1123,6 +1116,32 @@ class Circuit:
             return h[2], h[3]
         return float(parts[2]), float(parts[3])
 
+    def _z0_device(self, z0, dev, B):
+        """z0 as the one-pass steps and passes take it: detached float32 [ns, B] on dev, or None."""
+        if z0 is None:
+            return None
+        return torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(dev).float().reshape(self.ns, B).contiguous()
+
+    def _resident_stepper(self, x, target, kind, skip, store_output):
+        """What a new entry of the resident clipper holds, for training (_loss_resident) and for evaluation (_eval_resident)
+        alike: x time-major, the pot channel r (or None) and the target on the block's device, and an engine.MseStep on the
+        plan of engine.tuned_plan (fused: two sequences per lane).  Runs on a cache miss only."""
+        from . import engine
+        pb, dp, cap = self._pblock, self.root, self.top.P2
+        xd = x.as_subclass(torch.Tensor).to(pb.block.device).float()
+        xv, r = engine.split_channels(xd, self.per_sample_R is not None, time_major=True, anchor=x)
+        tgt = target.as_subclass(torch.Tensor).to(pb.block.device).float().reshape(xv.shape).contiguous()
+        host = pb.host_values()
+        R_plan = host[2] if r is None else engine.resistance_max(r)
+        tp = self.time_parallel
+        if tp == "auto":
+            tp = engine.tuned_plan(pb.block, xv, r, float(cap.FS), R_plan, host[3], n_up=dp.N_up, n_down=dp.N_down,
+                                   time_major=True, R_min=None if r is None else engine.resistance_min(r), fused=True)
+        T, B = xv.shape
+        st = engine.MseStep(B, T, float(cap.FS), tp, pb.block.device, n_up=dp.N_up, n_down=dp.N_down, time_major=True,
+                            warm=True, loss=kind, skip=int(skip), store_output=store_output)
+        return st, xv, r, tgt
+
     def _loss_resident(self, x, target, kind="mse", skip=0, store_output=True):
         """mse() / mse_esr() on a resident circuit: inputs prepared once per (x, target) pair -- a training set and a
         validation set alternate in clipper_pot.py:245-262, each keeps its own stepper and warm-start state -- then one pass
@@ -1139,19 +1158,8 @@ class Circuit:
                                           "block after to_device(); build a new Circuit")
         ent = self._res_cache.get((x, target), (kind, int(skip)))
         if ent is None:
-            dp, cap = self.root, self.top.P2
-            xd = x.as_subclass(torch.Tensor).to(pb.block.device).float()
-            xv, r = engine.split_channels(xd, self.per_sample_R is not None, time_major=True, anchor=x)
-            tgt = target.as_subclass(torch.Tensor).to(pb.block.device).float().reshape(xv.shape).contiguous()
-            host = pb.host_values()
-            R_plan = host[2] if r is None else engine.resistance_max(r)
-            tp = self.time_parallel
-            if tp == "auto":
-                tp = engine.tuned_plan(pb.block, xv, r, float(cap.FS), R_plan, host[3], n_up=dp.N_up, n_down=dp.N_down,
-                                       time_major=True, R_min=None if r is None else engine.resistance_min(r), fused=True)
+            st, xv, r, tgt = self._resident_stepper(x, target, kind, skip, store_output)
             T, B = xv.shape
-            st = engine.MseStep(B, T, float(cap.FS), tp, pb.block.device, n_up=dp.N_up, n_down=dp.N_down, time_major=True,
-                                warm=True, loss=kind, skip=int(skip), store_output=store_output)
             live = [(i, v) for i, v in sorted(pb.members.items()) if v.requires_grad]
             ent = self._res_cache.put((x, target), (st, xv, r, tgt, 1.0 / float(B * T) if kind == "mse" else 1.0,
                                                     [i for i, _ in live], [v for _, v in live], {id(v): i for i, v in live}),
@@ -1202,10 +1210,7 @@ class Circuit:
                 stateful, z0 = False, None                        # (no capacitor: nothing to carry)
             with torch._C.DisableTorchFunctionSubclass():
                 ent = lin.eval_entry(x, target)
-                z0d = None
-                if z0 is not None:
-                    z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["t"].device).float().reshape(self.ns, ent["B"]).contiguous()
-                loss = lin.evaluate(ent, kind, int(skip), store_output, z0d, bool(stateful))
+                loss = lin.evaluate(ent, kind, int(skip), store_output, self._z0_device(z0, ent["t"].device, ent["B"]), bool(stateful))
             self.last_output = ent["y"] if store_output else None
             if stateful:
                 self.last_state = ent["zT"].clone()              # (ent["zT"] is one of two ping-pong buffers: kept by value)
@@ -1253,19 +1258,7 @@ class Circuit:
         pb.flush()                                               # (queued optimizer updates of the block go out first)
         ent = self._res_cache.get((x, target), (kind, int(skip), "eval"))
         if ent is None:
-            dp, cap = self.root, self.top.P2
-            xd = x.as_subclass(torch.Tensor).to(pb.block.device).float()
-            xv, r = engine.split_channels(xd, self.per_sample_R is not None, time_major=True, anchor=x)
-            tgt = target.as_subclass(torch.Tensor).to(pb.block.device).float().reshape(xv.shape).contiguous()
-            host = pb.host_values()
-            R_plan = host[2] if r is None else engine.resistance_max(r)
-            tp = self.time_parallel
-            if tp == "auto":
-                tp = engine.tuned_plan(pb.block, xv, r, float(cap.FS), R_plan, host[3], n_up=dp.N_up, n_down=dp.N_down,
-                                       time_major=True, R_min=None if r is None else engine.resistance_min(r), fused=True)
-            T, B = xv.shape
-            st = engine.MseStep(B, T, float(cap.FS), tp, pb.block.device, n_up=dp.N_up, n_down=dp.N_down, time_major=True,
-                                warm=True, loss=kind, skip=int(skip), store_output=store_output)
+            st, xv, r, tgt = self._resident_stepper(x, target, kind, skip, store_output)
             ent = self._res_cache.put((x, target), (st, xv, r, tgt), (kind, int(skip), "eval"), 3 * _nbytes(xv, r, tgt))
         st, xv, r, tgt = ent
         st.store_output = bool(store_output)                     # (this call's choice: eval_fused makes y on first use)
@@ -1303,23 +1296,17 @@ class Circuit:
     def _mse_esr(self, x, target, skip, z0, carry_state, store_output):
         binding.require_gpu()
         stateful = (z0 is not None or carry_state) and self.ns > 0
+        if carry_state and z0 is None:                           # (once, for every branch that takes a state; the others never look at z0)
+            z0 = getattr(self, "last_state", None)
         if self.root_kind == "AsymDiodePair" and not self._asym_generic and self.root.mode != binding.ASYM_OMEGA_F32 \
                 and 0 <= int(skip) < int(np.shape(x)[1]):
-            if carry_state and z0 is None:
-                z0 = getattr(self, "last_state", None)
             return self._mse_esr_clipper_asym(x, target, int(skip), z0, stateful)      # the Newton solvers: the one-pass step
         if ASYM_TREE_STEP_SERVES["mse_esr"] and self._asym_step_tree(x, target, "mse_esr", skip):
-            if carry_state and z0 is None:
-                z0 = getattr(self, "last_state", None)
             return self._asym_tree_step(x, target, "mse_esr", int(skip), z0, stateful)
         if LIN_ESR_STEP_SERVES and getattr(self, "_lin", None) is not None and isinstance(x, torch.Tensor) \
                 and isinstance(target, torch.Tensor) and x.dim() >= 2 and 0 <= int(skip) < int(x.shape[1]):
-            if carry_state and z0 is None:
-                z0 = getattr(self, "last_state", None)
             return self._mse_esr_lin_step(x, target, int(skip), z0, stateful, store_output)      # the linear step takes z0 / zT itself
         if stateful:
-            if carry_state and z0 is None:
-                z0 = getattr(self, "last_state", None)
             y, zT = self(x, z0=z0, return_state=True)
             self.last_state, self.last_output = zT.detach(), y.detach()
             o = y[int(skip):]
@@ -1418,9 +1405,7 @@ class Circuit:
             lin.check()
             ent = lin.entry(x, target, "mse+esr", int(skip), store_output)
             live = [(i, v) for i, v in sorted(lin.pb.members.items()) if v.requires_grad]
-            z0d = None
-            if z0 is not None:
-                z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["t"].device).float().reshape(self.ns, ent["B"]).contiguous()
+            z0d = self._z0_device(z0, ent["t"].device, ent["B"])
         loss, out = _LinResidentMseFn.apply(lin, ent, 1.0, [i for i, _ in live], z0d, bool(stateful), *[v for _, v in live])
         loss = loss.as_subclass(tf.Tensor)
         loss._wdf_fused = (out, {id(v): i for i, v in live})
@@ -1470,8 +1455,8 @@ class Circuit:
         elif not isinstance(tp, SsTpPlan):
             tp = None
         k, W, tol = (int(tp.k_fwd), int(tp.warmup), float(tp.tol)) if (tp is not None and tp.k_fwd >= 2) else (1, 0, 1.0e-6)
-        z0t = None if z0 is None else torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(dev).float().reshape(self.ns, B).contiguous()
-        loss, y, zT = _AsymTreeStepFn.apply(coef, rootp, xt, tgt, self.ns, self.ni, kind, int(skip), z0t, bool(stateful), k, W, tol)
+        loss, y, zT = _AsymTreeStepFn.apply(coef, rootp, xt, tgt, self.ns, self.ni, kind, int(skip), self._z0_device(z0, dev, B),
+                                            bool(stateful), k, W, tol)
         self.last_output = y
         if stateful:
             self.last_state = zT
@@ -1552,9 +1537,7 @@ class Circuit:
                 lin.check()                                      #  send the queued optimizer updates: the probe carries them)
                 ent = lin.entry(x, target, store_output=store_output)
                 live = [(i, v) for i, v in sorted(lin.pb.members.items()) if v.requires_grad]
-                z0d = None
-                if z0 is not None:                               # the linear step takes the state in and hands it out
-                    z0d = torch.as_tensor(z0).as_subclass(torch.Tensor).detach().to(ent["t"].device).float().reshape(self.ns, ent["B"]).contiguous()
+                z0d = self._z0_device(z0, ent["t"].device, ent["B"])      # the linear step takes the state in and hands it out
             loss, out = _LinResidentMseFn.apply(lin, ent, 1.0 / float(ent["B"] * ent["T"]), [i for i, _ in live], z0d, stateful,
                                                 *[v for _, v in live])
             loss = loss.as_subclass(tf.Tensor)
