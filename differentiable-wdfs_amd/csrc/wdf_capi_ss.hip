@@ -19,6 +19,12 @@ using SsNlRoots = Values<int, wdf::kRootDiode, wdf::kRootAsym>;      // the spec
 // for this root in any of the four kernels: WDF_EUNSUPPORTED.
 constexpr int kAsymMaxStates = 3;
 template <class NS, class ROOT> constexpr bool ss_built(NS, ROOT) { return !(ROOT() == wdf::kRootAsym && NS() > kAsymMaxStates); }
+// the instantiations of ss_bwd_gx_kernel: the family's (no instantiation uses scratch: profiles/ss_gx_resources.txt).  A linear
+// tree takes SYM = true, two different diodes SYM = false, as in wdf_ss_bwd_tp.
+template <class NS, class ROOT, class SYM> constexpr bool ss_gx_built(NS ns, ROOT root, SYM)
+{
+    return ss_built(ns, root) && !(ROOT() == wdf::kRootNone && !SYM()) && !(ROOT() == wdf::kRootAsym && SYM());
+}
 constexpr int kUnit = 8;                          // chunk lengths and warm-ups of the time-parallel kernels: multiples of 8 steps
 
 int ss_check(const float* x, const float* coef, const float* rootp, int ns, int ni, int root, int n_up, int n_down,
@@ -270,6 +276,57 @@ int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns,
     if (rc) return rc;
     launch_ss_grad_reduce(part, ns, ni, root, rootp, gcoef, groot, B, s);
     return check_launch("wdf_ss_grad_reduce");
+}
+
+// ---- the input gradient dL/dx (wdf_statespace.h: ss_bwd_gx_kernel, ss_bwd_gx_lamin_kernel) ------------------------------
+
+size_t wdf_ss_bwd_gx_ws_bytes(int ns, int64_t B, int n_chunks)
+{
+    return (ns < 1 || B <= 0 || n_chunks <= 1) ? 0 : (size_t)n_chunks * (size_t)ns * (size_t)B * sizeof(float);
+}
+
+int wdf_ss_bwd_gx(const float* x, const float* coef, const float* rootp, int ns, int ni, int root, int n_up, int n_down,
+                  const float* zstash, const float* gy, const void* ws_bwd_tp, void* ws_gx, float* gx, int64_t B, int64_t T,
+                  int n_chunks, void* stream)
+{
+    int rc = ss_check(x, coef, rootp, ns, ni, root, n_up, n_down, B, T, 0);
+    if (rc) return rc;
+    const bool sym = root == wdf::kRootNone || (root == wdf::kRootDiode && n_up == n_down);
+    // (the table the launch below goes by, asked before anything else: a combination that is not built says so whatever else is wrong)
+    if (!dispatch([&](auto NS, auto ROOT, auto SYM) { return ss_gx_built(NS, ROOT, SYM); }, SsStates{ns}, SsRoots{root}, Bools{sym}))
+        return no_kernel("wdf_ss_bwd_gx");
+    const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);
+    if ((rc = check_tiles(g, n_chunks, T, kUnit, "wdf_ss_tp_chunks"))) return rc;
+    if (!gy || !gx) return fail(WDF_EINVAL, "null gy/gx");
+    if (ns > 0 && !zstash) return fail(WDF_EINVAL, "null zstash");
+    if (n_chunks > 1 && ns < 1) return fail(WDF_EINVAL, "a tree without states has no adjoint to carry across chunks: n_chunks = 1");
+    if (n_chunks > 1 && (!ws_bwd_tp || !ws_gx)) return fail(WDF_EINVAL, "n_chunks > 1 needs wdf_ss_bwd_tp's workspace and ws_gx");
+    hipStream_t s = (hipStream_t)stream;
+    float* lamin = g.K > 1 ? (float*)ws_gx : nullptr;
+    if (lamin) {
+        const float* rec = (const float*)((const char*)ws_bwd_tp + wdf_ss_bwd_ws_bytes(ns, ni, B));
+        const bool ok = dispatch([&](auto NS, auto NI, auto ROOT) {
+            if constexpr (!ss_built(NS, ROOT)) return false;
+            else {
+                hipLaunchKernelGGL((wdf::ss_bwd_gx_lamin_kernel<NS(), NI(), wdf::kSsRootAcc<ROOT()>>), dim3(waves64(B)), dim3(64), 0, s, rec,
+                                   lamin, B, (int64_t)g.K);
+                return true;
+            }
+        }, SsStates1{ns}, SsInputs{ni}, SsRoots{root});
+        if (!ok) return no_kernel("wdf_ss_bwd_gx");
+        if ((rc = check_launch("wdf_ss_bwd_gx (entering adjoints)"))) return rc;
+    }
+    const dim3 grid(waves64(B), (unsigned)g.K);
+    const bool ok = dispatch([&](auto NS, auto NI, auto ROOT, auto SYM, auto V4) {
+        if constexpr (!ss_gx_built(NS, ROOT, SYM)) return false;
+        else {
+            EventBracket bracket(s);
+            hipLaunchKernelGGL((wdf::ss_bwd_gx_kernel<NS(), NI(), ROOT(), SYM(), V4()>), grid, dim3(64), 0, s, x, coef, rootp, n_up, n_down,
+                               zstash, gy, (const float*)lamin, gx, B, T, g.L);
+            return true;
+        }
+    }, SsStates{ns}, SsInputs{ni}, SsRoots{root}, Bools{sym}, Bools{ss_v4(x, T, ni)});
+    return ok ? check_launch("wdf_ss_bwd_gx") : no_kernel("wdf_ss_bwd_gx");
 }
 
 // ---- the one-pass MSE step of linear trees (wdf_ss_step.h) -------------------------------------------------------------

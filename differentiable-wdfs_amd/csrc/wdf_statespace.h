@@ -926,4 +926,166 @@ __global__ __launch_bounds__(64) void ss_bwd_tp_combine_kernel(const float* __re
     }
 }
 
+// ---- input gradient --------------------------------------------------------------------------------------------
+// dL/dx falls out of the adjoint recurrence one line before its update: with lam the adjoint of the state AFTER step t,
+//   gb = fy g + E . lam ;  ga = gb D_a(a)
+//   gx[t][i] = dy[i] g + da[i] ga + sum_s Bx[s][i] lam[s]
+// and then lam moves on exactly as in ss_bwd_step.  A pass of its own behind the sweep (the sweeps' code stays what it is): it
+// re-reads x, the stash and gy, evaluates of the root only what D_a needs, keeps no sums and writes gx time-major, [T][NI][B]
+// -- one coalesced wave store per (step, channel); x's own [B][T][NI] layout would be 64 cache lines per store.
+// Per sample: 4 NI + 4 NS + 4 bytes read, 4 NI written.
+template <int NS, int NI, int ROOT, bool SYM>
+__device__ __forceinline__ void ss_bwd_gx_step(const SSCoef<NS, NI>& c, const SSRoot<ROOT>& dp, const float (&x)[NI],
+                                               const float (&z)[NS > 0 ? NS : 1], float g, float (&lam)[NS > 0 ? NS : 1],
+                                               float (&gx)[NI])
+{
+    using C = SSCoef<NS, NI>;
+    float Da = 0.0f;
+    if constexpr (ROOT != kRootNone) {
+        float a = 0.0f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) a = fmaf(c.v[C::oCa + s], z[s], a);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) a = fmaf(c.v[C::oDa + i], x[i], a);
+        if constexpr (ROOT == kRootAsym) {
+            int iters = 0;
+            float v, e1, e2;
+            float cf[5];
+            (void)asym_newton32_solve(dp.c, a, kSsAsymTol, kSsAsymMaxIter, iters, v, e1, e2);
+            asym_newton_partials(dp.c, v, e1, e2, Da, cf);
+        } else {
+            const DiodeOut o = diode_pair<SYM>(a, dp.L, dp.d);
+            const float w0p = o.w0 * fast_rcp(1.0f + o.w0);
+            const float w1p = o.w1 * fast_rcp(1.0f + o.w1);
+            Da = fmaf(-2.0f * (o.lam * o.lam), w0p + w1p, 1.0f);
+        }
+    }
+    float gb = c.v[C::oFy] * g;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) gb = fmaf(c.v[C::oE + s], lam[s], gb);
+    const float ga = gb * Da;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        float v = fmaf(c.v[C::oDa + i], ga, c.v[C::oDy + i] * g);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) v = fmaf(c.v[C::oB + s * NI + i], lam[s], v);
+        gx[i] = v;
+    }
+    // adjoint of the state (ss_bwd_step's)
+    float ln[NS > 0 ? NS : 1];
+#pragma unroll
+    for (int s2 = 0; s2 < NS; ++s2) {
+        float v = fmaf(c.v[C::oCa + s2], ga, c.v[C::oCy + s2] * g);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) v = fmaf(c.v[C::oA + s * NS + s2], lam[s], v);
+        ln[s2] = v;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) lam[s] = ln[s];
+}
+
+// grid (waves, K): chunk k owns [k L, min((k + 1) L, T)), L a multiple of 8 (one chunk: L >= T).  lamin [K][NS][B]: the adjoint
+// that enters chunk k from the future (ss_bwd_gx_lamin_kernel), or null: zero (one chunk).  Both roots' solves hold a wavefront
+// ballot, so dead lanes shadow sequence B - 1 to the end and only store nothing.
+template <int NS, int NI, int ROOT, bool SYM, bool VEC4>
+__global__ __launch_bounds__(64) void ss_bwd_gx_kernel(const float* __restrict__ x, const float* __restrict__ coef,
+                                                       const float* __restrict__ rootp, int n_up, int n_down,
+                                                       const float* __restrict__ zstash, const float* __restrict__ gy,
+                                                       const float* __restrict__ lamin, float* __restrict__ gx, int64_t B,
+                                                       int64_t T, int64_t L)
+{
+    constexpr int NSa = NS > 0 ? NS : 1;
+    const int64_t b_raw = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const bool live = b_raw < B;
+    const int64_t b = live ? b_raw : B - 1;
+    const int64_t k = blockIdx.y, t0 = k * L, t1 = (t0 + L < T) ? t0 + L : T;
+    SSCoef<NS, NI> c;
+    c.load(coef);
+    SSRoot<ROOT> dp = {};
+    if constexpr (ROOT != kRootNone) dp.load(rootp, n_up, n_down);
+    float lam[NSa];
+#pragma unroll
+    for (int s = 0; s < NSa; ++s) lam[s] = (NS > 0 && lamin) ? lamin[(k * NS + (s < NS ? s : 0)) * B + b] : 0.0f;
+    const float* __restrict__ xp = x + b * T * NI;
+    float* __restrict__ gp = gx + b;
+    const int64_t tfull = t1 - (t1 - t0) % kBlkSS;              // t0 is a multiple of 8: only the last chunk has a tail
+    for (int64_t t = t1 - 1; t >= tfull; --t) {                 // tail first (highest t)
+        float xt[NI], zt[NSa], gt[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) xt[i] = xp[t * NI + i];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) zt[s] = zstash[(t * NS + s) * B + b];
+        ss_bwd_gx_step<NS, NI, ROOT, SYM>(c, dp, xt, zt, gy[t * B + b], lam, gt);
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) gp[(t * NI + i) * B] = gt[i];
+        }
+    }
+    float xc[kBlkSS][NI], xn[kBlkSS][NI], zc[kBlkSS][NSa], zn[kBlkSS][NSa], gc[kBlkSS], gn[kBlkSS];
+    auto load_blk = [&](int64_t tb, float (&xv)[kBlkSS][NI], float (&zv)[kBlkSS][NSa], float (&gv)[kBlkSS]) {
+        ss_load_block<NI, VEC4>(x, b, T, tb, xv);
+#pragma unroll
+        for (int q = 0; q < kBlkSS; ++q) {
+            gv[q] = gy[(tb + q) * B + b];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) zv[q][s] = zstash[((tb + q) * NS + s) * B + b];
+        }
+    };
+    if (tfull > t0) load_blk(tfull - kBlkSS, xn, zn, gn);
+    for (int64_t tb = tfull - kBlkSS; tb >= t0; tb -= kBlkSS) {  // 8-step blocks, the next one (earlier in time) in flight
+#pragma unroll
+        for (int q = 0; q < kBlkSS; ++q) {
+            gc[q] = gn[q];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) xc[q][i] = xn[q][i];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) zc[q][s] = zn[q][s];
+        }
+        if (tb - kBlkSS >= t0) load_blk(tb - kBlkSS, xn, zn, gn);
+#pragma unroll
+        for (int q = kBlkSS - 1; q >= 0; --q) {
+            float gt[NI];
+            ss_bwd_gx_step<NS, NI, ROOT, SYM>(c, dp, xc[q], zc[q], gc[q], lam, gt);
+            if (live) {
+#pragma unroll
+                for (int i = 0; i < NI; ++i) gp[((tb + q) * NI + i) * B] = gt[i];
+            }
+        }
+    }
+}
+
+// lamin [K][NS][B] <- the adjoint entering every chunk, re-walked from the records ss_bwd_tp_kernel left (rec, the layout above:
+// Phi and beta only are read) with the arithmetic of ss_bwd_tp_combine_kernel's walk: LAM_{K-1} = 0, LAM_{k-1} = Phi_k LAM_k + beta_k.
+template <int NS, int NI, int NR>
+__global__ __launch_bounds__(64) void ss_bwd_gx_lamin_kernel(const float* __restrict__ rec, float* __restrict__ lamin, int64_t B,
+                                                             int64_t K)
+{
+    constexpr int NREC = SsTpRec<NS, NI, NR>::N;
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    double LAM[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) LAM[s] = 0.0;
+    for (int64_t k = K - 1; k >= 0; --k) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) lamin[(k * NS + s) * B + b] = (float)LAM[s];
+        const float* __restrict__ o = rec + (size_t)k * NREC * B + b;
+        float v[NS * NS + NS];
+#pragma unroll
+        for (int i = 0; i < NS * NS + NS; ++i) v[i] = o[(size_t)i * B];
+        const float* Phi = v;
+        const float* beta = v + NS * NS;
+        double nl[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            double a = (double)beta[s];
+#pragma unroll
+            for (int r = 0; r < NS; ++r) a += (double)Phi[s * NS + r] * LAM[r];
+            nl[s] = a;
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) LAM[s] = nl[s];
+    }
+}
+
 }  // namespace wdf

@@ -182,6 +182,8 @@ SIGNATURES = {
     "wdf_ss_fwd_tp_root": (_ci, _SS + [_p, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p]),
     "wdf_ss_bwd_tp_ws_bytes": (_sz, [_ci, _ci, _i64, _ci]),
     "wdf_ss_bwd_tp": (_ci, _SS + [_p, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
+    "wdf_ss_bwd_gx_ws_bytes": (_sz, [_ci, _i64, _ci]),
+    "wdf_ss_bwd_gx": (_ci, _SS + [_p, _p, _p, _p, _p, _i64, _i64, _ci, _p]),
     "wdf_ss_asym_step_ws_bytes": (_sz, _STEP_WS),
     "wdf_ss_asym_step_esr_ws_bytes": (_sz, _STEP_WS),
     "wdf_ss_asym_step_mse": (_ci, [_p, _p, _p, _ci, _ci, _p, _cf, _p, _p, _p, _i64, _i64, _ci, _ci, _cf, _p, _p, _p, _p]),
@@ -2084,8 +2086,53 @@ def ss_dyn_bwd_tp(x, rows, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, ro
     return grows, groot, gz0
 
 
-def ss_bwd_tp(x, coef, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, want_gz0=False):
-    """Exact chunked reverse sweep (wdf_ss_bwd_tp); same returns as ss_bwd."""
+def ss_bwd_gx_built(ns, ni, root_kind):
+    """Whether the input-gradient pass is built for (ns, ni, root_kind): the entry point itself answers, from the table its
+    launch goes by, before it looks at anything but x, coef and the root arguments (no GPU needed: with gy and gx null the
+    call ends in its argument checks, and no pointer is ever followed)."""
+    one = (C.c_float * 8)()
+    at = C.c_void_p(C.addressof(one))
+    rc = lib().wdf_ss_bwd_gx(at, at, at, int(ns), int(ni), int(root_kind), 1, 1, None, None, None, None, None, 64, 64, 1, None)
+    # (built: the call got as far as its null-pointer checks; not built, or no such ns / ni / root kind: it ended before them)
+    return rc == -1 and lib().wdf_last_error().decode().startswith("null gy/gx")
+
+
+def ss_bwd_gx(x, coef, ns, ni, zs, gy, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, n_chunks=1, ws_bwd_tp=None, gx=None,
+              ws_gx=None):
+    """The input gradient dL/dx of a reverse sweep (wdf_ss_bwd_gx) -> gx [T,ni,B], time-major: gx.permute(2, 0, 1) is a view in
+    x's own [B,T,ni] layout.  x, coef, zs (the stash), gy, the root arguments: the sweep's.  n_chunks == 1: the sequential form.
+    n_chunks > 1: behind ss_bwd_tp(..., n_chunks, return_ws=True) on the same stream, ws_bwd_tp the workspace that call handed
+    back; ws_gx (or a fresh buffer) receives the chunks' entering adjoints, float [K, ns, B].  gx can be preallocated."""
+    require_gpu()
+    x, coef, rootp = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(rootp, "rootp")
+    zs, gy = _f32_dev(zs, "zstash"), _f32_dev(gy, "gy")
+    B, T = _ss_check_shapes("ss_bwd_gx", x, coef, ns, ni, root_kind, rootp, zstash=zs, gy=gy, sweep=True)
+    if not ss_bwd_gx_built(ns, ni, root_kind):
+        raise WdfHipError(f"ss_bwd_gx: no input-gradient kernel is built for ns={ns}, ni={ni}, root kind {int(root_kind)}")
+    n_chunks = int(n_chunks)
+    if n_chunks < 1 or (n_chunks > 1 and ns < 1):
+        raise WdfHipError(f"ss_bwd_gx: n_chunks >= 1, and 1 for a tree without states (got {n_chunks}, ns={ns})")
+    K = lib().wdf_ss_tp_chunks(T, n_chunks)
+    if K > 1:
+        if ws_bwd_tp is None:
+            raise WdfHipError("ss_bwd_gx: n_chunks > 1 needs ws_bwd_tp, the workspace ss_bwd_tp(..., return_ws=True) handed back")
+        ws_bwd_tp = _ws(ws_bwd_tp, lib().wdf_ss_bwd_tp_ws_bytes(ns, ni, B, K), x)
+        ws_gx = _ws(ws_gx, lib().wdf_ss_bwd_gx_ws_bytes(ns, B, K), x)
+    else:
+        ws_bwd_tp = ws_gx = None
+    if gx is not None and tuple(getattr(gx, "shape", ())) != (T, ni, B):
+        raise WdfHipError(f"gx must be [T,ni,B] = [{T},{ni},{B}], got {tuple(getattr(gx, 'shape', ()))}")
+    gx = _out(gx, T * ni * B, "gx", "one value per sample and channel", x).view(T, ni, B)
+    rc = lib().wdf_ss_bwd_gx(_ptr(x), _ptr(coef), _ptr(rootp), int(ns), int(ni), int(root_kind), int(n_up), int(n_down), _ptr(zs),
+                             _ptr(gy), _ptr(ws_bwd_tp), _ptr(ws_gx), _ptr(gx), B, T, K, _stream())
+    _check(rc, "wdf_ss_bwd_gx")
+    return gx
+
+
+def ss_bwd_tp(x, coef, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, rootp=None, n_up=1, n_down=1, want_gz0=False,
+              return_ws=False):
+    """Exact chunked reverse sweep (wdf_ss_bwd_tp); same returns as ss_bwd.  return_ws: the workspace the call used comes back
+    as a fourth value (ss_bwd_gx reads the chunk records in it)."""
     require_gpu()
     x, coef, rootp = _f32_dev(x, "x"), _f32_dev(coef, "coef"), _f32_dev(rootp, "rootp")
     zstash, gy = _f32_dev(zstash, "zstash"), _f32_dev(gy, "gy")
@@ -2099,7 +2146,7 @@ def ss_bwd_tp(x, coef, ns, ni, zstash, gy, n_chunks, root_kind=ROOT_NONE, rootp=
     rc = lib().wdf_ss_bwd_tp(_ptr(x), _ptr(coef), _ptr(rootp), ns, ni, root_kind, int(n_up), int(n_down), _ptr(zstash),
                              _ptr(gy), _ptr(ws), _ptr(gcoef), _ptr(groot), _ptr(gz0), B, T, K, _stream())
     _check(rc, "wdf_ss_bwd_tp")
-    return gcoef, groot, gz0
+    return (gcoef, groot, gz0, ws) if return_ws else (gcoef, groot, gz0)
 
 
 def omega(x, want_iters=False):

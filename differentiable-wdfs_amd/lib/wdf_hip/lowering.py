@@ -187,11 +187,16 @@ class DynWarmStart:
 
 class _StateSpaceFn(torch.autograd.Function):
     """y [T,B] = statespace(coef, rootp, x [B,T,ni], z0).  tp: an SsTpPlan (time-parallel kernels) or None.
-    warm: an SsWarmStart for this batch (training loops) or None."""
+    warm: an SsWarmStart for this batch (training loops) or None.
+    An x that carries a graph gets dL/dx from a pass of its own behind the reverse sweep (csrc/wdf_statespace.h:
+    ss_bwd_gx_kernel); a plain x launches what it always launched.
+    launches: how many times the input-gradient pass went out (tests read it)."""
+    launches = {"gx": 0}
 
     @staticmethod
     def forward(ctx, coef, rootp, x, z0, ns, ni, root_kind, n_up, n_down, want_zT, tp=None, warm=None):
         need = coef.requires_grad or (rootp is not None and rootp.requires_grad) or (z0 is not None and z0.requires_grad)
+        need = need or ctx.needs_input_grad[2]
         c = coef.detach().contiguous()
         rp = None if rootp is None else rootp.detach().contiguous()
         z0d = None if z0 is None else z0.detach().contiguous()
@@ -221,13 +226,23 @@ class _StateSpaceFn(torch.autograd.Function):
     def backward(ctx, gy, _gzT):
         ns, ni, root_kind, n_up, n_down, has_z0, tp = ctx.cfg
         c, rp, x, zs = ctx.saved_tensors
+        want_gx = ctx.needs_input_grad[2]
+        gy = gy.contiguous()
+        k, ws = 1, None
         if tp is not None and tp.k_bwd >= 2 and ns >= 1:      # exact chunked reverse sweep (any root)
-            gcoef, groot, gz0 = binding.ss_bwd_tp(x, c, ns, ni, zs, gy.contiguous(), tp.k_bwd, root_kind, rp, n_up, n_down,
-                                                  want_gz0=has_z0)
+            k = tp.k_bwd
+            gcoef, groot, gz0, *ws = binding.ss_bwd_tp(x, c, ns, ni, zs, gy, k, root_kind, rp, n_up, n_down, want_gz0=has_z0,
+                                                       return_ws=want_gx)
         else:
-            gcoef, groot, gz0 = binding.ss_bwd(x, c, ns, ni, zs, gy.contiguous(), root_kind, rp, n_up, n_down,
-                                               want_gz0=has_z0)
-        return gcoef, groot, None, gz0, None, None, None, None, None, None, None, None
+            gcoef, groot, gz0 = binding.ss_bwd(x, c, ns, ni, zs, gy, root_kind, rp, n_up, n_down, want_gz0=has_z0)
+        gx = None
+        if want_gx:
+            # dL/dx: the sweep's chunks, each from the adjoint that enters it (re-walked from the records the sweep left in ws);
+            # time-major [T,ni,B], handed back as a view in x's layout
+            gx = binding.ss_bwd_gx(x, c, ns, ni, zs, gy, root_kind, rp, n_up, n_down, n_chunks=k,
+                                   ws_bwd_tp=ws[0] if ws else None).permute(2, 0, 1)
+            _StateSpaceFn.launches["gx"] += 1
+        return gcoef, groot, gx, gz0, None, None, None, None, None, None, None, None
 
 
 class _AsymTreeStepFn(torch.autograd.Function):
@@ -1294,10 +1309,22 @@ class Circuit:
         return loss
 
     def _mse_esr(self, x, target, skip, z0, carry_state, store_output):
+        gx_route = self._input_grad_route(x)                     # (an x with a graph: composed from self(x), no one-pass step)
         binding.require_gpu()
         stateful = (z0 is not None or carry_state) and self.ns > 0
         if carry_state and z0 is None:                           # (once, for every branch that takes a state; the others never look at z0)
             z0 = getattr(self, "last_state", None)
+        if gx_route is not None:
+            if stateful:
+                y, zT = self(x, z0=z0, return_state=True)
+                self.last_state, self.last_output = zT.detach(), y.detach()
+            else:
+                y = self(x)
+            o = y[int(skip):]
+            t = tf.convert(target, device=o.device).reshape(y.shape)[int(skip):]
+            S, E = tf.reduce_sum(tf.square(o - t)), tf.reduce_sum(tf.square(o)) + float(np.finfo(float).eps)
+            n = float(o.numel())
+            return S / n + tf.sqrt(S / E / n)
         if self.root_kind == "AsymDiodePair" and not self._asym_generic and self.root.mode != binding.ASYM_OMEGA_F32 \
                 and 0 <= int(skip) < int(np.shape(x)[1]):
             return self._mse_esr_clipper_asym(x, target, int(skip), z0, stateful)      # the Newton solvers: the one-pass step
@@ -1360,6 +1387,7 @@ class Circuit:
         weights, coeff = binding.check_loss_weights((mse, esr, esr_emph, avg), coeff)
         if n_global is not None and not float(n_global) > 0.0:
             raise ValueError(f"n_global must be positive, got {n_global}")
+        self._input_grad_route(x)                                # (a route without dL/dx says so before a device is asked for)
         binding.require_gpu()
         y = self(x)
         yt = y.as_subclass(torch.Tensor)
@@ -1520,12 +1548,20 @@ class Circuit:
         return loss
 
     def _mse(self, x, target, z0, carry_state, store_output):
+        gx_route = self._input_grad_route(x)                     # (an x with a graph: composed from self(x), no one-pass step)
         binding.require_gpu()
         stateful = z0 is not None or carry_state
         if carry_state and z0 is None:
             z0 = getattr(self, "last_state", None)
         if stateful and self.ns == 0:
             stateful, z0 = False, None                            # (no capacitor: nothing to carry)
+        if gx_route is not None:
+            if stateful:
+                y, zT = self(x, z0=z0, return_state=True)
+                self.last_state, self.last_output = zT.detach(), y.detach()
+            else:
+                y = self(x)
+            return tf.reduce_mean(tf.square(y - tf.convert(target, device=y.device).reshape(y.shape)))
         lin = getattr(self, "_lin", None)
         if lin is None and getattr(self, "_tree", None) is not None and self.root_kind == "DiodePair" and 1 <= self.ns <= 2 \
                 and 1 <= self.ni <= 2 and not self.force_generic:
@@ -1580,6 +1616,41 @@ class Circuit:
         loss = engine.clipper_mse(theta, xv, tgt, float(cap.FS), r=r, n_up=dp.N_up, n_down=dp.N_down, tp=tp,
                                   time_major=True)
         return loss.as_subclass(tf.Tensor)
+
+    def _input_grad_route(self, x):
+        """What __call__ does with an x that carries a graph (grad mode on, x.requires_grad): None for a plain x -- nothing
+        changes; "generic" for the diode-pair clipper with host-resident Variables and no resistance channel (it takes the
+        generic state-space path, force_generic's); "state-space" for whatever reaches _StateSpaceFn anyway (host-resident
+        trees, resident trees through _ProbeFn, AsymDiodePair(any_tree=True)): the reverse sweep is followed by the
+        input-gradient pass.  Every other route has no kernel that writes dL/dx and raises, naming itself, before a device is
+        asked for -- the gradient used to be dropped without a word."""
+        if not (torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad):
+            return None
+
+        def refuse(route, instead):
+            raise binding.WdfHipError(f"Circuit: the input carries an autograd graph (x.requires_grad), and {route} has no "
+                                      f"input gradient dL/dx: {instead}, or pass x.detach() if the gradient is not wanted")
+
+        if self._dyn:
+            refuse("the streamed-coefficient route (csrc/wdf_ss_dyn.h: a per_sample_R channel, a DenseRootModel root or "
+                   "AsymDiodePair(streamed=True) off the clipper's own kernels, more than four capacitors)",
+                   "the static state-space kernels serve trees of at most four capacitors with fixed resistances")
+        if self._is_clipper() and self.root_kind == "DiodePair" and not self.force_generic:
+            if self.per_sample_R is not None:
+                refuse("the diode-pair clipper with a per_sample_R channel", "a fixed source resistance takes the generic path")
+            if getattr(self, "_pblock", None) is not None:
+                refuse("the resident diode-pair clipper (to_device(): the one-pass step's kernels)",
+                       "a clipper left on the host path takes the generic state-space kernels")
+            return "generic"
+        if self.root_kind == "AsymDiodePair" and not self._asym_generic:
+            if self.per_sequence_R is not None:
+                refuse("the two-different-diode clipper under per_sequence_R (csrc/wdf_asym.h)",
+                       "AsymDiodePair(any_tree=True) with force_generic=True and a fixed resistance is served")
+            refuse("the two-different-diode clipper's own kernels (csrc/wdf_asym.h)",
+                   "AsymDiodePair(any_tree=True) with force_generic=True is served")
+        if self.root_kind == "DenseRootModel":
+            refuse("the MLP root (csrc/wdf_mlp.h)", "no route serves a network root yet")
+        return "state-space"
 
     def reset_state(self):
         """Forget the state carried by mse(..., carry_state=True): the next such call starts from zero (Capacitor.reset,
@@ -1636,7 +1707,10 @@ class Circuit:
     # -- run
     def __call__(self, x, z0=None, return_state=False):
         """x: [B,T] or [B,T,n_in] float32 CUDA tensor (batch-major, the reference's
-        input[:, i, c] layout).  Returns y [T,B] (and the final capacitor states [ns,B])."""
+        input[:, i, c] layout).  Returns y [T,B] (and the final capacitor states [ns,B]).
+        An x that carries a graph (a trainable gain or pre-filter in front, another circuit's output) gets its gradient where
+        a state-space kernel runs the tree (_input_grad_route); every other route raises."""
+        gx_route = self._input_grad_route(x)
         binding.require_gpu()
         self._anchor = x if isinstance(x, torch.Tensor) else None      # the caller's object: cache key for its copies
         if not isinstance(x, torch.Tensor):
@@ -1654,7 +1728,7 @@ class Circuit:
 
         if self._dyn:
             return self._run_dyn(x, z0, return_state)
-        if self._is_clipper() and self.root_kind == "DiodePair" and not self.force_generic:
+        if self._is_clipper() and self.root_kind == "DiodePair" and not self.force_generic and gx_route != "generic":
             return self._run_clipper(x, z0, return_state)
         if self.root_kind == "AsymDiodePair" and not self._asym_generic:
             return self._run_clipper_asym(x, z0, return_state)

@@ -482,7 +482,14 @@ class Recorder:
         def pick(w, slots):
             return w.c0[slots] if slots else torch.zeros(0, dtype=torch.float64)
 
-        if self.rin is not None or any(w.c1 is not None for w in trans + [y] + ([a] if a is not None else [])):
+        dynamic = self.rin is not None or any(w.c1 is not None for w in trans + [y] + ([a] if a is not None else []))
+        if (dynamic or root_kind == "DenseRootModel") and torch.is_grad_enabled() and isinstance(self.parent, torch.Tensor) \
+                and self.parent.requires_grad:
+            # (a static tree without a network root goes through _StateSpaceFn below, which returns dL/dx)
+            raise binding.WdfHipError("the recorded loop's input carries an autograd graph, and the compat tier's lowering of a "
+                                      "per-sample resistance or a DenseRootModel root has no input gradient dL/dx: build the "
+                                      "tree as a tf_wdf.Circuit with fixed resistances, or pass the input detached")
+        if dynamic:
             y_tb, zT = self._lower_dynamic(trans, a, y, lr, z0, dev, engine, mlp_root)
         elif root_kind == "DenseRootModel":
             y_tb, zT = self._lower_static_mlp(trans, a, y, lr, z0, dev, mlp_root)

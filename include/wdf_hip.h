@@ -670,6 +670,24 @@ int wdf_ss_bwd_tp(const float* x, const float* coef, const float* rootp, int ns,
                   int n_chunks, void* stream);
 size_t wdf_ss_bwd_ws_bytes(int ns, int ni, int64_t B);
 
+/* The input gradient of the two reverse sweeps above (csrc/wdf_statespace.h: ss_bwd_gx_kernel): gx [T][ni][B] <- dL/dx, time-major
+ * (every store one coalesced wave transaction; x's own [B][T][ni] layout is a permuted view of it).  With lam the adjoint of the
+ * state after step t:  gb = fy g + E . lam ;  ga = gb Da(a) ;  gx[t][i] = dy[i] g + da[i] ga + sum_s Bx[s][i] lam[s].
+ * A pass of its own behind the sweep: x, coef, rootp, the root arguments, zstash and gy are the sweep's; the root is evaluated
+ * again for Da alone and nothing is summed.  Per sample 4 ni + 4 ns + 4 bytes are read and 4 ni written.
+ * n_chunks == 1: the sequential form -- one lane walks a whole sequence; ws_bwd_tp and ws_gx may be NULL.  The only form for
+ *   ns == 0.
+ * n_chunks > 1 (a value wdf_ss_tp_chunks returns, ns >= 1): the call comes behind wdf_ss_bwd_tp with the same arguments on the
+ *   same stream, and ws_bwd_tp is that call's ws: the chunks' entering adjoints are re-walked from the records it left
+ *   (LAM_{K-1} = 0, LAM_{k-1} = Phi_k LAM_k + beta_k) into ws_gx (float [n_chunks][ns][B], wdf_ss_bwd_gx_ws_bytes bytes), then every
+ *   chunk runs from its own.  ws_bwd_tp is only read.
+ * Built for the sweeps' (ns, ni, root) combinations; any other answers WDF_EUNSUPPORTED before anything else is looked at but x,
+ * coef and the root arguments.  Every argument is checked before any device work.                                           */
+size_t wdf_ss_bwd_gx_ws_bytes(int ns, int64_t B, int n_chunks);            /* lamin; 0 when n_chunks == 1 */
+int wdf_ss_bwd_gx(const float* x, const float* coef, const float* rootp, int ns, int ni, int root, int n_up, int n_down,
+                  const float* zstash, const float* gy, const void* ws_bwd_tp, void* ws_gx, float* gx,
+                  int64_t B, int64_t T, int n_chunks, void* stream);
+
 /* One-pass training step of a small tree under WDF_ROOT_ASYM_PAIR (csrc/wdf_ss_asym_step.h): forward, loss and the gradient of
  * every coefficient and of the root's five values in one sweep -- x and target read once, y written once, no state stash, one
  * root solve per sample -- by carrying the state's forward-mode tangents.  ns in 1..2, ni in 1..2 for both losses; ns = 3
