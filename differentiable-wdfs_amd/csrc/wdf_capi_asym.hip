@@ -1,7 +1,7 @@
 // wdf_capi_asym.hip -- C ABI of the two-different-diode (asymmetric) clipper (csrc/wdf_asym.h, csrc/wdf_asym_step.h): sequential and
 // time-parallel forward / reverse sweep, the stand-alone root, the one-pass MSE and MSE + ESR steps.  Argument checking, workspace layouts,
 // template dispatch and launches.
-#include "wdf_capi_common.h"
+#include "wdf_capi_asym_checks.h"
 #include "wdf_asym.h"
 #include "wdf_asym_step.h"
 using namespace wdfcapi;
@@ -12,16 +12,7 @@ static_assert(WDF_ASYM_OMEGA_F32 == wdf::kAsymOmega && WDF_ASYM_NEWTON_F64 == wd
               "the header's mode numbers are the kernels'");
 using AsymModes = Values<int, wdf::kAsymOmega, wdf::kAsymNewton64, wdf::kAsymNewton32>;
 using NewtonModes = Values<int, wdf::kAsymNewton64, wdf::kAsymNewton32>;
-constexpr int kUnit = 8;                     // chunk lengths and warm-ups are multiples of 8 steps
-
-int asym_check(int64_t B, int64_t T, float fs, int mode)
-{
-    if (B <= 0 || T <= 0 || !(fs > 0.0f)) return fail(WDF_EINVAL, "B, T, fs must be positive");
-    if (mode < WDF_ASYM_OMEGA_F32 || mode > WDF_ASYM_NEWTON_F32) return fail(WDF_EINVAL, "unknown mode %d", mode);
-    return WDF_OK;
-}
-
-int newton_check(double tol, int max_iter) { return (!(tol > 0.0) || max_iter < 1) ? fail(WDF_EINVAL, "tol > 0, max_iter >= 1") : WDF_OK; }
+constexpr int kUnit = kAsymUnit;             // chunk lengths and warm-ups are multiples of 8 steps (wdf_capi_asym_checks.h, with asym_check and newton_check)
 
 // the sequential forward; with a gate: only the waves the verification flagged, the others leave at once
 // rseq != nullptr: one pot resistance per sequence (the RSEQ instantiations; Newton modes only: no closed-form twin is built)
@@ -98,15 +89,8 @@ int asym_step_common(const float* x, float* theta6, float fs, int mode, double t
                      int32_t* step, const float* lr, float beta1, float beta2, float eps, const float* lo, const float* hi, void* stream,
                      const char* what, const float* rseq = nullptr)
 {
-    int rc = asym_check(B, T, fs, mode);
+    int rc = asym_step_check(B, T, fs, mode, tol, max_iter, n_chunks, warmup, verify_tol, ws, z0, zT);
     if (rc) return rc;
-    if (mode == WDF_ASYM_OMEGA_F32)
-        return fail(WDF_EINVAL, "mode 0 (the closed form) has no one-pass step: use wdf_clipper_asym_fwd_tp + wdf_clipper_asym_bwd_tp");
-    if ((rc = newton_check(tol, max_iter))) return rc;
-    if (n_chunks < 1 || n_chunks > 65535 || warmup < 0 || !(verify_tol >= 0.0f))
-        return fail(WDF_EINVAL, "n_chunks in 1..65535, warmup >= 0, verify_tol >= 0");
-    if (!aligned8(ws)) return fail(WDF_EINVAL, "ws must be 8-byte aligned");
-    if (z0 && z0 == zT) return fail(WDF_EINVAL, "zT must not alias z0 (every chunk that starts at t = 0 reads z0)");
     if (LOSS != 0 && (skip < 0 || skip >= T)) return fail(WDF_EINVAL, "skip must be in 0..T-1");
     if ((rc = adam_check(m, v, step, lr))) return rc;
     const ChunkGeom g = chunk_geom(T, n_chunks, kUnit);

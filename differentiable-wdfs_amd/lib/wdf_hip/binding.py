@@ -225,6 +225,9 @@ SIGNATURES["wdf_ss_nl_eval"] = (_ci, _nl[:3] + _nl[4:11] + [_cd, _cd, _p, _p, _p
 # gscale, y, ws, sums, loss3, loss_out, B, T, n_chunks, z0, zT, stream
 SIGNATURES["wdf_ss_lin_eval_ws_bytes"] = (_sz, _STEP_WS)
 SIGNATURES["wdf_ss_lin_eval"] = (_ci, [_p, _p, _ci, _ci, _p, _i64, _cd, _cd, _cf, _p, _p, _p, _p, _p, _i64, _i64, _ci, _p, _p, _p])
+# the Gauss-Newton form of the two-different-diode clipper's MSE step: that step's arguments without the Adam tail (out28 for out7)
+SIGNATURES["wdf_clipper_asym_step_gn_ws_bytes"] = SIGNATURES["wdf_clipper_asym_step_mse_ws_bytes"]
+SIGNATURES["wdf_clipper_asym_step_gn"] = (_ci, SIGNATURES["wdf_clipper_asym_step_mse"][1][:-len(_ADAM) - 1] + [_p])
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
@@ -1342,6 +1345,37 @@ def clipper_asym_step_mse(x, theta6, fs, mode, target, gscale, n_chunks, warmup,
         _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws), _ptr(status), _ptr(out7), *adam, _stream())
     _check(rc, name)
     return y, zT, out7, status
+
+
+GN_TRI = tuple((q, r) for q in range(6) for r in range(q, 6))      # out28[7:28]: the upper triangle, row-major
+
+
+def clipper_asym_step_gn(x, theta6, fs, mode, target, gscale, n_chunks, warmup, tol=1e-12, max_iter=50, verify_tol=1e-6, y=None,
+                         z0=None, want_zT=False, ws=None, status=None, out28=None):
+    """The Gauss-Newton form of clipper_asym_step_mse (wdf_clipper_asym_step_gn): the same one pass over the data, which also
+    sums the products of the output's tangents.  out28 = {sse, g[6], H[21]}: g = gscale/2 d(sse)/d{Is_up, nVt_up, Is_down,
+    nVt_down, R, C} (clipper_asym_step_mse's out7[1:7]) and H = gscale sum_t (dy_t/dtheta_q)(dy_t/dtheta_r) for q <= r, the
+    upper triangle row-major (GN_TRI; gn_matrix() unpacks it) -- with gscale = 2/N the gradient of the mean squared error and
+    (2/N) J^T J.  mode: ASYM_NEWTON_F32 or ASYM_NEWTON_F64.  n_chunks is rounded like asym_chunks(); y, ws, status, out28 can
+    be preallocated.  theta6 is only read: a Levenberg-Marquardt optimizer (wdf_hip.lm) moves the parameters.
+    -> y [T,B], zT [B] | None, out28, status (int32[4]; read with mlp_tp_status())."""
+    x, theta6, target, z0, _, B, T, K, y, zT, ws, status, _ = _asym_step_args(
+        "clipper_asym_step_gn", lib().wdf_clipper_asym_step_gn_ws_bytes, x, theta6, mode, target, n_chunks, y, z0, want_zT, ws,
+        status, None, None)
+    out28 = _out(out28, 28, "out28", "{sse, g[6], H[21]}", x)
+    _check(lib().wdf_clipper_asym_step_gn(_ptr(x), _ptr(theta6), float(fs), int(mode), float(tol), int(max_iter), _ptr(target),
+                                          float(gscale), _ptr(y), _ptr(z0), _ptr(zT), B, T, K, int(warmup), float(verify_tol), _ptr(ws),
+                                          _ptr(status), _ptr(out28), _stream()), "wdf_clipper_asym_step_gn")
+    return y, zT, out28, status
+
+
+def gn_matrix(tri):
+    """The 21 values of out28[7:28] (any float tensor on any device) -> the symmetric [6,6] matrix, float64, same device."""
+    H = torch.zeros((6, 6), dtype=torch.float64, device=tri.device)
+    q, r = (torch.tensor(i, device=tri.device) for i in zip(*GN_TRI))
+    H[q, r] = tri.to(torch.float64)
+    H[r, q] = tri.to(torch.float64)
+    return H
 
 
 def clipper_asym_step_esr(x, theta6, fs, mode, target, n_global, eps_energy, skip, n_chunks, warmup, tol=1e-12, max_iter=50,

@@ -360,6 +360,57 @@ def clipper_asym_mse(theta6, x, target, fs, tp=None, mode=None, z0=None, return_
     return _ClipperAsymMseFn.apply(theta6, x, target, float(fs), tp, mode, z0, bool(return_state))
 
 
+class AsymGnStep:
+    """The Gauss-Newton form of AsymMseStep (csrc/wdf_asym_gn.h, binding.clipper_asym_step_gn): the same one pass over the
+    data, which also sums the products of the output's tangents.  Buffers are allocated once; run() fills self.y, self.status
+    and self.out = {sse, g[6], H[21]} (g the gradient of the mean over n_global, H = (2/n_global) J^T J, upper triangle) and
+    nothing synchronises.  tp, mode: as AsymMseStep (the MSE step's plan: plan_asym_time_parallel)."""
+
+    def __init__(self, B, T, fs, tp, device, mode=None, n_global=None, tol=1.0e-12, max_iter=50):
+        self.mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
+        if self.mode not in (binding.ASYM_NEWTON_F32, binding.ASYM_NEWTON_F64):
+            raise binding.WdfHipError(f"AsymGnStep: mode {self.mode} has no one-pass step (the Newton modes have)")
+        self.B, self.T, self.fs, self.tp = int(B), int(T), float(fs), tp
+        self.tol, self.max_iter = float(tol), int(max_iter)
+        self.n_global = float(n_global if n_global is not None else self.B * self.T)
+        self.gscale = 2.0 / self.n_global
+        k, self.warmup, self.verify_tol = (tp.k_fwd, tp.warmup, tp.tol) if tp is not None else (1, 0, 1.0e-6)
+        self.k = binding.asym_chunks(self.T, k)
+        self.ws = torch.empty((binding.lib().wdf_clipper_asym_step_gn_ws_bytes(self.B, self.k),), dtype=torch.uint8, device=device)
+        self.status = torch.zeros((4,), dtype=torch.int32, device=device)
+        self.out = torch.zeros((28,), dtype=torch.float32, device=device)     # {sse, g[6], H[21]}
+        self.y = torch.empty((self.T, self.B), dtype=torch.float32, device=device)
+
+    def run(self, theta6, x, target):
+        binding.clipper_asym_step_gn(x, theta6, self.fs, self.mode, target, self.gscale, self.k, self.warmup, tol=self.tol,
+                                     max_iter=self.max_iter, verify_tol=self.verify_tol, y=self.y, ws=self.ws, status=self.status,
+                                     out28=self.out)
+        return self.out
+
+
+_GN_STEPPERS = {}
+
+
+def clipper_asym_gn(theta6, x, target, fs, tp=None, mode=None):
+    """Loss, gradient and Gauss-Newton matrix of the two-different-diode clipper's mean squared error against target [T,B], in
+    ONE pass over the data (wdf_clipper_asym_step_gn; one stepper per shape, buffers reused).  theta6 = {Is_up, nVt_up,
+    Is_down, nVt_down, R, C}, float32[6] on the device.  mode: binding.ASYM_NEWTON_F32 (default) or binding.ASYM_NEWTON_F64.
+    tp: a TpPlan (plan_asym_time_parallel) or None for one chunk.  Stateless: the loop starts from zero.
+    -> loss (0-dim), g [6], H [6,6] symmetric, all float64 and detached, and y [T,B] -- the stepper's own buffer, overwritten
+    by the next call of this shape."""
+    mode = binding.ASYM_NEWTON_F32 if mode is None else int(mode)
+    B, T = x.shape
+    key = (B, T, float(fs), tp, mode, x.device)
+    st = _GN_STEPPERS.get(key)
+    if st is None:
+        if len(_GN_STEPPERS) > 8:
+            _GN_STEPPERS.clear()
+        st = _GN_STEPPERS[key] = AsymGnStep(B, T, fs, tp, x.device, mode=mode)
+    LAST_TP_STATUS["status"] = st.status
+    out = st.run(theta6.detach().contiguous(), x, target).to(torch.float64)
+    return out[0] / float(B * T), out[1:7], binding.gn_matrix(out[7:28]), st.y
+
+
 class AsymEsrStep:
     """The MSE + ESR training step of the two-different-diode clipper in one pass over the data (csrc/wdf_asym_step.h,
     binding.clipper_asym_step_esr): loss = S/n + sqrt(S / (E + eps) / n) on the rows past `skip` (clipper_pot.py:146-156,177,

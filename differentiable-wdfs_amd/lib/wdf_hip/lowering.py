@@ -1617,6 +1617,63 @@ class Circuit:
                                   time_major=True)
         return loss.as_subclass(tf.Tensor)
 
+    def _gn_parts(self):
+        """The six values [Is_up, nVt_up, Is_down, nVt_down, Vs.R, C] mse_gn() differentiates against, or the refusal, by name,
+        of every circuit the Gauss-Newton step (csrc/wdf_asym_gn.h) does not serve -- raised before a device is asked for."""
+        def refuse(what):
+            raise binding.WdfHipError(f"Circuit.mse_gn: {what} has no Gauss-Newton step: it serves the diode-clipper tree under "
+                                      "AsymDiodePair with a Newton solver (csrc/wdf_asym_gn.h), stateless")
+        if self.root_kind != "AsymDiodePair":
+            refuse(f"a {self.root_kind} root")
+        if getattr(self.root, "streamed", False):
+            refuse("AsymDiodePair(streamed=True) (the streamed-coefficient kernels)")
+        if self._asym_generic:
+            refuse("AsymDiodePair(any_tree=True) off the clipper's own kernels (the generic state-space kernels)")
+        if self.per_sequence_R is not None:
+            refuse("per_sequence_R (one pot per sequence)")
+        if self.root.mode == binding.ASYM_OMEGA_F32:
+            refuse("the omega_f32 solver (the closed form, a model approximation)")
+        dp, vs, cap = self.root, self.top.P1, self.top.P2
+        return [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, vs.R, cap.C]
+
+    @property
+    def gn_variables(self):
+        """The trainable Variables among [Is_up, nVt_up, Is_down, nVt_down, Vs.R, C], in that order: the rows and columns of
+        what mse_gn() returns."""
+        return [p for p in self._gn_parts() if isinstance(p, tf.Variable) and p.trainable]
+
+    def mse_gn(self, x, target, z0=None, carry_state=False):
+        """Loss, gradient and Gauss-Newton matrix of tf.reduce_mean(tf.square(self(x) - target)) in ONE pass over the data
+        (wdf_clipper_asym_step_gn: the one-pass MSE step, which holds dy_t/dtheta in registers at every sample, also sums
+        its products): -> (loss, g, H), detached device tensors, loss 0-dim, g [n] the gradient and H [n,n] = (2/N) J^T J,
+        symmetric, float64, over the n trainable Variables in the order of `circ.gn_variables`; rows and columns of values
+        that are not trainable are dropped.  What wdf_hip.lm.LevenbergMarquardt(lambda: circ.mse_gn(x, target),
+        circ.gn_variables) takes.  H is singular by construction (scaling Is_up, Is_down and C by s and R by 1/s leaves y
+        unchanged): judge a fit by its loss, never by the values.  Sets `circ.last_output` (the stepper's buffer, valid until
+        the next call of this shape).  Serves the clipper tree under AsymDiodePair with a Newton solver, from zero state;
+        every other circuit, z0 and carry_state raise."""
+        parts = self._gn_parts()
+        if z0 is not None or carry_state:
+            raise binding.WdfHipError("Circuit.mse_gn: z0 / carry_state has no Gauss-Newton step: the pass starts from zero state")
+        keep = [i for i, p in enumerate(parts) if isinstance(p, tf.Variable) and p.trainable]
+        if not keep:
+            raise binding.WdfHipError("Circuit.mse_gn: no trainable Variable among Is_up, nVt_up, Is_down, nVt_down, Vs.R, C")
+        binding.require_gpu()
+        from . import engine
+        anchor = x if isinstance(x, torch.Tensor) else None
+        x = torch.as_tensor(x).as_subclass(torch.Tensor)
+        x = (x if x.is_cuda else x.cuda()).float()
+        with torch.no_grad():
+            theta6, xv, _, tp = self._asym_inputs(x, anchor)
+        B, T = xv.shape
+        tgt = torch.as_tensor(target).as_subclass(torch.Tensor).to(x.device).float().reshape(T, B).contiguous()
+        loss, g, H, y = engine.clipper_asym_gn(theta6, xv, tgt, float(self.top.P2.FS), tp=tp, mode=self.root.mode)
+        self.last_output = y.as_subclass(tf.Tensor)
+        if len(keep) < 6:
+            idx = torch.tensor(keep, device=g.device)
+            g, H = g[idx], H[idx][:, idx]
+        return loss, g, H
+
     def _input_grad_route(self, x):
         """What __call__ does with an x that carries a graph (grad mode on, x.requires_grad): None for a plain x -- nothing
         changes; "generic" for the diode-pair clipper with host-resident Variables and no resistance channel (it takes the

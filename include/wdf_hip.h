@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too; + wdf_ss_lin_eval(_ws_bytes), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too; + wdf_ss_lin_eval(_ws_bytes), additions too; + wdf_clipper_asym_step_gn(_ws_bytes), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -885,6 +885,24 @@ int wdf_clipper_asym_step_esr(const float* x, float* theta6, float fs, int mode,
                               float* gtheta6, float* loss3, float* m, float* v, int32_t* step, const float* lr, float beta1,
                               float beta2, float eps, const float* lo, const float* hi, void* stream);
 int wdf_asym_esr_finish(const float* sums14, double n_global, double eps_energy, float* gtheta6, float* loss3, void* stream);
+
+/* The Gauss-Newton form of wdf_clipper_asym_step_mse (csrc/wdf_asym_gn.h), both NEWTON modes: the same single pass -- x and
+ * target read once, y written once, the same chunks, warm-up, verification, status words and gated repair launch -- that also
+ * sums the products of the output's tangents, which the pass holds in registers at every sample:
+ *   out28 (device float[28]) = {sum (y - target)^2 of this call,
+ *                               gscale/2 d(that sum)/d{Is_up, nVt_up, Is_down, nVt_down, R, C}                 (6, as out7[1:7]),
+ *                               gscale sum_t (dy_t/dtheta_q)(dy_t/dtheta_r), q <= r, row-major upper triangle  (21)}
+ * With gscale = 2/N: the gradient g of the mean squared error and H = (2/N) J^T J, what a Levenberg-Marquardt step solves
+ * (H + lambda D) delta = -g with.  H is singular by construction: scaling (Is_up, Is_down, C) by s and R by 1/s leaves y
+ * unchanged, so damping is part of any use of it.  No second sweep, no stored Jacobian; a chunk's record grows from the MSE
+ * step's 15 to 43 doubles per sequence and composes exactly.  There is no Adam in this launch and theta6 is only read.  Arguments
+ * and their checks are wdf_clipper_asym_step_mse's (WDF_ASYM_OMEGA_F32 is rejected; z0 optional, a constant of the call; zT
+ * optional, must not alias z0).  ws: wdf_clipper_asym_step_gn_ws_bytes bytes, 8-byte aligned, no initialisation needed.
+ * Additions to ABI 6: no existing signature changed. */
+size_t wdf_clipper_asym_step_gn_ws_bytes(int64_t B, int n_chunks);
+int wdf_clipper_asym_step_gn(const float* x, const float* theta6, float fs, int mode, double tol, int max_iter, const float* target,
+                             float gscale, float* y, const float* z0, float* zT, int64_t B, int64_t T, int n_chunks, int warmup,
+                             float verify_tol, void* ws, void* status, float* out28, void* stream);
 
 /* One pot resistance per SEQUENCE (clipper_pot.py's dataset: the pot is constant along a recording, dataimport.py:96): the
  * twins of the five entry points above, each its static twin's argument list with rseq behind x.  The contract:
