@@ -4,6 +4,7 @@
 #include "wdf_capi_common.h"
 #include "wdf_statespace.h"
 #include "wdf_ss_step.h"
+#include "wdf_capi_ss_lin_checks.h"
 using namespace wdfcapi;
 
 namespace {
@@ -368,20 +369,12 @@ int wdf_ss_probe_adam(const wdf_adam_job* jobs, int n_jobs, const int32_t* tape,
 // ---- the one-pass step of linear trees, MSE and MSE + ESR (wdf_ss_step.h) -----------------------------------------------
 namespace {
 
-bool lin_step_ok(int ns, int ni) { return ns >= 0 && ns <= 2 && ni >= 1 && ni <= 2; }
-int lin_step_d(int ns, int ni) { return ns * (1 + ns * ns + ns * ni); }
-int lin_step_g(int ns, int ni) { return ns * ns + ns * ni + ns + ni; }
-constexpr int kLinStepUnit = 32;
-
-// the ticket's line, the chunks' zero-state ends, a line of slack for the alignment, the waves' partial sums: `families` rows
-// of {gradient entries, sum of squares} per wave (1: MSE, 2: MSE + ESR)
+// (the trees served, the workspace walk and the MSE step's argument checks: wdf_capi_ss_lin_checks.h, shared with the Gauss-Newton
+//  step's translation unit)
+// `families` rows of {gradient entries, sum of squares} per wave (1: MSE, 2: MSE + ESR)
 size_t lin_step_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks, int families)
 {
-    if (!lin_step_ok(ns, ni) || B <= 0 || T <= 0 || n_chunks < 1) return 0;
-    const int K = chunk_geom(T, n_chunks, kLinStepUnit).K;
-    const size_t waves = waves64(B) * (size_t)K;
-    return 256 + (size_t)K * (size_t)lin_step_d(ns, ni) * (size_t)B * sizeof(float) + 256 +
-           waves * (size_t)(families * (lin_step_g(ns, ni) + 1)) * sizeof(double);
+    return lin_step_ws_rows(ns, ni, B, T, n_chunks, (size_t)(families * (lin_step_g(ns, ni) + 1)));
 }
 
 // Both losses' launches, arguments already checked: pass 1 where there is a state to carry across a chunk boundary, then pass 2
@@ -396,12 +389,13 @@ int lin_step_launch(const char* what, const float* x, const float* coef, const d
     const int K = g.K;
     const int64_t L = g.L;
     // the ticket, the chunks' zero-state ends and the waves' partial sums, each on a 256-byte line of its own (by ADDRESS)
-    unsigned* ticket = (unsigned*)ws;
-    float* uend0 = (float*)((char*)ws + 256);
-    double* part = (double*)round_up((uintptr_t)(uend0 + (size_t)K * (size_t)lin_step_d(ns, ni) * (size_t)B), 256);
+    const LinStepWs w = lin_step_ws(ws, ns, ni, B, K);
+    unsigned* ticket = w.ticket;
+    float* uend0 = w.uend0;
+    double* part = w.part;
     // two sequences per lane (8-byte loads and stores) when the rows of x, target, y and the workspace allow it, on every tree
     // and for both losses (no instantiation needs scratch for it: DESIGN.md's table)
-    const bool pair = (B % 2 == 0) && ((((uintptr_t)x | (uintptr_t)target | (uintptr_t)y | (uintptr_t)ws | (uintptr_t)z0 | (uintptr_t)zT) & 7u) == 0);
+    const bool pair = lin_step_pairs(B, x, target, y, ws, z0, zT);
     const int64_t per_wave = pair ? 128 : 64;
     const dim3 grid((unsigned)((B + per_wave - 1) / per_wave), (unsigned)K);
     const bool ok = dispatch([&](auto NS, auto NI, auto PAIR) {
@@ -420,10 +414,7 @@ int lin_step_mse(const char* what, const float* x, const float* coef, const doub
                  float gscale, float* y, void* ws, float* out, float* loss_out, float* gcoef_out, int64_t B, int64_t T, int n_chunks,
                  const float* z0, float* zT, void* stream)
 {
-    if (z0 && z0 == zT) return fail(WDF_EINVAL, "%s: zT must not alias z0 (every chunk reads z0)", what);
-    if (!x || !coef || !jac || !target || (STORE_Y && !y) || !ws || !out) return fail(WDF_EINVAL, "null argument");
-    if (!lin_step_ok(ns, ni)) return fail(WDF_EUNSUPPORTED, "%s: ns in 0..2, ni in 1..2 (got %d, %d)", what, ns, ni);
-    if (B <= 0 || T <= 0 || n_chunks < 1 || n_params < 1 || n_params > wdf::kProbeMaxParams) return fail(WDF_EINVAL, "B, T, n_chunks >= 1, 1..%d parameters", wdf::kProbeMaxParams);
+    if (int rc = lin_step_mse_check(what, x, coef, jac, n_params, ns, ni, target, STORE_Y, y, ws, out, B, T, n_chunks, z0, zT)) return rc;
     return lin_step_launch<0, STORE_Y>(what, x, coef, jac, n_params, ns, ni, target, y, ws, gcoef_out, B, T, n_chunks, z0, zT,
                                        wdf::LinMse{gscale, out, loss_out}, (hipStream_t)stream);
 }

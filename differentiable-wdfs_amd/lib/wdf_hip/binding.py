@@ -228,6 +228,9 @@ SIGNATURES["wdf_ss_lin_eval"] = (_ci, [_p, _p, _ci, _ci, _p, _i64, _cd, _cd, _cf
 # the Gauss-Newton form of the two-different-diode clipper's MSE step: that step's arguments without the Adam tail (out28 for out7)
 SIGNATURES["wdf_clipper_asym_step_gn_ws_bytes"] = SIGNATURES["wdf_clipper_asym_step_mse_ws_bytes"]
 SIGNATURES["wdf_clipper_asym_step_gn"] = (_ci, SIGNATURES["wdf_clipper_asym_step_mse"][1][:-len(_ADAM) - 1] + [_p])
+# the Gauss-Newton form of the linear trees' MSE step: that step's arguments (out and the matrix before the Jacobian are double)
+SIGNATURES["wdf_ss_lin_step_gn_ws_bytes"] = (_sz, _STEP_WS)
+SIGNATURES["wdf_ss_lin_step_gn"] = (_ci, list(SIGNATURES["wdf_ss_lin_step_mse"][1]))
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
@@ -1675,6 +1678,35 @@ def ss_lin_step_mse(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=
     _lin_step_call("wdf_ss_lin_step_mse", store_y, (_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), float(gscale)), y,
                    (_ptr(ws), _ptr(out), _ptr(loss), _ptr(gcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()))
     return {"y": y, "out": out, "loss": loss, "gcoef": gcoef, "zT": zT, "ws": ws}
+
+
+def sym_from_upper(tri, n):
+    """The symmetric [n,n] matrix whose upper triangle, by rows, is tri [n (n + 1) / 2] (a device gather: no synchronisation)."""
+    iu = torch.triu_indices(n, n, device=tri.device)
+    H = tri.new_zeros((n, n))
+    H[iu[0], iu[1]] = tri
+    H[iu[1], iu[0]] = tri
+    return H
+
+
+def ss_lin_step_gn(x_tm, coef, jac, target, gscale, n_chunks, z0=None, want_zT=False, want_hcoef=False, ws=None, y=None):
+    """The Gauss-Newton form of ss_lin_step_mse (wdf_ss_lin_step_gn, csrc/wdf_ss_lin_gn.h): the same pass also sums the products of
+    the per-row dy/d{A, Bx, cy, dy} and contracts them twice with jac.  Arguments, shape checks and buffers as ss_lin_step_mse
+    (always stores y); ws: zeroed wdf_ss_lin_step_gn_ws_bytes() bytes when not given.
+    -> dict: y [T,B], out float64 [1 + P + P (P + 1) / 2] = {SSE, d(gscale/2 SSE)/d param [P], H's upper triangle by rows},
+    H float64 [P,P] symmetric = gscale J^T J, loss (0-dim float32), hcoef float64 [kG (kG + 1) / 2] | None (sum d d^T over
+    {A, Bx, cy, dy} before the Jacobian, upper triangle by rows), zT [ns,B] | None, ws."""
+    x_tm, coef, target, z0, ns, ni, B, T, n_params, y, ws, zT = _lin_step_args("ss_lin_step_gn", lib().wdf_ss_lin_step_gn_ws_bytes, x_tm, coef,
+                                                                               jac, target, n_chunks, z0, want_zT, ws, y)
+    dev = x_tm.device
+    out = torch.empty((1 + n_params + n_params * (n_params + 1) // 2,), dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    kG = ns * ns + ns * ni + ns + ni
+    hcoef = torch.empty((kG * (kG + 1) // 2,), dtype=torch.float64, device=dev) if want_hcoef else None
+    _check(lib().wdf_ss_lin_step_gn(_ptr(x_tm), _ptr(coef), _ptr(jac), n_params, ns, ni, _ptr(target), float(gscale), _ptr(y), _ptr(ws),
+                                    _ptr(out), _ptr(loss), _ptr(hcoef), B, T, int(n_chunks), _ptr(z0), _ptr(zT), _stream()),
+           "wdf_ss_lin_step_gn")
+    return {"y": y, "out": out, "H": sym_from_upper(out[1 + n_params:], n_params), "loss": loss, "hcoef": hcoef, "zT": zT, "ws": ws}
 
 
 ESR_EPS = 2.220446049250313e-16      # what the scripts' esr_loss adds to the energy (clipper_pot.py:146-156: float64 machine epsilon)

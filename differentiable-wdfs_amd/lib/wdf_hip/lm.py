@@ -1,9 +1,11 @@
 """Levenberg-Marquardt on a handful of component values, driven by a Gauss-Newton evaluation.
 
     evaluate() -> (loss, g, H):  the loss, its gradient g [n] and the Gauss-Newton matrix H [n,n] ~ (2/N) J^T J at the current
-                                 values of `variables` (n of them, in g's order).  For the two-different-diode clipper:
+                                 values of `variables` (n of them, in g's order).  For the two-different-diode clipper
+                                 (csrc/wdf_asym_gn.h) and for a resident linear tree -- lpf.py's RC low-pass,
+                                 voltage_divider.py, after circ.to_device() (csrc/wdf_ss_lin_gn.h):
                                  lambda: circ.mse_gn(x, target) with variables = circ.gn_variables -- one pass over the data
-                                 on the device (csrc/wdf_asym_gn.h).
+                                 on the device.
 
 A step solves, on the host in float64,
 
@@ -16,7 +18,8 @@ otherwise every value is restored bit for bit, lambda <- lambda * up, and the st
 non-positive value (a component value is positive) is rejected without an evaluation.
 
 The six-parameter clipper has an exact gauge -- (Is_up, Is_down, C) -> s (Is_up, Is_down, C), R -> R / s leaves y unchanged --
-so its H is singular by construction and the damping is what makes the step well defined.  Judge a fit by its loss, never by
+so its H is singular by construction and the damping is what makes the step well defined.  The linear trees' H is singular as
+well: the RC low-pass's output depends on R C only, the voltage divider's on R1 / R2.  Judge a fit by its loss, never by
 the values.
 """
 import numpy as np

@@ -797,6 +797,41 @@ class _LinResident:
         binding._check(rc, "wdf_ss_lin_step_mse" if store_y else "wdf_ss_lin_step_mse_noy")
         return out, loss
 
+    # ---- the Gauss-Newton form of the linear step (csrc/wdf_ss_lin_gn.h) on entries of its own
+    def gn_entry(self, x, target):
+        """The buffers of one set the Gauss-Newton step runs on: an entry of its own per (x, target) pair -- its own workspace (the
+        MSE step's layout with larger partial rows) and output buffer; the MSE entry of the same pair is never touched."""
+        ent = self.cache.get((x, target), ("gn",))
+        if ent is None:
+            circ, dev = self.circ, self.pb.block.device
+            x_tm, tgt, B, T = self._resident_pair(x, target)
+            # (two sequences per lane when the rows pair up, except on two capacitors with two sources: one per lane there)
+            per_wave = 128 if (B % 2 == 0 and circ.ns * circ.ni != 4) else 64
+            k = max(1, min(T // 64, (_LIN_OCC * N_SIMD) // max(1, -(-B // per_wave))))     # the training entry's chunk formula
+            nbytes = binding.lib().wdf_ss_lin_step_gn_ws_bytes(circ.ns, circ.ni, B, T, k)
+            if nbytes == 0:
+                raise binding.WdfHipError(binding.lib().wdf_last_error().decode() or "wdf_ss_lin_step_gn_ws_bytes: unsupported tree")
+            ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+            y = torch.empty((T, B), dtype=torch.float32, device=dev)
+            ent = self.cache.put((x, target), {"x": x_tm, "t": tgt, "y": y, "ws": ws, "B": B, "T": T, "k": k}, ("gn",),
+                                 nbytes=_nbytes(x_tm, tgt, y, ws))
+        return ent
+
+    def gn_step(self, ent, z0=None):
+        """probe + the Gauss-Newton step -> out float64 [1 + n + n (n + 1) / 2] = {SSE, d(mean squared error)/d component value,
+        (2/N) J^T J's upper triangle by rows} over all n values of the block: a tensor of this call's own.  z0 [ns,B] float32 on
+        the device or None: a constant of the call.  The optimizer updates queued since the last step go out with the probe."""
+        circ = self.circ
+        self.probe()
+        B, T, n = ent["B"], ent["T"], self.pb.n
+        out = torch.empty((1 + n + n * (n + 1) // 2,), dtype=torch.float64, device=ent["t"].device)
+        rc = binding.lib().wdf_ss_lin_step_gn(binding._ptr(ent["x"]), binding._ptr(self.coef), binding._ptr(self.jac), n, circ.ns, circ.ni,
+                                              binding._ptr(ent["t"]), 2.0 / float(B * T), binding._ptr(ent["y"]), binding._ptr(ent["ws"]),
+                                              binding._ptr(out), None, None, B, T, ent["k"],
+                                              None if z0 is None else binding._ptr(z0), None, binding._stream())
+        binding._check(rc, "wdf_ss_lin_step_gn")
+        return out
+
 
 class _DynResident:
     """Circuit.to_device() of a circuit that runs on the streamed-coefficient kernels (per-sample impedance / an MLP root outside
@@ -1636,11 +1671,57 @@ class Circuit:
         dp, vs, cap = self.root, self.top.P1, self.top.P2
         return [dp.Is_up, dp.nVt_up, dp.Is_down, dp.nVt_down, vs.R, cap.C]
 
+    def _gn_lin(self):
+        """The resident linear tree mse_gn() runs on (csrc/wdf_ss_lin_gn.h) -- an ideal-source root, at most two capacitors and two
+        sources, made resident by to_device() -- or None for every other circuit (_gn_parts names those); such a tree whose
+        values still live on the host raises, naming to_device()."""
+        if self.root_kind != "IdealVoltageSource" or self._dyn or self.ns > 2 or self.ni > 2 or self.per_sample_R is not None:
+            return None
+        lin = getattr(self, "_lin", None)
+        if lin is None:
+            raise binding.WdfHipError("Circuit.mse_gn: a linear tree runs its Gauss-Newton step (csrc/wdf_ss_lin_gn.h) on component "
+                                      "values that live on the device: call circ.to_device() first")
+        return lin
+
+    @staticmethod
+    def _gn_lin_keep(lin):
+        """(index in the block, Variable) of every trainable Variable among the resident tree's component values, block order"""
+        return [(i, v) for i, v in sorted(lin.adopted.items()) if isinstance(v, tf.Variable) and v.trainable]
+
     @property
     def gn_variables(self):
-        """The trainable Variables among [Is_up, nVt_up, Is_down, nVt_down, Vs.R, C], in that order: the rows and columns of
-        what mse_gn() returns."""
+        """The rows and columns of what mse_gn() returns: the trainable Variables among [Is_up, nVt_up, Is_down, nVt_down, Vs.R, C],
+        in that order (the two-different-diode clipper), or among a resident linear tree's component values, in the order of its
+        parameter block (tree order)."""
+        lin = self._gn_lin()
+        if lin is not None:
+            return [v for _, v in self._gn_lin_keep(lin)]
         return [p for p in self._gn_parts() if isinstance(p, tf.Variable) and p.trainable]
+
+    def _mse_gn_lin(self, lin, x, target, z0, carry_state):
+        """mse_gn() on a resident linear tree: probe + wdf_ss_lin_step_gn on an entry of its own per (x, target) pair."""
+        if carry_state:
+            raise binding.WdfHipError("Circuit.mse_gn: carry_state has no Gauss-Newton step: a rejected Levenberg-Marquardt trial would "
+                                      "have moved the carried state; hand the state in as z0 (a constant of the call)")
+        if not (isinstance(x, torch.Tensor) and isinstance(target, torch.Tensor)):
+            raise binding.WdfHipError("Circuit.mse_gn: a resident linear tree takes x and target as tensors (the resident set is kept "
+                                      "per tensor pair)")
+        keep = self._gn_lin_keep(lin)
+        if not keep:
+            raise binding.WdfHipError("Circuit.mse_gn: no trainable Variable among the tree's component values")
+        binding.require_gpu()
+        with torch.no_grad(), torch._C.DisableTorchFunctionSubclass():
+            lin.check()
+            ent = lin.gn_entry(x, target)
+            z0d = self._z0_device(z0, ent["t"].device, ent["B"]) if self.ns > 0 else None
+            out = lin.gn_step(ent, z0d)
+            n = lin.pb.n
+            loss, g, H = out[0] / float(ent["B"] * ent["T"]), out[1:1 + n], binding.sym_from_upper(out[1 + n:], n)
+            if len(keep) < n:
+                idx = torch.tensor([i for i, _ in keep], device=g.device)
+                g, H = g[idx], H[idx][:, idx]
+        self.last_output = ent["y"].as_subclass(tf.Tensor)
+        return loss, g, H
 
     def mse_gn(self, x, target, z0=None, carry_state=False):
         """Loss, gradient and Gauss-Newton matrix of tf.reduce_mean(tf.square(self(x) - target)) in ONE pass over the data
@@ -1650,8 +1731,14 @@ class Circuit:
         that are not trainable are dropped.  What wdf_hip.lm.LevenbergMarquardt(lambda: circ.mse_gn(x, target),
         circ.gn_variables) takes.  H is singular by construction (scaling Is_up, Is_down and C by s and R by 1/s leaves y
         unchanged): judge a fit by its loss, never by the values.  Sets `circ.last_output` (the stepper's buffer, valid until
-        the next call of this shape).  Serves the clipper tree under AsymDiodePair with a Newton solver, from zero state;
-        every other circuit, z0 and carry_state raise."""
+        the next call of this shape).  Serves the clipper tree under AsymDiodePair with a Newton solver, from zero state
+        (z0 and carry_state raise there), and a resident linear tree (to_device(); lpf.py, voltage_divider.py:
+        wdf_ss_lin_step_gn, loss float64 too): there z0 [ns,B] is served, a constant of the call, carry_state raises (a rejected
+        trial would have moved the carried state), and H is singular as well -- y depends on R C, or on R1 / R2, only.  Every
+        other circuit raises, by name."""
+        lin = self._gn_lin()
+        if lin is not None:
+            return self._mse_gn_lin(lin, x, target, z0, carry_state)
         parts = self._gn_parts()
         if z0 is not None or carry_state:
             raise binding.WdfHipError("Circuit.mse_gn: z0 / carry_state has no Gauss-Newton step: the pass starts from zero state")

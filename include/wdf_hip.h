@@ -35,7 +35,7 @@ extern "C" {
  * the header are exported (tests/test_cabi_cpu.py compares `nm -D` with this header both ways). */
 #pragma GCC visibility push(default)
 
-#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too; + wdf_ss_lin_eval(_ws_bytes), additions too; + wdf_clipper_asym_step_gn(_ws_bytes), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
+#define WDF_HIP_ABI_VERSION 6   /* 6: wdf_ss_lin_step_mse takes z0 / zT (round 6); exports limited to this header; + wdf_clipper_asym_step_mse(_ws_bytes), an addition: no existing signature changed; + wdf_loss_terms_ws_bytes / _sums / _coef / _grad, additions too; + WDF_NO_Y_STORE and wdf_ss_lin_step_mse_noy / _esr_noy, additions too (no existing signature changed); + wdf_clipper_eval_tp(_ws_bytes, _ws_init), additions too; + wdf_clipper_mlp_eval, an addition too; + wdf_ss_nl_eval(_ws_bytes, _plan, _set, _read), additions too; + wdf_ss_lin_eval(_ws_bytes), additions too; + wdf_clipper_asym_step_gn(_ws_bytes), additions too; + wdf_ss_lin_step_gn(_ws_bytes), additions too.  5: + wdf_clipper_asym_bwd_tp, wdf_ss_dyn_* (round 5).  3: + wdf_clipper_mlp_step_* (round 4); TpCtl is 128 bytes, warm-up units are 16 steps.  4: + wdf_ss_nl_step_*; the linear step's workspace shrank */
 
 enum {
     WDF_OK = 0,
@@ -443,6 +443,27 @@ size_t wdf_ss_lin_eval_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chun
 int wdf_ss_lin_eval(const float* x, const float* coef, int ns, int ni, const float* target, int64_t skip, double n_global,
                     double eps_energy, float gscale, float* y, void* ws, double* sums, float* loss3, float* loss_out,
                     int64_t B, int64_t T, int n_chunks, const float* z0, float* zT, void* stream);
+
+/* The Gauss-Newton form of wdf_ss_lin_step_mse (csrc/wdf_ss_lin_gn.h; additions to ABI 6: no existing signature changed).  Pass 2 of
+ * the MSE step forms d_i = dy/d coefficient_i at every row, from an exact chunk start, for the kG = ns^2 + ns ni + ns + ni entries
+ * of {A, Bx, cy, dy}; this step also sums their products, Hc_ij = sum d_i d_j (i <= j), and its finishing wave applies the
+ * chain rule twice in float64:
+ *   out (device DOUBLE [1 + P + P (P + 1) / 2], P = n_params) = {sum (y - target)^2,
+ *                               d(gscale/2 x that sum)/d component value                                     (P, as the MSE step's out[1:]),
+ *                               H_qr = gscale sum_ij jac[row_i][q] Hc_ij jac[row_j][r], q <= r, upper triangle by rows}
+ * With gscale = 2/N: the gradient of the mean squared error and H = (2/N) J^T J, what a Levenberg-Marquardt step solves with.
+ * y, zT, the sum of squares and the gradient are the MSE step's (bit for bit where both run at the same lane width).
+ *   loss_out   (or NULL) float <- gscale/2 x the sum, as the MSE step's
+ *   hcoef_out  (or NULL) double [kG (kG + 1) / 2] <- Hc before the Jacobian, upper triangle by rows
+ *   ws         wdf_ss_lin_step_gn_ws_bytes() bytes (the MSE step's layout with kG + 1 + kG (kG + 1) / 2 doubles per wave), ZERO
+ *              before the first call; the step leaves it clean.  Not interchangeable with the MSE step's workspace.
+ * Every other argument, and every check (made before any HIP call, in the same words), is wdf_ss_lin_step_mse's; out, hcoef_out
+ * and ws must be 8-byte aligned.  Two sequences per lane where the MSE step pairs them up, except ns = ni = 2 (one per lane).
+ * wdf_ss_lin_step_gn_ws_bytes: 0 on bad arguments. */
+size_t wdf_ss_lin_step_gn_ws_bytes(int ns, int ni, int64_t B, int64_t T, int n_chunks);
+int wdf_ss_lin_step_gn(const float* x, const float* coef, const double* jac, int n_params, int ns, int ni, const float* target,
+                       float gscale, float* y, void* ws, double* out, float* loss_out, double* hcoef_out, int64_t B, int64_t T,
+                       int n_chunks, const float* z0, float* zT, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The one-pass MSE training step of small trees with a DIODE-PAIR root (csrc/wdf_ss_nl_step.h): the same epoch
